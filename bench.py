@@ -77,6 +77,9 @@ def parse():
                     help="pictures of the one extra scorer run at os.cpu_count() threads (torch-CPU is 4-6x slower at the box's 256 "
                          "hardware threads than at 20; reported, never the baseline unless it wins)")
     ap.add_argument("--cpu-full", action="store_true", help="kept for compatibility: the defaults are the 8(d) protocol now")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed round returned (class prior and weights, region scores, selected "
+                         "regions) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (see dump_outputs)")
     return ap.parse_args()
 
 
@@ -180,6 +183,7 @@ class ScanRound:
         n, simg, sid, ssc = select_regions(self.backend, self.rnd.plan, scores, None, self.rank_t, self.rank_t, self.cost, self.budget,
                                            self.budget + 1)
         self.tail_ev[1].record()
+        self.cls_w = cls_w
         self.scores = scores
         self.selected = (simg, sid, ssc)
         return n
@@ -211,6 +215,31 @@ def timed_scan_round(args, dev, rank, world, backend, bufs, ramp=None):
     n_selected = timed.run(True)
     fence()
     return timed, n_selected, max_over_ranks(time.perf_counter() - t0, dev)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, timed, n_selected):
+    """--dump-outputs: what the timed round handed its caller after its last step -- the class prior (f64 [C]) and class weights
+    (f32 [C]) of exchange 1, the region scores of the whole pool (f32 [N*K*B, S]) and the consumed prefix of the budget walk
+    (picture, region id, score) -- as DIR/<name>.npy.  The inputs depend on the arguments only (seeded generators), so two builds
+    can be compared file for file.  When the arrays exceed DUMP_LIMIT_BYTES together, every one of them is cut to the same fraction
+    of its rows: rows ``np.sort(np.random.RandomState(0).choice(n, k, replace=False))``, a fixed sample for fixed arguments."""
+    simg, sid, ssc = (np.asarray(a)[:n_selected] for a in timed.selected)
+    arrays = {"class_prior": np.asarray(timed.rnd.cum, dtype=np.float64),
+              "class_weights": timed.cls_w.cpu().numpy().astype(np.float32),
+              "region_scores": timed.scores.cpu().numpy().astype(np.float32),
+              "selected_picture": simg.astype(np.float64),
+              "selected_region": sid.astype(np.float64),
+              "selected_score": ssc.astype(np.float32)}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim > 0 and len(a) > 1:
+            k = max(1, len(a) * DUMP_LIMIT_BYTES // total)
+            a = a[np.sort(np.random.RandomState(0).choice(len(a), k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -920,6 +949,8 @@ def main():
             z, spx = bufs[k % args.nbuf]
             ops.single_pass_accum(z, spx, S, invT, prob_sum=p0, class_sum=c0, hist=h0)
     timed, n_selected, dt = timed_scan_round(args, dev, rank, world, backend, bufs, ramp)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed, n_selected)
 
     sp_ms = float(np.mean([a.elapsed_time(b) for a, b in timed.events]))
     tail_ms = float(timed.tail_ev[0].elapsed_time(timed.tail_ev[1]))

@@ -154,12 +154,15 @@ def _loss_inputs():
 def _run_loss(rank, world, port, out_dir):
     sys.path.insert(0, HERE)
     sys.path.insert(0, ROOT)
+    from helpers import OracleLossOps
+    from mulactseg_amd.utils import loss as loss_mod
+    # the world-1 run happens in the pytest process itself: the stand-in and the thread count are put back afterwards, so that later
+    # tests in the same process get the product's ops
+    product_ops, threads = loss_mod.ops, torch.get_num_threads()
     torch.set_num_threads(1)
     if world > 1:
         dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
     try:
-        from helpers import OracleLossOps
-        from mulactseg_amd.utils import loss as loss_mod
         loss_mod.ops = OracleLossOps                      # the scans come from oracle/exact.c; everything else is the product code
         z, tgt, spx, msk, S = _loss_inputs()
         per = z.shape[0] // world
@@ -176,6 +179,8 @@ def _run_loss(rank, world, port, out_dir):
         torch.save(dict(losses=torch.stack([group, ce, mc]).detach(), grad=g, acc=crit.last_acc.clone()),
                    os.path.join(out_dir, "loss_w%d_r%d.pt" % (world, rank)))
     finally:
+        loss_mod.ops = product_ops
+        torch.set_num_threads(threads)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()

@@ -1,12 +1,12 @@
-"""Readers of the reference's on-disk formats, on synthetic files; when the reference tree is mounted (build container
-only) additionally on its own init data (2 975 Cityscapes images, 6 092 789 valid regions)."""
+"""Readers of the reference's on-disk formats, on synthetic files and on the reference's own Cityscapes init data (2 975
+images, 6 092 789 valid regions), stored gzip-compressed under tests/golden/."""
+import gzip
 import json
 import os
 import pickle
 import tempfile
 
 import numpy as np
-import pytest
 import torch
 
 from mulactseg_amd.dataloader import formats
@@ -46,9 +46,12 @@ def test_multi_hot_from_labels_and_selection_mask():
     assert np.array_equal(m.numpy(), np.isin(np.array([[0, 5, 1], [3, 2, 5]]), [1, 3]))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/dataloader/init_data/cityscapes"), reason="reference tree not mounted")
-def test_reference_init_data_parses():
-    base = "/root/reference/dataloader/init_data/cityscapes"
+def test_reference_init_data_parses(golden_dir, tmp_path):
+    # dataloader/init_data/cityscapes/{train_seed2048.dict, train_seed2048_or.txt} of the reference, byte for byte
+    base = str(tmp_path)
+    for name in ("train_seed2048.dict", "train_seed2048_or.txt"):
+        with gzip.open(os.path.join(golden_dir, "cityscapes_" + name + ".gz"), "rb") as src, open(os.path.join(base, name), "wb") as dst:
+            dst.write(src.read())
     ids = formats.load_region_dict(os.path.join(base, "train_seed2048.dict"))
     assert len(ids) == 2975 and sum(len(v) for v in ids.values()) == 6092789
     im_idx, suppix = formats.read_datalist(os.path.join(base, "train_seed2048_or.txt"), "/data/Cityscapes", ids, known_ignore=True)
