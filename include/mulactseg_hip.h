@@ -52,8 +52,9 @@ extern "C" {
  * should have bumped it and did not); 5 = round 5 (mas_single_pass_accum_lowres_opt replaces the process-wide
  * mas_single_pass_lowres_generic switch; mas_test_occupy moved to the test-support library; the BatchNorm-fused forms of
  * mas_conv_bx_fwd); 6 = role 2 of mas_conv_bx_pack / _packed_bytes / _pack_job and ksize 3 at stride 2 in mas_conv_bx_supported /
- * mas_conv_bx_fwd (a library of version 5 answers "unsupported" to both). */
-#define MAS_ABI_VERSION 7
+ * mas_conv_bx_fwd (a library of version 5 answers "unsupported" to both); 8 = the region-label entry points of the data-generation
+ * step (mas_region_label_counts, mas_region_multi_hot, mas_region_dominant, mas_region_paint). */
+#define MAS_ABI_VERSION 8
 int mas_abi_version(void);
 const char* mas_error_string(int code);
 
@@ -244,6 +245,43 @@ int mas_dominant_hist(const int32_t* dominant, int64_t n, int C, uint64_t* count
  *   u <- (u - min(u[u != 0])) / max(u - min(u[u != 0]))     over all n region scores.
  * scratch2: 2 x uint32 of caller-owned device scratch. */
 int mas_minmax_normalize(float* scores, int64_t n, uint32_t* scratch2, void* stream);
+
+/* =============================================================================================
+ * Region labels of one picture: the data-generation step (tools/label_assignment_tensor[_voc].py,
+ * tools/label_assignment_dominant[_voc].py).  spx: superpixel ids [H,W] of type spx_dtype (MAS_ID_I64 / _I32 / _U16);
+ * labels: uint8 [H,W], train ids in [0,C) or 255 = ignore.  Ids outside [0,nseg) belong to no region.  listed: uint8 [nseg],
+ * non-zero for the ids the region dict lists for this picture.
+ * ============================================================================================= */
+
+/* status bit of mas_region_label_counts: some label is neither in [0,C) nor 255 (those pixels are not counted) */
+#define MAS_LABELS_BAD_VALUE 1
+
+/* full[p*(C+1) + c]: pixels of id p whose label is c (column C: label 255); with trim_k (odd, 1..15; 0 = no trimming)
+ * trimmed[...] the same over the pixels outside the thick superpixel boundary dilated by a trim_k x trim_k square
+ * (dataloader/region_cityscapes_tensor.py:47-56: find_boundaries(mode='thick') + binary_dilation).  full, trimmed and the
+ * status word are zeroed here; trimmed may be NULL when trim_k == 0.  Replaces the per-id np.unique of :58-84 and :38-50 of
+ * region_cityscapes_dominant_all.py. */
+int mas_region_label_counts(const void* spx, int spx_dtype, const uint8_t* labels, int H, int W, int nseg, int num_classes, int trim_k,
+                            int32_t* full /* [nseg, C+1] */, int32_t* trimmed /* [nseg, C+1] or NULL */, int32_t* status /* [1] */,
+                            void* stream);
+
+/* The multi-hot rows of region_cityscapes_tensor.py:58-84: for a listed id, the trimmed counts when that region is not empty
+ * (trimmed != NULL), otherwise the full ones; bits[p*(C+1) + c] = count > 0, size[p] = pixels of the region used.  Unlisted ids:
+ * zero row, size -1. */
+int mas_region_multi_hot(const int32_t* full, const int32_t* trimmed, const uint8_t* listed, int nseg, int num_classes,
+                         uint8_t* bits /* [nseg, C+1] */, int64_t* size /* [nseg] */, void* stream);
+
+/* choice[p]: the dominant value of listed id p (region_cityscapes_dominant_all.py:41-49): the most frequent label of the id's pixels,
+ * ties to the smaller value; with generate_ignore the value 255 competes (and loses ties), without it ignore pixels are left out.
+ * drawn != NULL (the _sample variant): drawn[p] is the column (0..C, or -1) the host drew instead.  -1 = leave the pixels alone
+ * (unlisted id, or no pixel counted). */
+int mas_region_dominant(const int32_t* full, const uint8_t* listed, const int32_t* drawn /* [nseg] or NULL */, int nseg, int num_classes,
+                        int generate_ignore, int32_t* choice /* [nseg] */, void* stream);
+
+/* out[i] = choice[spx[i]] where that is >= 0 (and, without generate_ignore, labels[i] != 255), else labels[i]: the dominant-label
+ * map of region_cityscapes_dominant_all.py:41-53. */
+int mas_region_paint(const void* spx, int spx_dtype, const uint8_t* labels, int H, int W, int nseg, const int32_t* choice,
+                     int generate_ignore, uint8_t* out /* [H,W] */, void* stream);
 
 /* =============================================================================================
  * mIoU counters

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("MAS_LIB") or os.path.join(_HERE, "libmulactseg_hip.so
 
 ID_I64, ID_I32, ID_U16 = 0, 1, 2
 MAX_CLASSES = 32
+LABELS_BAD_VALUE = 1
 SCORE_FRAC, PROB_FRAC, LOSS_FRAC = 40, 23, 32
 LOSS_CE, LOSS_GROUP, LOSS_GROUP_ONLY_MULTI, LOSS_DECOMP, LOSS_TCE = 1, 2, 4, 8, 16
 ACC_WORDS = 8
@@ -19,7 +20,7 @@ GRAD_FRAC = 44
 
 SK_DMA, SK_NOSPLIT = 1, 2
 LOWRES_GENERIC = 1
-ABI_VERSION = 7        # MAS_ABI_VERSION of include/mulactseg_hip.h this table was written against (load() refuses any other library)
+ABI_VERSION = 8        # MAS_ABI_VERSION of include/mulactseg_hip.h this table was written against (load() refuses any other library)
 
 _c = ctypes
 _vp, _i, _f, _i64, _d = _c.c_void_p, _c.c_int, _c.c_float, _c.c_int64, _c.c_double
@@ -44,6 +45,10 @@ SIGNATURES = {
     "mas_region_reweight": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "mas_dominant_hist": (_i, [_vp, _i64, _i, _vp, _vp]),
     "mas_minmax_normalize": (_i, [_vp, _i64, _vp, _vp]),
+    "mas_region_label_counts": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "mas_region_multi_hot": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "mas_region_dominant": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "mas_region_paint": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "mas_iou_counts": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _vp]),
     "mas_logits_iou_counts": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i64, _vp, _vp]),
     "mas_single_pass_accum": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),

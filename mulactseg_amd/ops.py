@@ -542,6 +542,124 @@ def dominant_hist(dominant, C):
 
 
 # ------------------------------------------------------------------------------------------------
+# Region labels of the data-generation step (csrc/labels.hip): multi-hot rows and dominant-label maps
+# ------------------------------------------------------------------------------------------------
+MAX_TRIM_KERNEL = 15
+
+
+def trim_kernel(trim_kernel_size):
+    """``None`` / 0 -> 0 (no trimming); odd 1..15 -> itself; anything else is an argument error."""
+    k = int(trim_kernel_size or 0)
+    if k and (k < 0 or k > MAX_TRIM_KERNEL or k % 2 == 0):
+        raise ValueError("trim kernel size must be odd and in 1..%d, got %d" % (MAX_TRIM_KERNEL, k))
+    return k
+
+
+def _label_picture(labels, superpixel, nseg, num_classes):
+    _need(labels, "labels", torch.uint8)
+    _need(superpixel, "superpixel")
+    code = _id_code(superpixel)
+    if labels.dim() != 2 or tuple(superpixel.shape) != tuple(labels.shape):
+        raise ValueError("labels and superpixel must be [H,W] of one shape, got %s and %s"
+                         % (tuple(labels.shape), tuple(superpixel.shape)))
+    if nseg < 1:
+        raise ValueError("nseg must be positive")
+    if not 1 <= num_classes < _lib.MAX_CLASSES:
+        raise ValueError("num_classes + 1 must be in 2..%d, got %d" % (_lib.MAX_CLASSES, num_classes + 1))
+    return code
+
+
+def listed_ids(ids, nseg, device):
+    """uint8 [nseg] on ``device``: 1 for the ids of the region dict's list (ids outside [0, nseg) are an argument error)."""
+    a = np.asarray(ids, dtype=np.int64).reshape(-1)
+    if a.size and (a.min() < 0 or a.max() >= nseg):
+        raise ValueError("listed superpixel ids must be in [0, %d)" % nseg)
+    lut = np.zeros(nseg, dtype=np.uint8)
+    lut[a] = 1
+    return torch.from_numpy(lut).to(device)
+
+
+def _raise_on_label_status(status, num_classes):
+    if int(status.item()) & _lib.LABELS_BAD_VALUE:
+        raise ValueError("label map holds values outside [0, %d) and 255" % num_classes)
+
+
+def _label_counts(labels, superpixel, nseg, num_classes, k):
+    code = _label_picture(labels, superpixel, nseg, num_classes)
+    H, W = labels.shape
+    dev = labels.device
+    full = torch.empty((nseg, num_classes + 1), dtype=torch.int32, device=dev)
+    trimmed = torch.empty_like(full) if k else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mas_region_label_counts(superpixel.data_ptr(), code, labels.data_ptr(), H, W, nseg, num_classes, k,
+                                                       full.data_ptr(), trimmed.data_ptr() if k else None, status.data_ptr(),
+                                                       _stream(labels)), "mas_region_label_counts")
+    return full, trimmed, status
+
+
+def region_label_counts(labels, superpixel, nseg, num_classes, trim_kernel_size=None):
+    """(full, trimmed): int32 ``[nseg, num_classes + 1]`` label histograms per superpixel id (last column: label 255), over all
+    pixels of the id and over those outside the dilated thick boundary (``None`` without trimming) --
+    ``region_cityscapes_tensor.py:47-66``.  labels: uint8 [H,W]; superpixel: int64 / int32 / uint16 (int16) [H,W].  Reads back one
+    status word (a label outside [0, C) and 255 is a ValueError)."""
+    full, trimmed, status = _label_counts(labels, superpixel, nseg, num_classes, trim_kernel(trim_kernel_size))
+    _raise_on_label_status(status, num_classes)
+    return full, trimmed
+
+
+def region_multi_hot(labels, superpixel, ids, nseg, num_classes, trim_kernel_size=None):
+    """(bits uint8 ``[nseg, num_classes + 1]``, size int64 ``[nseg]``): the multi-hot rows of one picture --
+    ``region_cityscapes_tensor.py:23-86``.  ``ids``: the listed superpixel ids (region dict), or a uint8 [nseg] device mask."""
+    k = trim_kernel(trim_kernel_size)
+    full, trimmed, status = _label_counts(labels, superpixel, nseg, num_classes, k)
+    listed = ids if torch.is_tensor(ids) else listed_ids(ids, nseg, labels.device)
+    _need(listed, "listed", torch.uint8)
+    if listed.numel() != nseg:
+        raise ValueError("listed must be uint8 [nseg]")
+    bits = torch.empty((nseg, num_classes + 1), dtype=torch.uint8, device=labels.device)
+    size = torch.empty(nseg, dtype=torch.int64, device=labels.device)
+    with torch.cuda.device(labels.device):
+        _lib.check(_lib.load().mas_region_multi_hot(full.data_ptr(), trimmed.data_ptr() if k else None, listed.data_ptr(), nseg,
+                                                    num_classes, bits.data_ptr(), size.data_ptr(), _stream(labels)),
+                   "mas_region_multi_hot")
+    _raise_on_label_status(status, num_classes)
+    return bits, size
+
+
+def region_dominant(labels, superpixel, ids, nseg, num_classes, generate_ignore=False, draw=None):
+    """uint8 [H,W]: the dominant-label map of one picture -- ``region_cityscapes_dominant_all.py:24-62``.  ``draw`` (the ``_sample``
+    variant, ``region_cityscapes_dominant_all_sample.py``): a host callable ``full -> int32 [nseg]`` that receives the int32
+    ``[nseg, num_classes + 1]`` counts as a numpy array and returns the drawn column per id (-1: none); it replaces the arg-max."""
+    full, _, status = _label_counts(labels, superpixel, nseg, num_classes, 0)
+    code = _id_code(superpixel)
+    listed = ids if torch.is_tensor(ids) else listed_ids(ids, nseg, labels.device)
+    _need(listed, "listed", torch.uint8)
+    if listed.numel() != nseg:
+        raise ValueError("listed must be uint8 [nseg]")
+    drawn = None
+    if draw is not None:
+        _raise_on_label_status(status, num_classes)
+        d = np.ascontiguousarray(draw(full.cpu().numpy()), dtype=np.int32)
+        if d.shape != (nseg,) or d.min() < -1 or d.max() > num_classes:
+            raise ValueError("draw() must return int32 [nseg] columns in -1..%d" % num_classes)
+        drawn = torch.from_numpy(d).to(labels.device)
+    H, W = labels.shape
+    choice = torch.empty(nseg, dtype=torch.int32, device=labels.device)
+    out = torch.empty_like(labels)
+    gi = 1 if generate_ignore else 0
+    with torch.cuda.device(labels.device):
+        lib, st = _lib.load(), _stream(labels)
+        _lib.check(lib.mas_region_dominant(full.data_ptr(), listed.data_ptr(), drawn.data_ptr() if drawn is not None else None, nseg,
+                                           num_classes, gi, choice.data_ptr(), st), "mas_region_dominant")
+        _lib.check(lib.mas_region_paint(superpixel.data_ptr(), code, labels.data_ptr(), H, W, nseg, choice.data_ptr(), gi,
+                                        out.data_ptr(), st), "mas_region_paint")
+    if draw is None:
+        _raise_on_label_status(status, num_classes)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # K9: stage-2 cosine pseudo labels
 # ------------------------------------------------------------------------------------------------
 def stage2_pseudo_labels(feats, logits, targets, spmasks, superpixels, include_onehot=True):
