@@ -53,8 +53,8 @@ extern "C" {
  * mas_single_pass_lowres_generic switch; mas_test_occupy moved to the test-support library; the BatchNorm-fused forms of
  * mas_conv_bx_fwd); 6 = role 2 of mas_conv_bx_pack / _packed_bytes / _pack_job and ksize 3 at stride 2 in mas_conv_bx_supported /
  * mas_conv_bx_fwd (a library of version 5 answers "unsupported" to both); 8 = the region-label entry points of the data-generation
- * step (mas_region_label_counts, mas_region_multi_hot, mas_region_dominant, mas_region_paint). */
-#define MAS_ABI_VERSION 8
+ * step (mas_region_label_counts, mas_region_multi_hot, mas_region_dominant, mas_region_paint); 9 = mas_ms_ensemble. */
+#define MAS_ABI_VERSION 9
 int mas_abi_version(void);
 const char* mas_error_string(int code);
 
@@ -420,6 +420,19 @@ int mas_train_augment(const uint8_t* img, int H, int W, int th, int tw, const in
  * bwd requires Wo <= 6 * Wi. */
 int mas_upsample_bilinear_fwd(const float* x, int64_t NC, int Hi, int Wi, int Ho, int Wo, float* y, void* stream);
 int mas_upsample_bilinear_bwd(const float* gy, int64_t NC, int Hi, int Wi, int Ho, int Wo, float* gx, void* stream);
+
+/* The multi-scale + flip ensemble of the VOC stage-2 generator (trainer/eval_save_cosplbl_prop_includeonehot_voc_ms.py:56-79) in one
+ * launch.  n <= MAS_MS_MAX_SOURCES sources; source k: feats_q[k] f32 [Ch,hq,wq] (unit-norm point features at quarter resolution),
+ * logits_q[k] f32 [C,hq,wq], geometry[5k..5k+4] = (hq, wq, Hs, Ws, flip): the scaled picture the network saw (Hs x Ws, hq <= Hs,
+ * wq <= Ws) and whether it was flipped horizontally.  Per channel and output pixel: stage 1 = the x4 upsampling of feat_forward
+ * (quarter -> Hs x Ws, the arithmetic of mas_upsample_bilinear_fwd), flipped back, stage 2 = F.interpolate(bilinear,
+ * align_corners=False) to H x W with the same arithmetic, summed in source order and divided by (float)n; the features are then
+ * divided by max(sqrtf(sum over channels of m*m, channel order), 1e-12).  feat_out f32 [Ch,H,W], logit_out f32 [C,H,W].  The per-source
+ * pointers and geometry travel as a by-value kernel argument (host arrays here, no device table).  MAS_ERR_RANGE when n is out of
+ * range or a stage-2 downsample needs more LDS than one tile may use (factors up to ~2 fit). */
+#define MAS_MS_MAX_SOURCES 16
+int mas_ms_ensemble(const float* const* feats_q, const float* const* logits_q, const int32_t* geometry /* [n,5] */, int n, int Ch, int C,
+                    int H, int W, float* feat_out, float* logit_out, void* stream);
 
 /* BatchNorm2d fused with the following ReLU and residual add (models/segmentation/backbone/resnet.py:143-160 Bottleneck,
  * the conv -> bn -> relu triples of the stem / ASPP / decoder, deeplabv3.py:93-110,216-245).  x, y, residual: [N,C,HW]

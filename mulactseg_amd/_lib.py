@@ -17,10 +17,11 @@ SCORE_FRAC, PROB_FRAC, LOSS_FRAC = 40, 23, 32
 LOSS_CE, LOSS_GROUP, LOSS_GROUP_ONLY_MULTI, LOSS_DECOMP, LOSS_TCE = 1, 2, 4, 8, 16
 ACC_WORDS = 8
 GRAD_FRAC = 44
+MS_MAX_SOURCES = 16
 
 SK_DMA, SK_NOSPLIT = 1, 2
 LOWRES_GENERIC = 1
-ABI_VERSION = 8        # MAS_ABI_VERSION of include/mulactseg_hip.h this table was written against (load() refuses any other library)
+ABI_VERSION = 9        # MAS_ABI_VERSION of include/mulactseg_hip.h this table was written against (load() refuses any other library)
 
 _c = ctypes
 _vp, _i, _f, _i64, _d = _c.c_void_p, _c.c_int, _c.c_float, _c.c_int64, _c.c_double
@@ -67,6 +68,7 @@ SIGNATURES = {
                                _vp, _i, _i64, _vp, _i, _vp, _i, _i64, _vp, _i, _vp, _vp]),
     "mas_upsample_bilinear_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "mas_upsample_bilinear_bwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp]),
+    "mas_ms_ensemble": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mas_bn_workspace_bytes": (_i64, [_i, _i, _i]),
     "mas_bn_mask_bytes": (_i64, [_i, _i, _i]),
     "mas_bn_act_train_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

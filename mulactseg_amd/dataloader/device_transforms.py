@@ -162,6 +162,32 @@ class DeviceTrainAugment:
         return out, outs
 
 
+class DeviceMultiScaleFlip(DeviceTrainAugment):
+    """``TestTimeAugmentation`` (``ext_transforms.py:18-46``, name ``eval_spx_identity_ms``): for flip in (False, True), then for each
+    factor, the picture resized (Pillow BILINEAR) to ``(int(factor * H), int(factor * W))``, flipped horizontally after the resize
+    when ``flip``, to-tensor + normalise -> a list of f32 ``[3,h_k,w_k]`` tensors, the unflipped ones first.  One launch of the
+    augmentation kernel per entry (no pad, no crop); factor 1.0 is the exact identity (every bilinear weight is 1).  The picture
+    only: labels and ids stay at the original size."""
+
+    def __init__(self, factors=(0.5, 0.75, 1.0, 1.25, 1.5), **kw):
+        super().__init__(size=(1, 1), scale_range=(1.0, 1.0), pad_values=(), **kw)
+        self.factors = tuple(factors)
+
+    def geometry(self, H, W):
+        """[(th, tw, flip)] in the reference's order."""
+        return [(int(f * H), int(f * W), flip) for flip in (False, True) for f in self.factors]
+
+    def __call__(self, img, maps=(), params=None):
+        if len(maps):
+            raise ValueError("the multi-scale transform takes the picture only")
+        out = []
+        for th, tw, flip in self.geometry(int(img.shape[0]), int(img.shape[1])):
+            self.size = (th, tw)
+            p = dict(scale=1.0, th=th, tw=tw, gap_y=0, gap_x=0, i=0, j=0, flip=flip)
+            out.append(DeviceTrainAugment.__call__(self, img, (), params=p)[0])
+        return out
+
+
 def get_device_transform(args):
     """The reference's ``'rescale_769_multi'`` training transform (``transform.py:67-89``) for resident data."""
     return DeviceTrainAugment(size=(768, 768), scale_range=(0.5, 2.0), pad_values=[args.ignore_idx, args.nseg])

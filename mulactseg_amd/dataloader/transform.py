@@ -6,8 +6,9 @@ called as ``transform(picture u8 [H,W,3] cuda, [maps]) -> (image f32 [3,h,w], [m
 it pads (``ExtRandomCrop.pad_values``; the reference asserts the same count, ``ext_transforms.py:489``).
 
 Not offered (outside the production configurations): the unpadded 512x1024 crops (``orig_*``, ``rescale``), ``load_smaller_spx``
-(a third map), the colour-jitter variant, the multi-scale identity evaluation (``eval_spx_identity_ms``)."""
-from .device_transforms import DeviceResize, DeviceResizeFlip, DeviceTrainAugment
+(a third map), the colour-jitter variant.  ``eval_spx_identity_ms`` (VOC) returns a LIST of ten pictures (five scales, then the same
+flipped) and takes no map (``n_maps == 0``)."""
+from .device_transforms import DeviceMultiScaleFlip, DeviceResize, DeviceResizeFlip, DeviceTrainAugment
 
 
 def _with_maps(t, n):
@@ -59,6 +60,8 @@ def get_train_transform_voc(args, transform):
         return _with_maps(DeviceTrainAugment(pad_values=[args.nseg], **crop), 1)
     if transform == 'eval_spx':
         return _with_maps(DeviceResize(513, center_crop=513, pad_values=[args.ignore_idx, args.nseg]), 2)
+    if transform == 'eval_spx_identity_ms':                         # TestTimeAugmentation: 5 scales x {no flip, flip}, picture only
+        return _with_maps(DeviceMultiScaleFlip(), 0)
     raise NotImplementedError("train_transform %r is outside the hot path (see dataloader/transform.py)" % transform)
 
 

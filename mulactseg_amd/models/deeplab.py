@@ -486,6 +486,11 @@ class DeepLabV3PlusWN(nn.Module):
         feat, prob = self.classifier(self.backbone(x), return_feat=True)
         return feat, _upsample(prob, size)
 
+    def feat_forward_quarter(self, x):
+        """(L2-normalised point features [N,256,h,w], logits [N,C,h,w]) at 1/4 resolution, neither upsampled: the multi-scale
+        ensemble (ops.ms_ensemble) evaluates feat_forward's upsampling, the flip and the resize to the original size in one kernel."""
+        return self.classifier(self.backbone(x), return_feat=True)
+
     def feat_forward(self, x):
         size = x.shape[-2:]
         feat, prob = self.classifier(self.backbone(x), return_feat=True)

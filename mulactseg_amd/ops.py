@@ -4,6 +4,7 @@ Every function launches on the current torch stream and never synchronises with 
 These are the only callers of ``_lib``; the plugin-level code (``active_selection``, ``utils.loss``)
 is written against this module.
 """
+import ctypes
 import os
 
 import numpy as np
@@ -873,6 +874,62 @@ def upsample_bilinear_into(x, out):
             _lib.check(lib.mas_upsample_bilinear_fwd(x[n].data_ptr(), C, Hi, Wi, Ho, Wo, out[n].data_ptr(), _stream(x)),
                        "mas_upsample_bilinear_fwd")
     return out
+
+
+def quarter_size(n):
+    """The side the network emits at quarter resolution for an input side n: the stride-2 stem convolution and the stride-2
+    max-pool (both padding 1, kernel 3) each give (n - 1) // 2 + 1."""
+    return ((int(n) - 1) // 2) // 2 + 1
+
+
+def ms_ensemble(feats_q, logits_q, scaled_sizes, flips, out_size):
+    """The multi-scale + flip ensemble of the VOC stage-2 generator (trainer/eval_save_cosplbl_prop_includeonehot_voc_ms.py:56-79) in
+    one launch (csrc/ms_ensemble.hip): n <= 16 sources, each the quarter-resolution ``(feat [1,Ch,hq,wq], logits [1,C,hq,wq])`` of the
+    network on a picture scaled to ``scaled_sizes[k] = (Hs, Ws)`` and flipped horizontally when ``flips[k]``.  -> (features
+    [1,Ch,H,W] unit-norm per pixel, logits [1,C,H,W]) at ``out_size = (H, W)``: upsampled x4 to the scaled size, flipped back, resized
+    to (H, W), averaged; the features re-normalised over the channels.  The scaled-size maps never exist in memory."""
+    n = len(feats_q)
+    if not 1 <= n <= _lib.MS_MAX_SOURCES:
+        raise ValueError("ms_ensemble takes 1 .. %d sources, got %d" % (_lib.MS_MAX_SOURCES, n))
+    if len(logits_q) != n or len(scaled_sizes) != n or len(flips) != n:
+        raise ValueError("feats_q, logits_q, scaled_sizes and flips must have one entry per source")
+    H, W = int(out_size[0]), int(out_size[1])
+    if H < 1 or W < 1:
+        raise ValueError("out_size must be non-empty, got %r" % (tuple(out_size),))
+    dev = feats_q[0].device
+    Ch, C = None, None
+    geom = []
+    for k in range(n):
+        f, z = feats_q[k], logits_q[k]
+        _need(f, "feats_q[%d]" % k, torch.float32)
+        _need(z, "logits_q[%d]" % k, torch.float32)
+        if f.device != dev or z.device != dev:
+            raise ValueError("all sources must live on one device")
+        if f.dim() != 4 or z.dim() != 4 or f.shape[0] != 1 or z.shape[0] != 1:
+            raise ValueError("source %d: features and logits must be [1,Ch,hq,wq] / [1,C,hq,wq]" % k)
+        if Ch is None:
+            Ch, C = int(f.shape[1]), int(z.shape[1])
+        if f.shape[1] != Ch or z.shape[1] != C:
+            raise ValueError("source %d: channel counts differ from source 0" % k)
+        hq, wq = int(f.shape[2]), int(f.shape[3])
+        if tuple(z.shape[2:]) != (hq, wq):
+            raise ValueError("source %d: features %s and logits %s differ in size" % (k, tuple(f.shape), tuple(z.shape)))
+        Hs, Ws = int(scaled_sizes[k][0]), int(scaled_sizes[k][1])
+        if Hs < 1 or Ws < 1:
+            raise ValueError("source %d: empty scaled size %dx%d" % (k, Hs, Ws))
+        if (hq, wq) != (quarter_size(Hs), quarter_size(Ws)):
+            raise ValueError("source %d: quarter-resolution maps %dx%d are not what the network emits for %dx%d (%dx%d)"
+                             % (k, hq, wq, Hs, Ws, quarter_size(Hs), quarter_size(Ws)))
+        geom += [hq, wq, Hs, Ws, 1 if flips[k] else 0]
+    feat = torch.empty((1, Ch, H, W), dtype=torch.float32, device=dev)
+    logit = torch.empty((1, C, H, W), dtype=torch.float32, device=dev)
+    fp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in feats_q])
+    lp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in logits_q])
+    g = (ctypes.c_int32 * (5 * n))(*geom)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mas_ms_ensemble(fp, lp, g, n, Ch, C, H, W, feat.data_ptr(), logit.data_ptr(), _stream(feat)),
+                   "mas_ms_ensemble")
+    return feat, logit
 
 
 # ------------------------------------------------------------------------------------------------

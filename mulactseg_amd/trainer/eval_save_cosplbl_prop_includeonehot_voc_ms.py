@@ -3,7 +3,11 @@
 second half of the list is horizontally flipped) goes through ``feat_forward``; features and scores are flipped back,
 resized to the original size (bilinear, ``align_corners=False``: torchvision's tensor ``resize`` without antialiasing),
 averaged, the features re-normalised over the channels, and handed to the K9 kernels at full resolution.
-PNGs go to ``plbl_gen_ms`` (:43)."""
+On the GPU the network stops at quarter resolution (``feat_forward_quarter``) and one kernel (``ops.ms_ensemble``,
+csrc/ms_ensemble.hip) does the upsampling, the flip, the resize, the mean and the normalisation; ``MAS_MS_ENSEMBLE=aten`` takes
+the ATen chain instead (A/B).  PNGs go to ``plbl_gen_<plbl_type>`` or ``plbl_gen_ms`` (:40-43)."""
+import os
+
 import torch
 import torch.nn.functional as F
 
@@ -12,17 +16,27 @@ from . import eval_save_cosplbl_prop_includeonehot_voc
 
 class ActiveTrainer(eval_save_cosplbl_prop_includeonehot_voc.ActiveTrainer):
     def _save_dir(self):
+        """``<dir of init_checkpoint>/plbl_gen_<plbl_type>/round_RR``, or ``plbl_gen_ms/round_RR`` without a type (:40-43)."""
         if self.save_dir is None:
-            base = super()._save_dir()
-            self.save_dir = base.replace('/plbl_gen', '/plbl_gen_ms', 1)
-            import os
+            ckpt = self.args.init_checkpoint
+            rnd = ckpt.split('/')[-1][-6:-4]
+            base = '/'.join(ckpt.split('/')[:-1])
+            ptype = getattr(self.args, 'plbl_type', None)
+            self.save_dir = '{}/plbl_gen_{}/round_{}'.format(base, 'ms' if ptype is None else ptype, rnd)
             os.makedirs(self.save_dir, exist_ok=True)
         return self.save_dir
 
     def ensemble(self, image_list, im_size):
         """-> (features [1,Ch,H,W] unit-norm, scores [1,C,H,W]) averaged over the scales / flips."""
-        feats = outs = None
         n = len(image_list)
+        if torch.device(self.device).type == 'cuda' and os.environ.get("MAS_MS_ENSEMBLE", "fused") != "aten":
+            from .. import ops
+            feats, outs, sizes = [], [], []
+            for img in image_list:
+                feat, out = self.net.feat_forward_quarter(img.to(self.device, dtype=torch.float32)[None])
+                feats.append(feat.contiguous()), outs.append(out.contiguous()), sizes.append(tuple(img.shape[-2:]))
+            return ops.ms_ensemble(feats, outs, sizes, [(n - 1) // 2 < idx for idx in range(n)], im_size)
+        feats = outs = None
         for idx, img in enumerate(image_list):
             feat, out = self.net.feat_forward(img.to(self.device, dtype=torch.float32)[None])
             if (n - 1) // 2 < idx:                                    # (:64-66) the flipped half
