@@ -53,7 +53,9 @@ extern "C" {
  * mas_single_pass_lowres_generic switch; mas_test_occupy moved to the test-support library; the BatchNorm-fused forms of
  * mas_conv_bx_fwd); 6 = role 2 of mas_conv_bx_pack / _packed_bytes / _pack_job and ksize 3 at stride 2 in mas_conv_bx_supported /
  * mas_conv_bx_fwd (a library of version 5 answers "unsupported" to both); 8 = the region-label entry points of the data-generation
- * step (mas_region_label_counts, mas_region_multi_hot, mas_region_dominant, mas_region_paint); 9 = mas_ms_ensemble. */
+ * step (mas_region_label_counts, mas_region_multi_hot, mas_region_dominant, mas_region_paint); 9 = mas_ms_ensemble.  mas_naive_plbl and
+ * mas_spx_max_onehot came later under 9: new entry points change no existing signature or argument; a library built before them
+ * lacks their symbols, and load() refuses it with a rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
 int mas_abi_version(void);
 const char* mas_error_string(int code);
@@ -283,6 +285,17 @@ int mas_region_dominant(const int32_t* full, const uint8_t* listed, const int32_
 int mas_region_paint(const void* spx, int spx_dtype, const uint8_t* labels, int H, int W, int nseg, const int32_t* choice,
                      int generate_ignore, uint8_t* out /* [H,W] */, void* stream);
 
+/* Stage 2 with dominant labels (trainer/eval_save_cosplbl_prop_onehotignore.py:29-58), one picture: mask[i] = target[i] != 255 and,
+ * per superpixel id p in [0,nseg), m = the largest target value of its pixels (torch_scatter.scatter_max), 255 read as num_classes-1,
+ * rows[p*num_classes + c] = (c == m): the one-hot target rows.  An id with no pixel gets the row of m = 0 (scatter_max's fill for
+ * an empty segment; the reference sizes the table max(id)+1, this one nseg).  target: uint8 (MAS_MAP_U8) or int64 (MAS_ID_I64)
+ * [H,W], values in [0,num_classes) or 255 -- anything else sets MAS_LABELS_BAD_VALUE in *status and is not counted; ids outside
+ * [0,nseg) belong to no row.  seg_max int32 [nseg] (workspace: the maxima, -1 for no pixel) and the status word are set here.
+ * nseg <= 16384 (MAS_ERR_RANGE otherwise). */
+int mas_spx_max_onehot(const void* target, int target_dtype, const void* spx, int spx_dtype, int H, int W, int nseg, int num_classes,
+                       int32_t* seg_max /* [nseg] */, int32_t* status /* [1] */, uint8_t* mask /* [H,W] */,
+                       uint8_t* rows /* [nseg, num_classes] */, void* stream);
+
 /* =============================================================================================
  * mIoU counters
  * ============================================================================================= */
@@ -433,6 +446,16 @@ int mas_upsample_bilinear_bwd(const float* gy, int64_t NC, int Hi, int Wi, int H
 #define MAS_MS_MAX_SOURCES 16
 int mas_ms_ensemble(const float* const* feats_q, const float* const* logits_q, const int32_t* geometry /* [n,5] */, int n, int Ch, int C,
                     int H, int W, float* feat_out, float* logit_out, void* stream);
+
+/* Naive top-1 pseudo labels (trainer/eval_save_naiveplbl.py:46-61) without materialising the full-resolution logits.  logits_q f32
+ * [N,C,h,w] (the network's quarter-resolution logits); labels u8 [N,H,W].  Per pixel the C values of mas_upsample_bilinear_fwd's
+ * output to H x W (bit for bit: same taps, same expression; the identity geometry h == H, w == W reads the logits themselves), label
+ * = first arg-max in channel order (a NaN wins where it first appears, as torch.max).  th <= 0: labels[i] = mask[i] ? label : 255,
+ * mask u8 [N,H,W] required.  th > 0: the mask is ignored (may be NULL) and a label is kept iff 1 / sum_c expf(y_c - y_max) > th
+ * (channel order) -- not bit-equal to torch.softmax.  Geometry: the identity, or h <= H, w <= W, W <= 6 w, H <= 65535 (what
+ * mas_upsample_bilinear_fwd accepts); MAS_ERR_SHAPE otherwise.  C <= 255. */
+int mas_naive_plbl(const float* logits_q, int N, int C, int h, int w, int H, int W, const uint8_t* mask /* [N,H,W] or NULL */, float th,
+                   uint8_t* labels /* [N,H,W] */, void* stream);
 
 /* BatchNorm2d fused with the following ReLU and residual add (models/segmentation/backbone/resnet.py:143-160 Bottleneck,
  * the conv -> bn -> relu triples of the stem / ASPP / decoder, deeplabv3.py:93-110,216-245).  x, y, residual: [N,C,HW]

@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MAS_LIB") or os.path.join(_HERE, "libmulactseg_hip.so")
 
 ID_I64, ID_I32, ID_U16 = 0, 1, 2
+MAP_U8 = 3
 MAX_CLASSES = 32
 LABELS_BAD_VALUE = 1
 SCORE_FRAC, PROB_FRAC, LOSS_FRAC = 40, 23, 32
@@ -50,6 +51,7 @@ SIGNATURES = {
     "mas_region_multi_hot": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "mas_region_dominant": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "mas_region_paint": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "mas_spx_max_onehot": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mas_iou_counts": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _vp]),
     "mas_logits_iou_counts": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i64, _vp, _vp]),
     "mas_single_pass_accum": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
@@ -69,6 +71,7 @@ SIGNATURES = {
     "mas_upsample_bilinear_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "mas_upsample_bilinear_bwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "mas_ms_ensemble": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mas_naive_plbl": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp]),
     "mas_bn_workspace_bytes": (_i64, [_i, _i, _i]),
     "mas_bn_mask_bytes": (_i64, [_i, _i, _i]),
     "mas_bn_act_train_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -182,8 +185,12 @@ def load():
     if got != ABI_VERSION:
         raise MulActSegHipError("%s reports ABI version %s, this package binds version %d (include/mulactseg_hip.h MAS_ABI_VERSION): "
                                 "rebuild it with `make -C mulactseg_amd/csrc`" % (LIB_PATH, got, ABI_VERSION))
+    missing = [name for name in SIGNATURES if not hasattr(lib, name)]
+    if missing:         # a library of this version built before entry points were added to it
+        raise MulActSegHipError("%s does not export %s (declared in include/mulactseg_hip.h): a stale build; rebuild it with "
+                                "`make -C mulactseg_amd/csrc`" % (LIB_PATH, ', '.join(missing)))
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)      # AttributeError if the .so does not export a declared symbol
+        fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
     _lib = lib

@@ -15,6 +15,12 @@
 //   k_region_finalize  one lane per id: the multi-hot row (trimmed counts, or the full ones when the trimmed region is empty) and
 //                      its size, or the dominant label (arg-max with ties to the smaller value, or a choice drawn on the host).
 //   k_region_paint     one lane per pixel: the dominant-label map.
+//   k_spx_max_onehot   stage 2 with dominant labels (trainer/eval_save_cosplbl_prop_onehotignore.py:29-58): per superpixel the largest
+//                      target value (torch_scatter.scatter_max), and the mask target != 255.  A workgroup owns a contiguous run of
+//                      pixels, a lane 8 consecutive ones; each run of equal ids within a lane goes into an LDS table of all nseg
+//                      ids with one LDS atomicMax, and the table reaches the global maxima with one atomicMax per touched id.
+//   k_spx_onehot_rows  the finalize step: one lane per (id, class) writes the one-hot row of the id's maximum (255 -> C - 1; an id
+//                      with no pixel gets the row of value 0, torch_scatter's fill for an empty segment).
 #include "common.h"
 
 namespace {
@@ -244,7 +250,108 @@ void launch_counts(const void* spx, const uint8_t* labels, int H, int W, int nse
     else
         hipLaunchKernelGGL((k_region_counts<IdT, false>), grid, dim3(kThreads), 0, st, s, labels, H, W, nseg, C, 0, f, nullptr, status);
 }
+// ------------------------------------------------------------------------------------------------------------------------------
+// dominant-label target rows of one picture (k_spx_max_onehot + k_spx_onehot_rows)
+constexpr int kMaxPix = 8;                     // consecutive pixels per lane
+constexpr int kMaxChunk = kThreads * kMaxPix;  // pixels per workgroup
+constexpr int kMaxSeg = 16384;                 // LDS table: 64 KB
+
+template <typename TgtT>
+__device__ __forceinline__ int load_target(const TgtT* p, size_t i) {
+    return (int)p[i];
+}
+template <>
+__device__ __forceinline__ int load_target<long long>(const long long* p, size_t i) {
+    const long long v = p[i];                   // anything outside [0, 255] is a bad value; -1 keeps it recognisable as one
+    return v < 0 || v > 255 ? -1 : (int)v;
+}
+
+template <typename IdT, typename TgtT>
+__global__ __launch_bounds__(kThreads) void k_spx_max_onehot(const TgtT* __restrict__ target, const IdT* __restrict__ spx, long long n,
+                                                              int nseg, int C, int* __restrict__ seg_max, unsigned char* __restrict__ mask,
+                                                              int* __restrict__ status) {
+    extern __shared__ int t_max[];              // [nseg], -1 = no pixel of this id in the workgroup's run
+    const int tid = threadIdx.x;
+    for (int i = tid; i < nseg; i += kThreads) t_max[i] = -1;
+    __syncthreads();
+    const long long p0 = (long long)blockIdx.x * kMaxChunk + (long long)tid * kMaxPix;
+    int cur_id = -1, cur = -1, bad = 0;
+    for (int j = 0; j < kMaxPix; ++j) {
+        const long long p = p0 + j;
+        if (p >= n) break;
+        const int t = load_target(target, (size_t)p);
+        const int id = load_id32(spx, (size_t)p);
+        mask[p] = t != 255;
+        if ((t < 0 || t >= C) && t != 255) { bad = 1; continue; }
+        if (id < 0 || id >= nseg) continue;
+        if (id != cur_id) {
+            if (cur_id >= 0) atomicMax(&t_max[cur_id], cur);
+            cur_id = id;
+            cur = t;
+        } else {
+            cur = t > cur ? t : cur;
+        }
+    }
+    if (cur_id >= 0) atomicMax(&t_max[cur_id], cur);
+    if (bad) atomicOr(status, MAS_LABELS_BAD_VALUE);
+    __syncthreads();
+    for (int i = tid; i < nseg; i += kThreads)
+        if (t_max[i] >= 0) atomicMax(&seg_max[i], t_max[i]);
+}
+
+__global__ __launch_bounds__(kThreads) void k_spx_onehot_rows(const int* __restrict__ seg_max, int nseg, int C,
+                                                               unsigned char* __restrict__ rows) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= (long long)nseg * C) return;
+    const int id = (int)(i / C), c = (int)(i - (long long)id * C);
+    const int m = seg_max[id];
+    const int v = m < 0 ? 0 : (m == 255 ? C - 1 : m);
+    rows[i] = c == v;
+}
+
+template <typename IdT, typename TgtT>
+void launch_spx_max(const void* target, const void* spx, long long n, int nseg, int C, int32_t* seg_max, uint8_t* mask, int32_t* status,
+                    hipStream_t st) {
+    hipLaunchKernelGGL((k_spx_max_onehot<IdT, TgtT>), dim3((unsigned)((n + kMaxChunk - 1) / kMaxChunk)), dim3(kThreads),
+                       sizeof(int) * (size_t)nseg, st, static_cast<const TgtT*>(target), static_cast<const IdT*>(spx), n, nseg, C, seg_max,
+                       mask, status);
+}
+
+template <typename IdT>
+void launch_spx_max_ids(const void* target, int target_dtype, const void* spx, long long n, int nseg, int C, int32_t* seg_max,
+                        uint8_t* mask, int32_t* status, hipStream_t st) {
+    if (target_dtype == MAS_MAP_U8)
+        launch_spx_max<IdT, unsigned char>(target, spx, n, nseg, C, seg_max, mask, status, st);
+    else
+        launch_spx_max<IdT, long long>(target, spx, n, nseg, C, seg_max, mask, status, st);
+}
 }  // namespace
+
+extern "C" int mas_spx_max_onehot(const void* target, int target_dtype, const void* spx, int spx_dtype, int H, int W, int nseg,
+                                  int num_classes, int32_t* seg_max, int32_t* status, uint8_t* mask, uint8_t* rows, void* stream) {
+    if (!target || !spx || !seg_max || !status || !mask || !rows) return MAS_ERR_NULL;
+    if (target_dtype != MAS_MAP_U8 && target_dtype != MAS_ID_I64) return MAS_ERR_DTYPE;
+    if (spx_dtype != MAS_ID_I64 && spx_dtype != MAS_ID_I32 && spx_dtype != MAS_ID_U16) return MAS_ERR_DTYPE;
+    if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) return MAS_ERR_SHAPE;
+    if (nseg <= 0 || nseg > kMaxSeg) return MAS_ERR_RANGE;
+    if (num_classes < 1 || num_classes > 255) return MAS_ERR_CLASSES;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(seg_max, 0xff, sizeof(int32_t) * (size_t)nseg, st);      // -1: no pixel
+    if (e == hipSuccess) e = hipMemsetAsync(status, 0, sizeof(int32_t), st);
+    if (e != hipSuccess) return (int)e;
+    const long long n = (long long)H * W;
+    if (spx_dtype == MAS_ID_I64)
+        launch_spx_max_ids<long long>(target, target_dtype, spx, n, nseg, num_classes, seg_max, mask, status, st);
+    else if (spx_dtype == MAS_ID_I32)
+        launch_spx_max_ids<int>(target, target_dtype, spx, n, nseg, num_classes, seg_max, mask, status, st);
+    else
+        launch_spx_max_ids<unsigned short>(target, target_dtype, spx, n, nseg, num_classes, seg_max, mask, status, st);
+    if (int r = mas_launch_status()) return r;
+    const long long cells = (long long)nseg * num_classes;
+    hipLaunchKernelGGL(k_spx_onehot_rows, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, seg_max, nseg,
+                       num_classes, rows);
+    return mas_launch_status();
+}
 
 extern "C" int mas_region_label_counts(const void* spx, int spx_dtype, const uint8_t* labels, int H, int W, int nseg, int num_classes,
                                        int trim_k, int32_t* full, int32_t* trimmed, int32_t* status, void* stream) {

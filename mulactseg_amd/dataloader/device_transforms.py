@@ -226,6 +226,30 @@ class DeviceResize(DeviceTrainAugment):
         return super().__call__(img, maps, params=p)
 
 
+class DeviceResizeThreeMaps(DeviceResize):
+    """``ExtResize((h, w))`` + to-tensor + normalise with THREE maps (name ``eval_dom_gt_spx``, ``transform.py:161-167``: dominant
+    target, precise label, superpixel ids), all resampled NEAREST with the same tables.  The augmentation entry takes at most two maps,
+    so the third goes through a second launch with the same geometry; that launch also resamples the picture again into a scratch
+    tensor (one more picture read and a 3 x h x w f32 write, 25 MB at 1024 x 2048) -- the price of leaving the kernel's entry as it
+    is."""
+
+    def __init__(self, size, pad_values=(255, 255, 2048), **kw):
+        pads = list(pad_values)
+        if len(pads) != 3:
+            raise ValueError("three maps, three pad values")
+        super().__init__(size, pad_values=pads[:2], **kw)
+        self._third = DeviceResize(size, pad_values=pads[2:], **kw)
+
+    def __call__(self, img, maps=(), params=None):
+        maps = list(maps)
+        if len(maps) != 3:
+            raise ValueError("the three-map resize takes exactly three maps, got %d" % len(maps))
+        self._third.target = self.target
+        image, out = super().__call__(img, maps[:2])
+        _, third = self._third(img, maps[2:])
+        return image, out + third
+
+
 class DeviceResizeFlip(DeviceResize):
     """``ExtResize(s)`` + ``ExtCenterCrop(s)`` + ``ExtRandomHorizontalFlip`` -- the VOC stage-2 training transform
     (``transform_voc.py:52-61``, name ``rescale_769_nospx``): one ``random()`` draw per sample."""

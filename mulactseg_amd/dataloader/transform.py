@@ -1,14 +1,14 @@
 """Training transforms by name -- the reference's ``dataloader/transform.py:5-170`` (Cityscapes) and
 ``dataloader/transform_voc.py:5-224`` (VOC) -- built on the device augmentation (``device_transforms.py``,
 ``csrc/augment.hip``): the names the launch scripts use (``script/**/*.sh``: ``rescale_769_multi_notrg``, ``rescale_769_nospx``,
-``rescale_513_multi_notrg``, ``rescale_513_notrg``, ``eval_spx``) plus the other names with the same structure.  A transform is
+``rescale_513_multi_notrg``, ``rescale_513_notrg``, ``eval_spx``, ``eval_dom_gt_spx``) plus the other names with the same structure.  A transform is
 called as ``transform(picture u8 [H,W,3] cuda, [maps]) -> (image f32 [3,h,w], [maps])``; ``transform.n_maps`` says how many maps
 it pads (``ExtRandomCrop.pad_values``; the reference asserts the same count, ``ext_transforms.py:489``).
 
 Not offered (outside the production configurations): the unpadded 512x1024 crops (``orig_*``, ``rescale``), ``load_smaller_spx``
 (a third map), the colour-jitter variant.  ``eval_spx_identity_ms`` (VOC) returns a LIST of ten pictures (five scales, then the same
 flipped) and takes no map (``n_maps == 0``)."""
-from .device_transforms import DeviceMultiScaleFlip, DeviceResize, DeviceResizeFlip, DeviceTrainAugment
+from .device_transforms import DeviceMultiScaleFlip, DeviceResize, DeviceResizeFlip, DeviceResizeThreeMaps, DeviceTrainAugment
 
 
 def _with_maps(t, n):
@@ -39,8 +39,10 @@ def get_train_transform(args, transform):
     if transform == 'rescale_769_multi_notrg_ignore':               # [label padded with 0, superpixel]
         _no_small(args, transform)
         return _with_maps(DeviceTrainAugment(pad_values=[0, args.nseg], **crop), 2)
-    if transform in ('eval_spx', 'eval_dom_gt_spx'):                # ExtResize((1024, 2048)), two maps
+    if transform == 'eval_spx':                                     # ExtResize((1024, 2048)), two maps
         return _with_maps(DeviceResize((1024, 2048), pad_values=[args.ignore_idx, args.nseg]), 2)
+    if transform == 'eval_dom_gt_spx':                              # ExtResize((1024, 2048)), three maps: dominant target, label, ids
+        return _with_maps(DeviceResizeThreeMaps((1024, 2048), pad_values=[args.ignore_idx, args.ignore_idx, args.nseg]), 3)
     raise NotImplementedError("train_transform %r is outside the hot path (see dataloader/transform.py)" % transform)
 
 

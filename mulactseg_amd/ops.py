@@ -660,6 +660,36 @@ def region_dominant(labels, superpixel, ids, nseg, num_classes, generate_ignore=
     return out
 
 
+def spx_max_onehot(target, superpixel, nseg, num_classes=20):
+    """(rows uint8 ``[nseg, num_classes]``, mask bool ``[H,W]``) of one picture -- the dominant-label stage-2 targets of
+    ``trainer/eval_save_cosplbl_prop_onehotignore.py:29-33``: ``mask = target != 255``; per superpixel id the largest target value of
+    its pixels (``torch_scatter.scatter_max``), 255 read as ``num_classes - 1``, one-hot.  An id with no pixel gets the row of 0 (the
+    reference's table has ``max(id) + 1`` rows, this one ``nseg``: such rows carry no masked pixel and change no label).  target:
+    uint8 or int64 [H,W]; superpixel: int64 / int32 / uint16 (int16) [H,W].  One pass (``csrc/labels.hip``); reads back one status
+    word (a target value outside [0, num_classes) and 255 is a ValueError)."""
+    _need(target, "target")
+    _need(superpixel, "superpixel")
+    if target.dtype not in (torch.uint8, torch.int64):
+        raise TypeError("target must be uint8 or int64, got %s" % target.dtype)
+    code = _id_code(superpixel)
+    if target.dim() != 2 or tuple(superpixel.shape) != tuple(target.shape):
+        raise ValueError("target and superpixel must be [H,W] of one shape, got %s and %s"
+                         % (tuple(target.shape), tuple(superpixel.shape)))
+    H, W = target.shape
+    dev = target.device
+    seg_max = torch.empty(nseg, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    rows = torch.empty((nseg, num_classes), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mas_spx_max_onehot(target.data_ptr(), _lib.MAP_U8 if target.dtype == torch.uint8 else _lib.ID_I64,
+                                                  superpixel.data_ptr(), code, H, W, nseg, num_classes, seg_max.data_ptr(),
+                                                  status.data_ptr(), mask.data_ptr(), rows.data_ptr(), _stream(target)),
+                   "mas_spx_max_onehot")
+    _raise_on_label_status(status, num_classes)
+    return rows, mask.view(torch.bool)
+
+
 # ------------------------------------------------------------------------------------------------
 # K9: stage-2 cosine pseudo labels
 # ------------------------------------------------------------------------------------------------
@@ -930,6 +960,57 @@ def ms_ensemble(feats_q, logits_q, scaled_sizes, flips, out_size):
         _lib.check(_lib.load().mas_ms_ensemble(fp, lp, g, n, Ch, C, H, W, feat.data_ptr(), logit.data_ptr(), _stream(feat)),
                    "mas_ms_ensemble")
     return feat, logit
+
+
+def naive_plbl_supported(logits_q, size):
+    """The geometries ``mas_naive_plbl`` takes: the identity, or what ``upsample_bilinear_supported`` takes."""
+    H, W = int(size[0]), int(size[1])
+    if logits_q.dim() != 4:
+        return False
+    if (H, W) == tuple(logits_q.shape[2:]):
+        return True
+    h, w = int(logits_q.shape[2]), int(logits_q.shape[3])
+    return h <= H and w <= W and W <= 6 * w and H <= 65535
+
+
+def _naive_plbl_aten(logits_q, size, spmask, th):
+    """The reference's lines (``eval_save_naiveplbl.py:52-56``) on the upsampled logits: ``F.interpolate``, ``softmax`` / ``max``,
+    ``masked_fill``."""
+    import torch.nn.functional as F
+    H, W = int(size[0]), int(size[1])
+    z = logits_q if tuple(logits_q.shape[2:]) == (H, W) else F.interpolate(logits_q, size=(H, W), mode='bilinear', align_corners=False)
+    if th > 0:
+        spmask = torch.softmax(z, dim=1).max(dim=1)[0] > th
+    label = z.max(dim=1)[1]
+    return torch.masked_fill(label, torch.logical_not(spmask), 255)
+
+
+def naive_pseudo_labels(logits_q, size, spmask, th=0.0):
+    """Naive top-1 pseudo labels int64 ``[N,H,W]`` (255 = none) -- ``trainer/eval_save_naiveplbl.py:46-61``.  logits_q f32
+    ``[N,C,h,w]``: the network's quarter-resolution logits (``net(x, lowres=True)``), or full-resolution ones (h, w = H, W).  Label =
+    the first arg-max over the C channels of the bilinear upsampling to ``size`` (bit for bit that of ``upsample_bilinear``);
+    ``th <= 0``: kept where ``spmask`` (bool [N,H,W]); ``th > 0``: kept where ``1 / sum_c exp(y_c - y_max) > th`` over every pixel
+    (``spmask`` unused; not bit-equal to ``torch.softmax``).  One launch (``csrc/naive_plbl.hip``): the full-resolution logits never
+    exist.  CPU tensors, and ``MAS_NAIVE_PLBL=aten``, take the reference's ATen chain."""
+    H, W = int(size[0]), int(size[1])
+    th = float(th)
+    if not logits_q.is_cuda or os.environ.get("MAS_NAIVE_PLBL", "fused") == "aten":
+        return _naive_plbl_aten(logits_q, (H, W), spmask, th)
+    _need(logits_q, "logits_q", torch.float32)
+    if not naive_plbl_supported(logits_q, (H, W)):
+        raise ValueError("naive_pseudo_labels: logits %s cannot be upsampled to %dx%d (an upsampling with W <= 6 w, or the identity)"
+                         % (tuple(logits_q.shape), H, W))
+    N, C, h, w = logits_q.shape
+    mask = None
+    if th <= 0:
+        if spmask is None or tuple(spmask.shape) != (N, H, W):
+            raise ValueError("spmask must be [N,H,W] = [%d,%d,%d] when th <= 0" % (N, H, W))
+        mask = _mask_u8(spmask.contiguous())
+    out = torch.empty((N, H, W), dtype=torch.uint8, device=logits_q.device)
+    with torch.cuda.device(logits_q.device):
+        _lib.check(_lib.load().mas_naive_plbl(logits_q.data_ptr(), N, C, h, w, H, W, mask.data_ptr() if mask is not None else None, th,
+                                              out.data_ptr(), _stream(logits_q)), "mas_naive_plbl")
+    return out.long()
 
 
 # ------------------------------------------------------------------------------------------------

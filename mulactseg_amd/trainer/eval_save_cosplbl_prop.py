@@ -8,7 +8,6 @@ import os
 import queue
 import threading
 
-import numpy as np
 import torch
 
 from .. import ops
@@ -18,6 +17,7 @@ from . import eval_within_multihot
 
 class ActiveTrainer(eval_within_multihot.ActiveTrainer):
     include_onehot = False
+    threaded_generation = None      # True / False: the loop below or the one-thread loop; None: threaded unless pseudo_labels is replaced
 
     def __init__(self, args, logger, selection_iter):
         super().__init__(args, logger, selection_iter)
@@ -51,10 +51,14 @@ class ActiveTrainer(eval_within_multihot.ActiveTrainer):
         1024 x 2048 picture for 13 ms of kernels; 10.9 ms with four threads (``tools/stage2_loop_probe.py``).  The loader is read by the calling thread, in order; a PNG is a per-picture file and
         the IoU counters are integer sums, so neither depends on which thread took which picture.  The first picture runs on the
         caller's stream (everything the model derives lazily from its weights is built there).  Subclasses that replace
-        ``pseudo_labels`` (the sliding-window form keeps state between calls) run the one-thread loop."""
+        ``pseudo_labels`` run the one-thread loop (the sliding-window form keeps state between calls) unless they declare
+        ``threaded_generation = True``."""
         workers = int(os.environ.get("MAS_STAGE2_WORKERS", "4"))
         dev = torch.device(self.device)
-        if workers <= 1 or dev.type != 'cuda' or type(self).pseudo_labels is not ActiveTrainer.pseudo_labels or len(loader) < 2:
+        threaded = self.threaded_generation
+        if threaded is None:
+            threaded = type(self).pseudo_labels is ActiveTrainer.pseudo_labels
+        if workers <= 1 or dev.type != 'cuda' or not threaded or len(loader) < 2:
             return super().inference(loader, prefix)
         meter = MeanIoU(self.num_classes + 1, self.args.ignore_idx)
         meter._before_epoch()
@@ -109,11 +113,7 @@ class ActiveTrainer(eval_within_multihot.ActiveTrainer):
         if errors:
             raise errors[0]
         meter.all_reduce(self.device)
-        ious = meter._after_epoch()
-        miou = np.mean(ious)
-        table = ','.join(['%.2f' % miou] + ['%.2f' % v for v in ious])
-        print("\n[AL {}-round]: {}\n{}".format(self.selection_iter, prefix, table), flush=True)
-        return miou, table
+        return self.report(meter, prefix)
 
     def after_batch(self, batch, plbl):
         from PIL import Image

@@ -64,6 +64,10 @@ class ActiveTrainer(BaseTrainer):
                 meter._after_step({'outputs': plbl, 'targets': labels})
                 self.after_batch(batch, plbl)
         meter.all_reduce(self.device)
+        return self.report(meter, prefix)
+
+    def report(self, meter, prefix):
+        """Print the IoU table of the generated labels (mIoU, then per class) and return (mIoU, table)."""
         ious = meter._after_epoch()
         miou = np.mean(ious)
         table = ','.join(['%.2f' % miou] + ['%.2f' % v for v in ious])

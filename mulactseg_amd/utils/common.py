@@ -132,6 +132,7 @@ def get_parser():
     a('--spx_method', type=str, default="seeds", choices=["seeds", "slic"])
     a('--nseg_list', nargs='+', default=None, type=int)
     a('--plbl_type', type=str, default=None)
+    a('--plbl_th', type=float, default=0.0)             # eval_save_naiveplbl: keep labels whose softmax maximum exceeds this (0: the mask)
     a('--loading', default='binary', choices=['binary', 'naive', 'tensor'])
     a('--ignore_size', type=int, default=0)
     a('--mark_topk', type=int, default=-1)
