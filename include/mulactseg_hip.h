@@ -54,8 +54,8 @@ extern "C" {
  * mas_conv_bx_fwd); 6 = role 2 of mas_conv_bx_pack / _packed_bytes / _pack_job and ksize 3 at stride 2 in mas_conv_bx_supported /
  * mas_conv_bx_fwd (a library of version 5 answers "unsupported" to both); 8 = the region-label entry points of the data-generation
  * step (mas_region_label_counts, mas_region_multi_hot, mas_region_dominant, mas_region_paint); 9 = mas_ms_ensemble.  mas_naive_plbl and
- * mas_spx_max_onehot came later under 9: new entry points change no existing signature or argument; a library built before them
- * lacks their symbols, and load() refuses it with a rebuild message rather than binding a partial table. */
+ * mas_spx_max_onehot came later under 9, then mas_lowres_iou_counts: new entry points change no existing signature or argument; a
+ * library built before them lacks their symbols, and load() refuses it with a rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
 int mas_abi_version(void);
 const char* mas_error_string(int code);
@@ -313,6 +313,14 @@ int mas_iou_counts(const int64_t* outputs, const int64_t* outputs_all, const int
  * logits [B,channels,H,W] f32 (channels = num_classes or num_classes+1) yields argmax over the first
  * num_classes channels, argmax over all channels and every counter above; first maximum wins. */
 int mas_logits_iou_counts(const float* z, const int64_t* targets, int B, int channels, int H, int W, int num_classes,
+                          int64_t ignore_label, uint64_t* counts /* [3C+3] */, void* stream);
+
+/* The same counters from the quarter-resolution logits (trainer/eval_naive.py:39-80 with net(images, lowres=True)): z_q f32
+ * [B,channels,h,w], targets int64 [B,H,W].  Each pixel's values are those of mas_upsample_bilinear_fwd to H x W (same taps, same
+ * expression; the identity geometry h == H, w == W reads the logits themselves), the two arg-maxes and the tally those of
+ * mas_logits_iou_counts, so the counters equal mas_logits_iou_counts on the materialised upsampling element for element.
+ * Geometry: the identity, or h <= H, w <= W, W <= 6 w, H <= 65535 (what mas_naive_plbl accepts); MAS_ERR_SHAPE otherwise. */
+int mas_lowres_iou_counts(const float* z_q, const int64_t* targets, int B, int channels, int h, int w, int H, int W, int num_classes,
                           int64_t ignore_label, uint64_t* counts /* [3C+3] */, void* stream);
 
 /* =============================================================================================

@@ -10,6 +10,7 @@
 //                    and issues 19 x 3 host-synchronising reductions).
 // Exact integer work: per-workgroup LDS histograms, one 64-bit global atomic per non-zero counter.
 #include "common.h"
+#include "iou_tally.h"
 
 namespace {
 constexpr int kThreads = 256;
@@ -19,24 +20,6 @@ __device__ __forceinline__ void flush(unsigned* s_cnt, int n, mas_u64* out) {
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += kThreads)
         if (s_cnt[i]) atomicAdd(&out[i], (mas_u64)s_cnt[i]);
-}
-
-// counts layout: seen[C], correct[C], positive[C], then (ignore_seen, ignore_correct, ignore_positive)
-__device__ __forceinline__ void tally(unsigned* s_cnt, int C, long long t, long long o_cls, long long o_all, long long ignore_label,
-                                      bool with_ignore_iou) {
-    if (t != ignore_label) {
-        if (t >= 0 && t < C) {
-            atomicAdd(&s_cnt[t], 1u);
-            if (o_cls == t) atomicAdd(&s_cnt[C + t], 1u);
-        }
-        if (o_cls >= 0 && o_cls < C) atomicAdd(&s_cnt[2 * C + o_cls], 1u);
-    }
-    if (with_ignore_iou) {
-        const bool tig = (t == ignore_label), oig = (o_all == C);
-        if (tig) atomicAdd(&s_cnt[3 * C], 1u);
-        if (tig && oig) atomicAdd(&s_cnt[3 * C + 1], 1u);
-        if (oig) atomicAdd(&s_cnt[3 * C + 2], 1u);
-    }
 }
 
 __global__ __launch_bounds__(kThreads) void k_iou_counts(const long long* __restrict__ outputs, const long long* __restrict__ outputs_all,

@@ -18,25 +18,13 @@
 // The tile's quarter-resolution footprint (nrq x ncq, exact maxima over tiles computed on the host with the same tap arithmetic) is
 // staged in LDS for `cb` channels at a time, channel blocks in order; the threshold pass walks the blocks a second time.
 #include "common.h"
+#include "upsample_tap.h"
 
 namespace {
 constexpr int kTH = 16, kTW = 64;          // output tile
 constexpr int kThreads = 256;              // 16 lanes x 4 pixels per row, 16 rows
 constexpr int kPix = 4;
 constexpr size_t kLdsBudget = 32 * 1024;
-
-struct Tap { int i0, i1; float l0, l1; };
-
-__host__ __device__ __forceinline__ Tap make_tap(float scale, int o, int n_in) {
-    float s = scale * ((float)o + 0.5f) - 0.5f;
-    s = s < 0.0f ? 0.0f : s;
-    Tap t;
-    t.i0 = (int)s;
-    t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
-    t.l1 = s - (float)t.i0;
-    t.l0 = 1.0f - t.l1;
-    return t;
-}
 
 struct PlblArgs {
     const float* z;               // [N,C,h,w]
@@ -199,17 +187,8 @@ extern "C" int mas_naive_plbl(const float* logits_q, int N, int C, int h, int w,
         return mas_launch_status();
     }
     // LDS extents: the exact maxima over tiles (same tap arithmetic as the kernel)
-    int nrq = 1, ncq = 1;
-    for (int y0 = 0; y0 < H; y0 += kTH) {
-        const int y1 = (y0 + kTH < H ? y0 + kTH : H) - 1;
-        const int v = make_tap(a.sh, y1, h).i1 - make_tap(a.sh, y0, h).i0 + 1;
-        nrq = v > nrq ? v : nrq;
-    }
-    for (int x0 = 0; x0 < W; x0 += kTW) {
-        const int x1 = (x0 + kTW < W ? x0 + kTW : W) - 1;
-        const int v = make_tap(a.sw, x1, w).i1 - make_tap(a.sw, x0, w).i0 + 1;
-        ncq = v > ncq ? v : ncq;
-    }
+    int nrq, ncq;
+    tile_footprint(a.sh, a.sw, h, w, H, W, kTH, kTW, &nrq, &ncq);
     int cb = (int)(kLdsBudget / (sizeof(float) * (size_t)nrq * ncq));     // >= 7: nrq <= kTH + 1, ncq <= kTW + 1
     cb = cb > C ? C : cb;
     a.nrq = nrq, a.ncq = ncq, a.cb = cb;

@@ -426,6 +426,36 @@ def logits_iou_counts(z, targets, num_classes, ignore_label, counts=None):
     return counts
 
 
+def lowres_iou_supported(z_q, size):
+    """The geometries ``mas_lowres_iou_counts`` takes for quarter-resolution logits ``z_q`` [B,CH,h,w] and an output ``size`` (H, W):
+    those of ``naive_plbl_supported`` (the identity, or h <= H, w <= W, W <= 6 w, H <= 65535), on a GPU tensor."""
+    return z_q.is_cuda and naive_plbl_supported(z_q, size)
+
+
+def lowres_iou_counts(z_q, targets, size, num_classes, ignore_label, counts=None):
+    """``logits_iou_counts`` of the bilinear upsampling of quarter-resolution logits ``z_q`` f32 [B,channels,h,w] to ``size`` = (H, W),
+    without materialising it (``csrc/lowres_iou.hip``): the counters equal
+    ``logits_iou_counts(upsample_bilinear(z_q, size), targets, ...)`` element for element.  targets int64 [B,H,W].  A geometry
+    ``lowres_iou_supported`` declines and CPU tensors raise: there is no fall-back."""
+    _need(z_q, "z_q", torch.float32)
+    _need(targets, "targets", torch.int64)
+    H, W = int(size[0]), int(size[1])
+    if z_q.dim() != 4:
+        raise ValueError("z_q must be [B,channels,h,w], got %s" % (tuple(z_q.shape),))
+    B, CH, h, w = z_q.shape
+    if tuple(targets.shape) != (B, H, W):
+        raise ValueError("targets %s do not match %d pictures of %dx%d" % (tuple(targets.shape), B, H, W))
+    if not lowres_iou_supported(z_q, (H, W)):
+        raise ValueError("lowres_iou_counts: logits %s cannot be upsampled to %dx%d (an upsampling with W <= 6 w, or the identity)"
+                         % (tuple(z_q.shape), H, W))
+    if counts is None:
+        counts = torch.zeros(3 * num_classes + 3, dtype=torch.int64, device=z_q.device)
+    with torch.cuda.device(z_q.device):
+        _lib.check(_lib.load().mas_lowres_iou_counts(z_q.data_ptr(), targets.data_ptr(), B, CH, h, w, H, W, num_classes,
+                                                     int(ignore_label), counts.data_ptr(), _stream(z_q)), "mas_lowres_iou_counts")
+    return counts
+
+
 # ------------------------------------------------------------------------------------------------
 # single-pass acquisition scan
 # ------------------------------------------------------------------------------------------------

@@ -6,6 +6,8 @@ on the device (``csrc/metrics.hip``) instead of 19 x 3 host-synchronising reduct
 ``IoUIgnore``: IoU of the extra "undefined" class (label ``num_classes`` in the prediction,
 ``ignore_label`` in the ground truth).
 ``LogitsIoU`` (new): both meters from one read of the logits (fused arg-max).
+``LowresLogitsIoU`` (new): the same counters from the quarter-resolution logits (``net(x, lowres=True)``), upsampled per pixel in
+registers: the full-resolution logits never exist.
 The only host synchronisation is in ``_after_epoch`` / ``total_*`` (one copy of 3C+3 integers).
 """
 import numpy as np
@@ -138,3 +140,12 @@ class LogitsIoU(MeanIoU):
         c = self._host_counts()
         seen, correct, positive = c[3 * self.num_classes:3 * self.num_classes + 3]
         return 100.0 if seen == 0 else correct / (seen + positive - correct) * 100
+
+
+class LowresLogitsIoU(LogitsIoU):
+    """``LogitsIoU`` fed the network's quarter-resolution logits: ``step_lowres(z_q, labels)`` counts what ``step`` counts on
+    ``ops.upsample_bilinear(z_q, labels.shape[-2:])``, counter for counter (``ops.lowres_iou_counts``)."""
+
+    def step_lowres(self, z_q, labels):
+        ops.lowres_iou_counts(z_q.contiguous(), labels.contiguous(), labels.shape[-2:], self.num_classes, self.ignore_label,
+                              self._ensure(z_q.device))
