@@ -19,10 +19,12 @@ finish it (`engine.AcquisitionRound` -- the product object, not a private loop):
               sort + fair-counting budget walk on every rank (engine.select_regions; one rank: keys, sort, walk over all regions).
 value = N * K * 4 * 2048 / seconds (max over ranks, barrier + synchronize on both sides).
 
-Secondary legs (same JSON line): the reference-structured two-pass kernels; "pool_round" -- the FIXED 2 975-picture x
-2 048-superpixel pool with a 100 000-click budget through RegionSelector.select_next_batch, sharded over the ranks (strong
-scaling), scan-only and with the model forward; "train_iter" / "train_iter_769" -- the stage-1 step at the reference's real
-768x768 crop and at BASELINE.json's literal 769x769; "acquisition_with_model"; "stage2"; "cpu_baseline" (rank 0, N = 1).
+A plain run does only that: set-up, W warm-up steps, the K timed steps, --dump-outputs, and the line (with the "roofline" of
+the timed scans, read from their own events).  --full adds the secondary legs to the same JSON line: "two_pass" -- the
+reference-structured two-pass kernels; "pool_round" -- the FIXED 2 975-picture x 2 048-superpixel pool with a 100 000-click
+budget through RegionSelector.select_next_batch, sharded over the ranks (strong scaling), scan-only and with the model forward;
+"train_iter" / "train_iter_769" -- the stage-1 step at the reference's real 768x768 crop and at BASELINE.json's literal 769x769;
+"acquisition_with_model"; "stage2"; "cpu_baseline" (rank 0, N = 1).  The --no-* switches trim what --full runs.
 
 Prints ONE JSON line on rank 0.
 """
@@ -63,6 +65,9 @@ def parse():
                     help="superpixel id element type (the reference data layer yields int64)")
     ap.add_argument("--ramp", type=int, default=500, help="untimed launches before the warm-up steps (GPU clock ramp: 100 launches leave the scan ~6 % slower than 400+, tools/ramp_probe.sh)")
     ap.add_argument("--nbuf", type=int, default=3, help="distinct resident batches rotated through")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed round, run the secondary legs too (two-pass kernels, pool round, model legs, CPU baseline); "
+                         "the options below up to --cpu-full apply to them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="skip the model legs (train-iter, acquisition with model, stage 2)")
     ap.add_argument("--no-trainleg", action="store_true", help="skip the train-iter and stage-2 legs but keep the acquisition leg with the model forward")
@@ -886,6 +891,94 @@ def pmc_traffic(kernel, default_shape):
     return None, None
 
 
+def full_legs(args, dev, rank, world, backend, bufs, out):
+    """--full: the secondary legs, after the timed round, into the same line `out`.  `bufs` is the caller's list of resident
+    batches: it is emptied here, so that they are freed unless the CPU baseline still reads them."""
+    from mulactseg_amd import ops
+    B, C, H, W, S = args.batch, args.classes, args.height, args.width, args.nseg
+    invT = ops.inv_temperature(0.1)
+    id_bytes = {"int64": 8, "int32": 4, "int16": 2}[args.id_dtype]
+
+    # reference-structured two-pass kernels on the same buffers (secondary; not part of `value`)
+    def time_kernel(fn, n=100):
+        for _ in range(2):
+            fn()
+        torch.cuda.synchronize()
+        es = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+        for k, (a, b) in enumerate(es):
+            a.record(); fn(k); b.record()
+        torch.cuda.synchronize()
+        return float(np.mean([a.elapsed_time(b) for a, b in es]))
+    cls_w = torch.linspace(0.3, 1.0, C, device=dev)
+    p2 = torch.zeros((B, C), dtype=torch.int64, device=dev)
+    s2 = torch.zeros((B, S), dtype=torch.int64, device=dev)
+    h2 = torch.zeros((B, S, C), dtype=torch.int32, device=dev)
+    k2_ms = time_kernel(lambda k=0: ops.class_prob_sum(bufs[k % args.nbuf][0], invT, out=p2))
+    k3_ms = time_kernel(lambda k=0: ops.bvsb_region_accum(bufs[k % args.nbuf][0], bufs[k % args.nbuf][1], cls_w, S, invT,
+                                                          score_sum=s2, hist=h2))
+    k2_bytes = B * (C * H * W * 4)
+    k3_bytes = B * (C * H * W * 4 + H * W * id_bytes + S * (8 + 4 * C))
+    default_shape = (B, C, H, W, S, args.id_dtype) == (4, 20, 1024, 2048, 2048, "int64")
+    traffic3, traffic3_src = pmc_traffic("k_bvsb_region_accum", default_shape)
+    out["two_pass"] = {"k_class_prob_sum": {"avg_launch_ms": k2_ms, "achieved_GBs": k2_bytes / (k2_ms * 1e-3) / 1e9,
+                                            "bytes_per_launch": k2_bytes},
+                       "k_bvsb_region_accum": {"avg_launch_ms": k3_ms, "achieved_GBs": k3_bytes / (k3_ms * 1e-3) / 1e9,
+                                               "frac_of_peak": k3_bytes / (k3_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                               "bytes_per_launch": k3_bytes, "traffic": traffic3, "traffic_source": traffic3_src},
+                       "superpixels_per_s": B * S * world / ((k2_ms + k3_ms) * 1e-3)}
+
+    def secondary(fn, *a):
+        """Secondary legs never take the primary line down with them."""
+        try:
+            return fn(*a)
+        except Exception as e:          # noqa: BLE001
+            return {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
+    cpu_bufs = list(bufs) if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    bufs.clear()
+    torch.cuda.empty_cache()
+    if not args.no_pool:
+        out["pool_round"] = {"metric": "acquisition round over the fixed %d-picture x %d-superpixel pool, %d clicks, through "
+                                       "RegionSelector.select_next_batch; sharded over %d rank(s)" % (POOL_IMAGES, S, POOL_CLICKS, world),
+                             "scaling": "strong",
+                             # the first round of a process pays first-use costs that no later round of the loop sees (code objects
+                             # of the ordering / walk kernels and of the ATen ops behind the tail, allocator growth: ~0.05 s): one
+                             # round over a 64-picture pool of the same shapes is run before the timed one, as the W warm-up steps are
+                             "warm_up": "one untimed round over a %d-picture pool (%d clicks) before the timed ones" % (POOL_WARM_IMAGES, POOL_WARM_CLICKS),
+                             "scan_only": (secondary(pool_round_bench, args, dev, rank, world, False, POOL_WARM_IMAGES, POOL_WARM_CLICKS),
+                                           secondary(pool_round_bench, args, dev, rank, world, False))[1],
+                             "with_model_forward": None if args.no_train else secondary(pool_round_bench, args, dev, rank, world, True)}
+        torch.cuda.empty_cache()
+    def leg(fn, *a):
+        # every leg starts from an empty caching allocator: the blocks a previous leg left behind fit the next leg's shapes badly (the
+        # 769 crop after the 768 one) and what the allocator then carves out of them is scattered -- not part of any timed region
+        gc.collect()
+        torch.cuda.empty_cache()
+        return secondary(fn, *a)
+    out["train_iter"] = None if (args.no_train or args.no_trainleg) else leg(train_iter_bench, args, dev, world, args.crop)
+    out["train_iter_769"] = None if (args.no_train or args.no_trainleg) else leg(train_iter_bench, args, dev, world, 769)
+    out["acquisition_with_model"] = None if args.no_train else leg(acquisition_with_model_bench, args, dev, world)
+    out["stage2"] = None if (args.no_train or args.no_trainleg or rank != 0) else secondary(stage2_bench, args, dev)
+    # the secondary legs' headline numbers as TOP-LEVEL keys (a reader of the parsed line need not dig through the nested objects)
+    def pick(d, *path):
+        for k in path:
+            if not isinstance(d, dict) or k not in d:
+                return None
+            d = d[k]
+        return d
+    out["train_iter_ms_768"] = pick(out, "train_iter", "ms_per_iter")
+    out["train_iter_images_per_s_768"] = pick(out, "train_iter", "value")
+    out["train_iter_mfma_frac_768"] = pick(out, "train_iter", "mfma", "mfma_frac")
+    out["train_iter_ms_769"] = pick(out, "train_iter_769", "ms_per_iter")
+    out["train_iter_images_per_s_769"] = pick(out, "train_iter_769", "value")
+    out["pool_forward_ms_per_batch"] = pick(out, "acquisition_with_model", "ms_per_batch")
+    out["pool_forward_mfma_frac"] = pick(out, "acquisition_with_model", "mfma", "mfma_frac")
+    out["pool_round_scan_only_s"] = pick(out, "pool_round", "scan_only", "seconds")
+    out["pool_round_with_model_s"] = pick(out, "pool_round", "with_model_forward", "seconds")
+    out["loss_gpu_ms_fwd_bwd"] = pick(out, "train_iter", "loss_only", "gpu_ms_fwd_bwd")
+    if rank == 0:
+        out["cpu_baseline"] = secondary(cpu_baseline, args, dev, cpu_bufs, backend) if cpu_bufs is not None else None
+
+
 def rank_launch_command(n_gpus, argv, port):
     """The command `python bench.py --gpus N` runs when no launcher is around it: one rank per GPU of this node over RCCL,
     rendezvous on 127.0.0.1 (the container hostname may not resolve)."""
@@ -958,33 +1051,12 @@ def main():
     # algorithmic bytes of one k_single_pass launch: logits + ids read once, (prob + class sums + hist) written once
     sp_bytes = B * (C * H * W * 4 + H * W * id_bytes + S * C * (8 + 4) + C * 8)
     ach = sp_bytes / (sp_ms * 1e-3) / 1e9
-
-    # reference-structured two-pass kernels on the same buffers (secondary; not part of `value`)
-    def time_kernel(fn, n=100):
-        for _ in range(2):
-            fn()
-        torch.cuda.synchronize()
-        es = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
-        for k, (a, b) in enumerate(es):
-            a.record(); fn(k); b.record()
-        torch.cuda.synchronize()
-        return float(np.mean([a.elapsed_time(b) for a, b in es]))
-    cls_w = torch.linspace(0.3, 1.0, C, device=dev)
-    p2 = torch.zeros((B, C), dtype=torch.int64, device=dev)
-    s2 = torch.zeros((B, S), dtype=torch.int64, device=dev)
-    h2 = torch.zeros((B, S, C), dtype=torch.int32, device=dev)
-    k2_ms = time_kernel(lambda k=0: ops.class_prob_sum(bufs[k % args.nbuf][0], invT, out=p2))
-    k3_ms = time_kernel(lambda k=0: ops.bvsb_region_accum(bufs[k % args.nbuf][0], bufs[k % args.nbuf][1], cls_w, S, invT,
-                                                          score_sum=s2, hist=h2))
-    k2_bytes = B * (C * H * W * 4)
-    k3_bytes = B * (C * H * W * 4 + H * W * id_bytes + S * (8 + 4 * C))
     default_shape = (B, C, H, W, S, args.id_dtype) == (4, 20, 1024, 2048, 2048, "int64")
     traffic, traffic_src = pmc_traffic("k_single_pass", default_shape)
-    traffic3, traffic3_src = pmc_traffic("k_bvsb_region_accum", default_shape)
     out = {
         "metric": "superpixels scored/sec", "value": args.steps * B * S * world / dt, "unit": "superpixels/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
         "config": {"workload": "acquisition-round: PixBal+ban-ignore scorer on resident logits, Cityscapes pool shape [%d,%d,%d,%d] per step; "
                                "per rank K single-pass scans (class prior + region sums + histograms) of its shard, then exchange 1 "
                                "(all-gather class sums) + device class weights (k_class_weight) + weighted finalize + ban + exchange 2 (all-gather scores) + "
@@ -997,66 +1069,11 @@ def main():
         "roofline": {"bound": "hbm", "kernel": "k_single_pass", "achieved": ach, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                      "bytes_per_launch": sp_bytes, "avg_launch_ms": sp_ms},
-        "two_pass": {"k_class_prob_sum": {"avg_launch_ms": k2_ms, "achieved_GBs": k2_bytes / (k2_ms * 1e-3) / 1e9,
-                                          "bytes_per_launch": k2_bytes},
-                     "k_bvsb_region_accum": {"avg_launch_ms": k3_ms, "achieved_GBs": k3_bytes / (k3_ms * 1e-3) / 1e9,
-                                             "frac_of_peak": k3_bytes / (k3_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                             "bytes_per_launch": k3_bytes, "traffic": traffic3, "traffic_source": traffic3_src},
-                     "superpixels_per_s": B * S * world / ((k2_ms + k3_ms) * 1e-3)},
     }
-
-    def secondary(fn, *a):
-        """Secondary legs never take the primary line down with them."""
-        try:
-            return fn(*a)
-        except Exception as e:          # noqa: BLE001
-            return {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-    cpu_bufs = bufs if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
-    if cpu_bufs is None:
-        del bufs
-    del timed
-    torch.cuda.empty_cache()
-    if not args.no_pool:
-        out["pool_round"] = {"metric": "acquisition round over the fixed %d-picture x %d-superpixel pool, %d clicks, through "
-                                       "RegionSelector.select_next_batch; sharded over %d rank(s)" % (POOL_IMAGES, S, POOL_CLICKS, world),
-                             "scaling": "strong",
-                             # the first round of a process pays first-use costs that no later round of the loop sees (code objects
-                             # of the ordering / walk kernels and of the ATen ops behind the tail, allocator growth: ~0.05 s): one
-                             # round over a 64-picture pool of the same shapes is run before the timed one, as the W warm-up steps are
-                             "warm_up": "one untimed round over a %d-picture pool (%d clicks) before the timed ones" % (POOL_WARM_IMAGES, POOL_WARM_CLICKS),
-                             "scan_only": (secondary(pool_round_bench, args, dev, rank, world, False, POOL_WARM_IMAGES, POOL_WARM_CLICKS),
-                                           secondary(pool_round_bench, args, dev, rank, world, False))[1],
-                             "with_model_forward": None if args.no_train else secondary(pool_round_bench, args, dev, rank, world, True)}
-        torch.cuda.empty_cache()
-    def leg(fn, *a):
-        # every leg starts from an empty caching allocator: the blocks a previous leg left behind fit the next leg's shapes badly (the
-        # 769 crop after the 768 one) and what the allocator then carves out of them is scattered -- not part of any timed region
-        gc.collect()
-        torch.cuda.empty_cache()
-        return secondary(fn, *a)
-    out["train_iter"] = None if (args.no_train or args.no_trainleg) else leg(train_iter_bench, args, dev, world, args.crop)
-    out["train_iter_769"] = None if (args.no_train or args.no_trainleg) else leg(train_iter_bench, args, dev, world, 769)
-    out["acquisition_with_model"] = None if args.no_train else leg(acquisition_with_model_bench, args, dev, world)
-    out["stage2"] = None if (args.no_train or args.no_trainleg or rank != 0) else secondary(stage2_bench, args, dev)
-    # the secondary legs' headline numbers as TOP-LEVEL keys (a reader of the parsed line need not dig through the nested objects)
-    def pick(d, *path):
-        for k in path:
-            if not isinstance(d, dict) or k not in d:
-                return None
-            d = d[k]
-        return d
-    out["train_iter_ms_768"] = pick(out, "train_iter", "ms_per_iter")
-    out["train_iter_images_per_s_768"] = pick(out, "train_iter", "value")
-    out["train_iter_mfma_frac_768"] = pick(out, "train_iter", "mfma", "mfma_frac")
-    out["train_iter_ms_769"] = pick(out, "train_iter_769", "ms_per_iter")
-    out["train_iter_images_per_s_769"] = pick(out, "train_iter_769", "value")
-    out["pool_forward_ms_per_batch"] = pick(out, "acquisition_with_model", "ms_per_batch")
-    out["pool_forward_mfma_frac"] = pick(out, "acquisition_with_model", "mfma", "mfma_frac")
-    out["pool_round_scan_only_s"] = pick(out, "pool_round", "scan_only", "seconds")
-    out["pool_round_with_model_s"] = pick(out, "pool_round", "with_model_forward", "seconds")
-    out["loss_gpu_ms_fwd_bwd"] = pick(out, "train_iter", "loss_only", "gpu_ms_fwd_bwd")
+    if args.full:
+        del timed
+        full_legs(args, dev, rank, world, backend, bufs, out)
     if rank == 0:
-        out["cpu_baseline"] = secondary(cpu_baseline, args, dev, cpu_bufs, backend) if cpu_bufs is not None else None
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     d = _dist()

@@ -9,7 +9,7 @@ for L in product libbx_3of6.so; do
   python tools/layer_alone.py --cin 512 --cout 512 --h 64 --w 128 --dil 2 2>&1 | grep "us per"
   python tools/layer_alone.py --cin 2048 --cout 512 --h 64 --w 128 --k 1 2>&1 | grep "us per"
   python tools/layer_alone.py --cin 64 --cout 256 --h 256 --w 512 --k 1 2>&1 | grep "us per"
-  python bench.py --no-cpu-baseline --no-pool --no-trainleg --steps 2 --warmup 1 --ramp 0 --acq-steps 24 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-pool --no-trainleg --steps 2 --warmup 1 --ramp 0 --acq-steps 24 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('pool batch %.2f ms' % d['pool_forward_ms_per_batch'])"

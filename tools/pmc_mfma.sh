@@ -1,11 +1,12 @@
 # MFMA utilisation of the stage-1 train step (bench.py train_iter leg): PMC pass (kernel-trace + counters only)
 set -eu; cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
-rm -rf gpurun_out/mf && rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 GRBM_GUI_ACTIVE --output-format csv -d gpurun_out/mf -o m -- python bench.py --no-cpu-baseline --steps 2 --warmup 1 --ramp 0 --train-steps 6 --acq-steps 1 > /dev/null 2>&1
+O=${OUT:-build/profile}; mkdir -p $O; export O     # where the traces and tables go
+rm -rf $O/mf && rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 GRBM_GUI_ACTIVE --output-format csv -d $O/mf -o m -- python bench.py --full --no-cpu-baseline --steps 2 --warmup 1 --ramp 0 --train-steps 6 --acq-steps 1 > /dev/null 2>&1
 python - <<'PY'
-import csv, collections, sys
+import csv, collections, os, sys
 sys.path.insert(0, 'profiles')
 from summarize import short
-cc = list(csv.DictReader(open('gpurun_out/mf/m_counter_collection.csv')))
+cc = list(csv.DictReader(open(os.path.join(os.environ['O'], 'mf/m_counter_collection.csv'))))
 # dispatches in order; find optimizer markers to keep the last 3 train steps
 disp = collections.OrderedDict()
 for r in cc:
@@ -40,6 +41,6 @@ out = ["# MFMA utilisation of the stage-1 train step (3 steady steps, rocprofv3 
        "| kernel | calls/step | MfmaUtil | share of MFMA cycles |", "|---|---|---|---|"]
 for m, k, v in rows[:16]:
     out.append("| %s | %.1f | %.3f | %.1f %% |" % (k[:90], v['n'] / 3, m / max(1.0, 4 * v['SQ_BUSY_CU_CYCLES']), 100 * m / max(1.0, tot['SQ_VALU_MFMA_BUSY_CYCLES'])))
-open('gpurun_out/j_train_step_mfma_pmc.md', 'w').write("\n".join(out) + "\n")
+open(os.path.join(os.environ['O'], 'j_train_step_mfma_pmc.md'), 'w').write("\n".join(out) + "\n")
 print("\n".join(out))
 PY

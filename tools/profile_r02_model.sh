@@ -1,11 +1,12 @@
 # round 2: kernel traces of the model legs (pool forward on the MFMA convolution; train step at 768 and 769) + MFMA PMC of the pool forward
 set -eu; cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
-rm -rf gpurun_out/tr2 && rocprofv3 --kernel-trace --output-format csv -d gpurun_out/tr2 -o t -- python bench.py --no-cpu-baseline --no-pool --steps 2 --warmup 1 --ramp 0 --train-steps 8 --acq-steps 8 > gpurun_out/tr2_bench.json 2>/dev/null
+O=${OUT:-build/profile}; mkdir -p $O; export O     # where the traces and tables go
+rm -rf $O/tr2 && rocprofv3 --kernel-trace --output-format csv -d $O/tr2 -o t -- python bench.py --full --no-cpu-baseline --no-pool --steps 2 --warmup 1 --ramp 0 --train-steps 8 --acq-steps 8 > $O/tr2_bench.json 2>/dev/null
 python - <<'PY'
-import csv, collections, sys
+import csv, collections, os, sys
 sys.path.insert(0, 'profiles')
 from summarize import short
-rows = list(csv.DictReader(open('gpurun_out/tr2/t_kernel_trace.csv')))
+rows = list(csv.DictReader(open(os.path.join(os.environ['O'], 'tr2/t_kernel_trace.csv'))))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 # optimizer-step groups: the first run of train steps is crop 768, the second crop 769
 ends, last = [], None
@@ -29,16 +30,16 @@ def table(a, b, n, title, out):
     print("\n".join(lines[:14]))
 print(len(ends), "optimizer steps")
 if len(ends) >= 22:
-    table(ends[4], ends[10], 6, "train step, crop 768: steady-state kernel breakdown (last 6 steps)", 'gpurun_out/c_train_768_steady.md')
-    table(ends[15], ends[21], 6, "train step, crop 769: steady-state kernel breakdown (last 6 steps)", 'gpurun_out/d_train_769_steady.md')
+    table(ends[4], ends[10], 6, "train step, crop 768: steady-state kernel breakdown (last 6 steps)", os.path.join(os.environ['O'], 'c_train_768_steady.md'))
+    table(ends[15], ends[21], 6, "train step, crop 769: steady-state kernel breakdown (last 6 steps)", os.path.join(os.environ['O'], 'd_train_769_steady.md'))
 PY
-python profiles/steady.py gpurun_out/tr2/t_kernel_trace.csv k_cosine_fwd4 5 gpurun_out/e_pool_forward_steady.md "rocprofv3 --kernel-trace -- python bench.py --no-cpu-baseline --no-pool --steps 2 --warmup 1 --ramp 0 --train-steps 8 --acq-steps 8 (acquisition_with_model leg)" | head -30
-rm -rf gpurun_out/mf2 && rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 GRBM_GUI_ACTIVE --output-format csv -d gpurun_out/mf2 -o m -- python bench.py --no-cpu-baseline --no-pool --no-trainleg --steps 2 --warmup 1 --ramp 0 --acq-steps 4 > /dev/null 2>&1
+python profiles/steady.py $O/tr2/t_kernel_trace.csv k_cosine_fwd4 5 $O/e_pool_forward_steady.md "rocprofv3 --kernel-trace -- python bench.py --full --no-cpu-baseline --no-pool --steps 2 --warmup 1 --ramp 0 --train-steps 8 --acq-steps 8 (acquisition_with_model leg)" | head -30
+rm -rf $O/mf2 && rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 GRBM_GUI_ACTIVE --output-format csv -d $O/mf2 -o m -- python bench.py --full --no-cpu-baseline --no-pool --no-trainleg --steps 2 --warmup 1 --ramp 0 --acq-steps 4 > /dev/null 2>&1
 python - <<'PY'
-import csv, collections, sys
+import csv, collections, os, sys
 sys.path.insert(0, 'profiles')
 from summarize import short
-cc = list(csv.DictReader(open('gpurun_out/mf2/m_counter_collection.csv')))
+cc = list(csv.DictReader(open(os.path.join(os.environ['O'], 'mf2/m_counter_collection.csv'))))
 disp = collections.OrderedDict()
 for r in cc:
     e = disp.setdefault(int(r['Dispatch_Id']), {'name': r['Kernel_Name']})
@@ -66,6 +67,6 @@ out = ["# MFMA utilisation of the pool forward + scan (3 steady steps, rocprofv3
        "| kernel | calls/step | MfmaUtil | share of MFMA cycles |", "|---|---|---|---|"]
 for m, k, v in rows[:12]:
     out.append("| %s | %.1f | %.3f | %.1f %% |" % (k[:90], v['n'] / 3, m / max(1.0, 4 * v['SQ_BUSY_CU_CYCLES']), 100 * m / max(1.0, tot['SQ_VALU_MFMA_BUSY_CYCLES'])))
-open('gpurun_out/f_pool_forward_mfma_pmc.md', 'w').write("\n".join(out) + "\n")
+open(os.path.join(os.environ['O'], 'f_pool_forward_mfma_pmc.md'), 'w').write("\n".join(out) + "\n")
 print("\n".join(out))
 PY

@@ -5,7 +5,7 @@
 set -eu; cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
 PART=${1:-scan}; O=gpurun_out/p4; mkdir -p $O
 if [ "$PART" = scan ]; then
-  CMD="python bench.py --no-cpu-baseline --no-train --no-pool"
+  CMD="python bench.py --full --no-cpu-baseline --no-train --no-pool"
   rm -rf $O/s_stats $O/s_fetch $O/s_write
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/s_stats -o s -- $CMD > $O/scan_bench.json 2> /dev/null
   rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/s_fetch -o s -- $CMD --steps 20 --warmup 2 --ramp 0 > /dev/null 2>&1
@@ -14,7 +14,7 @@ if [ "$PART" = scan ]; then
   python profiles/summarize.py pmc $(find $O/s_fetch -name "*counter_collection.csv") $(find $O/s_write -name "*counter_collection.csv") $O/b_pmc_traffic.json "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- $CMD --steps 20 --warmup 2 --ramp 0"
   head -12 $O/a_bench_kernel_stats.md; head -c 900 $O/b_pmc_traffic.json
 elif [ "$PART" = pool ]; then
-  CMD="python bench.py --no-cpu-baseline --no-pool --no-trainleg --steps 2 --warmup 1 --ramp 0 --acq-steps 8"
+  CMD="python bench.py --full --no-cpu-baseline --no-pool --no-trainleg --steps 2 --warmup 1 --ramp 0 --acq-steps 8"
   rm -rf $O/p_tr $O/p_mf $O/p_fetch $O/p_write
   rocprofv3 --kernel-trace --output-format csv -d $O/p_tr -o t -- $CMD > $O/pool_bench.json 2> /dev/null
   python profiles/steady.py $O/p_tr/t_kernel_trace.csv k_cosine_fwd4 5 $O/e_pool_forward_steady.md "rocprofv3 --kernel-trace -- $CMD (acquisition leg only: no train / stage-2 leg in the process)" > /dev/null
