@@ -54,8 +54,9 @@ extern "C" {
  * mas_conv_bx_fwd); 6 = role 2 of mas_conv_bx_pack / _packed_bytes / _pack_job and ksize 3 at stride 2 in mas_conv_bx_supported /
  * mas_conv_bx_fwd (a library of version 5 answers "unsupported" to both); 8 = the region-label entry points of the data-generation
  * step (mas_region_label_counts, mas_region_multi_hot, mas_region_dominant, mas_region_paint); 9 = mas_ms_ensemble.  mas_naive_plbl and
- * mas_spx_max_onehot came later under 9, then mas_lowres_iou_counts: new entry points change no existing signature or argument; a
- * library built before them lacks their symbols, and load() refuses it with a rebuild message rather than binding a partial table. */
+ * mas_spx_max_onehot came later under 9, then mas_lowres_iou_counts, then mas_render_labels and mas_render_lowres_pred: new entry
+ * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
+ * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
 int mas_abi_version(void);
 const char* mas_error_string(int code);
@@ -464,6 +465,25 @@ int mas_ms_ensemble(const float* const* feats_q, const float* const* logits_q, c
  * mas_upsample_bilinear_fwd accepts); MAS_ERR_SHAPE otherwise.  C <= 255. */
 int mas_naive_plbl(const float* logits_q, int N, int C, int h, int w, int H, int W, const uint8_t* mask /* [N,H,W] or NULL */, float th,
                    uint8_t* labels /* [N,H,W] */, void* stream);
+
+/* Colour images of label maps (--save_vis of the stage-2 generators, trainer/eval_save_cosplbl_prop.py:77-86; eval_naive_vis.py:70-83).
+ * labels [N,H,W] of label_dtype MAS_ID_I64 or MAS_MAP_U8; palette u8 [P,3], 1 <= P <= 256; a label 255 takes the colour of `fill`
+ * (0 <= fill < P).  mark_boundaries == 0: rgb u8 [N,H,W,3] = palette[label] (spx unused, may be NULL).  mark_boundaries != 0: spx
+ * int64 [N,H,W] required; the image of skimage's mark_boundaries(colours, spx) * 255 cast to uint8 with its defaults (mode 'outer',
+ * background 0, colour (1, 1, 0)): pixels on the outer boundaries of the id map are (255, 255, 0), every other channel value c is
+ * uint8(float64(c) / 255 * 255) (csrc/render.hip states the rule).  A label outside [0, P) after the fill is a device error: it is
+ * counted into *n_bad (one u32 in device memory, accumulated, not reset) and its pixel written (0, 0, 0); the caller reads the count.
+ * rgb must be 4-byte aligned (MAS_ERR_ALIGN). */
+int mas_render_labels(const void* labels, int label_dtype, int N, int H, int W, const uint8_t* palette, int P, int fill,
+                      const int64_t* spx, int mark_boundaries, uint8_t* rgb /* [N,H,W,3] */, unsigned* n_bad, void* stream);
+
+/* rgb u8 [N,H,W,3] = palette[first arg-max over channels 0..CH-2 of the bilinear upsampling of z_q f32 [N,CH,h,w] to H x W]
+ * (eval_naive_vis.py:70: decode_target(preds[:, :-1].max(1)[1])), the labels those of mas_naive_plbl on the first CH - 1 channels
+ * (bit for bit ops.upsample_bilinear + torch.max), without the full-resolution logits.  Geometries: those of mas_naive_plbl
+ * (MAS_ERR_SHAPE otherwise); 2 <= CH <= 256 (MAS_ERR_CLASSES); CH - 1 <= P <= 256 (MAS_ERR_RANGE).  work: (N + 1) * H * W bytes of
+ * device memory.  rgb 4-byte aligned. */
+int mas_render_lowres_pred(const float* z_q, int N, int CH, int h, int w, int H, int W, const uint8_t* palette, int P,
+                           uint8_t* work /* [(N+1)*H*W] */, uint8_t* rgb /* [N,H,W,3] */, void* stream);
 
 /* BatchNorm2d fused with the following ReLU and residual add (models/segmentation/backbone/resnet.py:143-160 Bottleneck,
  * the conv -> bn -> relu triples of the stem / ASPP / decoder, deeplabv3.py:93-110,216-245).  x, y, residual: [N,C,HW]

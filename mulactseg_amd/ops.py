@@ -456,6 +456,69 @@ def lowres_iou_counts(z_q, targets, size, num_classes, ignore_label, counts=None
     return counts
 
 
+def render_labels(labels, palette, fill, superpixels=None):
+    """Colour image u8 ``[N,H,W,3]`` of the label maps ``labels`` (int64 or uint8 ``[N,H,W]``) -- the ``--save_vis`` images of the
+    stage-2 generators and the ``eval_naive_vis`` pictures (``csrc/render.hip``).  ``palette`` u8 ``[P,3]`` on the GPU (P <= 256), label
+    255 painted as ``fill``.  Without ``superpixels``: ``palette[label]``.  With ``superpixels`` (int64 ``[N,H,W]``): the reference's
+    ``mark_boundaries(colours, superpixels) * 255`` cast to uint8 (outer boundaries in (255, 255, 0), the other bytes through
+    skimage's float64 round trip).  A label outside the palette after the fill raises
+    ``MulActSegHipError`` (counted on the device; reading the count waits for this stream).  CPU tensors raise: there is no
+    fall-back."""
+    _need(labels, "labels")
+    _need(palette, "palette", torch.uint8)
+    if labels.dtype not in (torch.int64, torch.uint8):
+        raise TypeError("labels must be torch.int64 or torch.uint8, got %s" % labels.dtype)
+    if labels.dim() != 3:
+        raise ValueError("labels must be [N,H,W], got %s" % (tuple(labels.shape),))
+    if palette.dim() != 2 or palette.shape[1] != 3 or not 1 <= palette.shape[0] <= 256:
+        raise ValueError("palette must be [P,3] with 1 <= P <= 256, got %s" % (tuple(palette.shape),))
+    P = int(palette.shape[0])
+    if not 0 <= int(fill) < P:
+        raise ValueError("fill %d is not an index of the %d-colour palette" % (int(fill), P))
+    N, H, W = labels.shape
+    if superpixels is not None:
+        _need(superpixels, "superpixels", torch.int64)
+        if tuple(superpixels.shape) != (N, H, W):
+            raise ValueError("superpixels %s do not match labels %s" % (tuple(superpixels.shape), tuple(labels.shape)))
+    rgb = torch.empty((N, H, W, 3), dtype=torch.uint8, device=labels.device)
+    bad = torch.zeros(1, dtype=torch.int32, device=labels.device)
+    dt = _lib.ID_I64 if labels.dtype == torch.int64 else _lib.MAP_U8
+    with torch.cuda.device(labels.device):
+        _lib.check(_lib.load().mas_render_labels(labels.data_ptr(), dt, N, H, W, palette.data_ptr(), P, int(fill),
+                                                 None if superpixels is None else superpixels.data_ptr(), int(superpixels is not None),
+                                                 rgb.data_ptr(), bad.data_ptr(), _stream(labels)), "mas_render_labels")
+    n_bad = int(bad.item())
+    if n_bad:
+        raise _lib.MulActSegHipError("render_labels: %d label(s) outside the %d-colour palette after filling 255 with %d"
+                                     % (n_bad, P, int(fill)))
+    return rgb
+
+
+def render_lowres_pred(z_q, size, palette):
+    """Colour image u8 ``[N,H,W,3]`` of ``palette[first arg-max over channels 0..CH-2 of upsample_bilinear(z_q, size)]`` --
+    ``decode_target(preds[:, :-1].max(1)[1])`` of ``eval_naive_vis`` from the quarter-resolution logits ``z_q`` f32 ``[N,CH,h,w]``,
+    equal to ``palette[torch.max(ops.upsample_bilinear(z_q, size)[:, :-1], 1)[1]]`` (first maximum, first NaN) without the
+    full-resolution logits.  Geometries: those of ``naive_plbl_supported``; ``palette`` u8 ``[P,3]`` with CH - 1 <= P <= 256.  CPU
+    tensors raise: there is no fall-back."""
+    _need(z_q, "z_q", torch.float32)
+    _need(palette, "palette", torch.uint8)
+    H, W = int(size[0]), int(size[1])
+    if z_q.dim() != 4:
+        raise ValueError("z_q must be [N,CH,h,w], got %s" % (tuple(z_q.shape),))
+    N, CH, h, w = z_q.shape
+    if not naive_plbl_supported(z_q, (H, W)):
+        raise ValueError("render_lowres_pred: logits %s cannot be upsampled to %dx%d (an upsampling with W <= 6 w, or the identity)"
+                         % (tuple(z_q.shape), H, W))
+    if palette.dim() != 2 or palette.shape[1] != 3 or not CH - 1 <= palette.shape[0] <= 256:
+        raise ValueError("palette must be [P,3] with %d <= P <= 256, got %s" % (CH - 1, tuple(palette.shape)))
+    rgb = torch.empty((N, H, W, 3), dtype=torch.uint8, device=z_q.device)
+    work = torch.empty((N + 1) * H * W, dtype=torch.uint8, device=z_q.device)
+    with torch.cuda.device(z_q.device):
+        _lib.check(_lib.load().mas_render_lowres_pred(z_q.data_ptr(), N, CH, h, w, H, W, palette.data_ptr(), int(palette.shape[0]),
+                                                      work.data_ptr(), rgb.data_ptr(), _stream(z_q)), "mas_render_lowres_pred")
+    return rgb
+
+
 # ------------------------------------------------------------------------------------------------
 # single-pass acquisition scan
 # ------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ import threading
 import torch
 
 from .. import ops
+from ..dataloader.constant import train_id_to_color
 from ..utils.miou import MeanIoU
 from . import eval_within_multihot
 
@@ -18,6 +19,8 @@ from . import eval_within_multihot
 class ActiveTrainer(eval_within_multihot.ActiveTrainer):
     include_onehot = False
     threaded_generation = None      # True / False: the loop below or the one-thread loop; None: threaded unless pseudo_labels is replaced
+    vis_palette = train_id_to_color     # --save_vis: decode_target's palette and the colour index of label 255 (:80, "unselected")
+    vis_fill = 20
 
     def __init__(self, args, logger, selection_iter):
         super().__init__(args, logger, selection_iter)
@@ -115,8 +118,30 @@ class ActiveTrainer(eval_within_multihot.ActiveTrainer):
         meter.all_reduce(self.device)
         return self.report(meter, prefix)
 
+    def _vis_dir(self):
+        """``'{}_vis'.format(save_dir)`` (:43-44), made on first use."""
+        d = '{}_vis'.format(self._save_dir())
+        os.makedirs(d, exist_ok=True)
+        return d
+
+    def vis_image(self, plbl, superpixels):
+        """The ``--save_vis`` picture of the first label map (:79-84) as a host uint8 [H,W,3] array: ``decode_target`` of the labels
+        with 255 painted ``vis_fill``, ``mark_boundaries`` over ``superpixels`` (the batch's map; int64 on the device), ``* 255``
+        cast to uint8."""
+        dev = plbl.device
+        pal = getattr(self, '_vis_pal', None)
+        if pal is None or pal.device != dev:
+            pal = self._vis_pal = torch.from_numpy(self.vis_palette.astype('uint8')).to(dev)
+        rgb = ops.render_labels(plbl[:1].contiguous(), pal, self.vis_fill, superpixels[:1].to(dev, dtype=torch.int64).contiguous())
+        return rgb[0].cpu().numpy()
+
     def after_batch(self, batch, plbl):
+        """Save the label PNG and, with ``--save_vis``, its colour picture over the batch's superpixel map ``batch['spx']`` (the map
+        the generator used; every caller's batch carries it, so the hook's signature stays the reference's)."""
         from PIL import Image
         fname = batch['fnames'][0][1]
         lbl_id = fname.split('/')[-1].split('.')[0]
         Image.fromarray(plbl[0].cpu().numpy().astype('uint8')).save("{}/{}.png".format(self._save_dir(), lbl_id))
+        if getattr(self.args, 'save_vis', False):
+            vis = self.vis_image(plbl, batch['spx'])
+            Image.fromarray(vis).save("{}/{}.png".format(self._vis_dir(), lbl_id))

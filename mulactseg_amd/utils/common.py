@@ -141,6 +141,7 @@ def get_parser():
     a('--small_nseg', type=int, default=2048)
     a('--trim_kernel_size', type=int, default=3)
     a('--trim_multihot_boundary', action='store_true', default=False)
+    a('--save_vis', action='store_true', default=False)  # stage-2 generators / eval_naive_vis: also write colour images
     a('--wandb_tags', nargs='+', default=None)
     a('--wandb_group', default=None)
     return p

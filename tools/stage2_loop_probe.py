@@ -2,7 +2,7 @@
 """Wall time per picture of the stage-2 pseudo-label generation LOOP (trainer/eval_save_cosplbl_prop*.py: forward at batch 1, K9 kernels,
 IoU counters, one PNG per picture) on synthetic resident 1024 x 2048 pictures -- the loop, not only the kernels bench.py's stage2 leg times.
 
-    python tools/stage2_loop_probe.py [--pictures 48]"""
+    python tools/stage2_loop_probe.py [--pictures 48] [--save_vis]"""
 import argparse
 import os
 import sys
@@ -20,6 +20,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pictures", type=int, default=48)
     ap.add_argument("--workers", type=int, nargs="+", default=[1, 2, 3, 4])
+    ap.add_argument("--save_vis", action="store_true", help="also render and write the --save_vis picture of every label map")
     a = ap.parse_args()
     from mulactseg_amd import synth
     from mulactseg_amd.models import get_model
@@ -65,7 +66,8 @@ def main():
         run = os.path.join(tmp, "w%d" % workers)
         os.makedirs(run)
         tr = object.__new__(G.ActiveTrainer)
-        tr.args = types.SimpleNamespace(ignore_idx=255, init_checkpoint=os.path.join(run, "checkpoint01.tar"), plbl_type=None, val_batch_size=1)
+        tr.args = types.SimpleNamespace(ignore_idx=255, init_checkpoint=os.path.join(run, "checkpoint01.tar"), plbl_type=None, val_batch_size=1,
+                                        save_vis=a.save_vis)
         tr.net, tr.device, tr.num_classes, tr.selection_iter, tr.save_dir = net, dev, C, 1, None
         tr.inference(Loader(6))                     # warm-up (first launches of the process, the threads' streams)
         torch.cuda.synchronize()
@@ -79,7 +81,7 @@ def main():
             h.update(f.encode())
             h.update(open(os.path.join(tr._save_dir(), f), "rb").read())
         results[workers] = (h.hexdigest(), table)
-        print("MAS_STAGE2_WORKERS=%d: %d pictures in %.2f s = %.1f ms per picture; %d PNGs, sha256 over names and bytes %s"
+        print(("--save_vis " if a.save_vis else "") + "MAS_STAGE2_WORKERS=%d: %d pictures in %.2f s = %.1f ms per picture; %d PNGs, sha256 over names and bytes %s"
               % (workers, a.pictures, dt, dt / a.pictures * 1e3, len(files), h.hexdigest()[:16]), flush=True)
     same = len(set(results.values())) == 1
     print("PNG files and IoU table identical for every worker count" if same else "MISMATCH between worker counts")
