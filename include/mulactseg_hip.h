@@ -54,7 +54,7 @@ extern "C" {
  * mas_conv_bx_fwd); 6 = role 2 of mas_conv_bx_pack / _packed_bytes / _pack_job and ksize 3 at stride 2 in mas_conv_bx_supported /
  * mas_conv_bx_fwd (a library of version 5 answers "unsupported" to both); 8 = the region-label entry points of the data-generation
  * step (mas_region_label_counts, mas_region_multi_hot, mas_region_dominant, mas_region_paint); 9 = mas_ms_ensemble.  mas_naive_plbl and
- * mas_spx_max_onehot came later under 9, then mas_lowres_iou_counts, then mas_render_labels and mas_render_lowres_pred: new entry
+ * mas_spx_max_onehot came later under 9, then mas_lowres_iou_counts, then mas_render_labels and mas_render_lowres_pred, then mas_ms_naive_plbl: new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -465,6 +465,20 @@ int mas_ms_ensemble(const float* const* feats_q, const float* const* logits_q, c
  * mas_upsample_bilinear_fwd accepts); MAS_ERR_SHAPE otherwise.  C <= 255. */
 int mas_naive_plbl(const float* logits_q, int N, int C, int h, int w, int H, int W, const uint8_t* mask /* [N,H,W] or NULL */, float th,
                    uint8_t* labels /* [N,H,W] */, void* stream);
+
+/* Naive arg-max pseudo labels of the VOC generators (trainer/eval_save_cosplbl_naive_voc.py:54-67, single-scale, and
+ * trainer/eval_save_cosplbl_naive_voc_ms.py:55-92, multi-scale + flip) with their IoU counters, in one launch per picture.  Sources as
+ * mas_ms_ensemble's logits: n <= MAS_MS_MAX_SOURCES, logits_q[k] f32 [C,hq,wq], geometry[5k..5k+4] = (hq, wq, Hs, Ws, flip) with the
+ * same rules (MAS_ERR_SHAPE otherwise).  Per pixel and channel the source values of mas_ms_ensemble (bit for bit), summed in source
+ * order, m = sum / (float)n; labels u8 [H,W] = the first arg-max of m over the C channels (a NaN wins where it first appears, as
+ * torch.max), i.e. torch.max(mas_ms_ensemble's logit_out, 1)[1]; n = 1 with the geometry (hq, wq, H, W, 0) gives the arg-max of
+ * mas_upsample_bilinear_fwd's output.  counts (optional, int64 [3K+3] with K = num_classes, the layout of mas_iou_counts without the
+ * "undefined" triple): ADDED to, not reset -- MeanIoU(K, ignore_label)._after_step(labels, targets); targets int64 [H,W] required with
+ * counts, unused without.  1 <= C <= 255 (MAS_ERR_CLASSES); with counts C <= K <= MAS_MAX_CLASSES (MAS_ERR_CLASSES); MAS_ERR_RANGE when
+ * n is out of range or a stage-2 downsample needs more LDS than one tile may use.  Nothing is written when an argument is refused. */
+int mas_ms_naive_plbl(const float* const* logits_q, const int32_t* geometry /* [n,5] */, int n, int C, int H, int W,
+                      const int64_t* targets /* [H,W] or NULL */, int num_classes, int64_t ignore_label, uint8_t* labels /* [H,W] */,
+                      uint64_t* counts /* [3K+3] or NULL, accumulated */, void* stream);
 
 /* Colour images of label maps (--save_vis of the stage-2 generators, trainer/eval_save_cosplbl_prop.py:77-86; eval_naive_vis.py:70-83).
  * labels [N,H,W] of label_dtype MAS_ID_I64 or MAS_MAP_U8; palette u8 [P,3], 1 <= P <= 256; a label 255 takes the colour of `fill`

@@ -188,6 +188,20 @@ class DeviceMultiScaleFlip(DeviceTrainAugment):
         return out
 
 
+class DeviceIdentity(DeviceTrainAugment):
+    """``ExtToTensor`` + ``ExtNormalize`` at the picture's own size (name ``eval_spx_identity``, ``transform_voc.py:212-219``): the
+    augmentation kernel at factor 1.0 (every bilinear weight is 1, every nearest index its own), no pad, no crop, no flip -- the
+    picture as Pillow's to-tensor + normalise, the label and id maps unchanged."""
+
+    def __init__(self, pad_values=(255, 2048), **kw):
+        super().__init__(size=(1, 1), scale_range=(1.0, 1.0), pad_values=pad_values, **kw)
+
+    def __call__(self, img, maps=(), params=None):
+        H, W = int(img.shape[0]), int(img.shape[1])
+        self.size = (H, W)
+        return super().__call__(img, maps, params=dict(scale=1.0, th=H, tw=W, gap_y=0, gap_x=0, i=0, j=0, flip=False))
+
+
 def get_device_transform(args):
     """The reference's ``'rescale_769_multi'`` training transform (``transform.py:67-89``) for resident data."""
     return DeviceTrainAugment(size=(768, 768), scale_range=(0.5, 2.0), pad_values=[args.ignore_idx, args.nseg])

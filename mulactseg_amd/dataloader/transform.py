@@ -6,9 +6,10 @@ called as ``transform(picture u8 [H,W,3] cuda, [maps]) -> (image f32 [3,h,w], [m
 it pads (``ExtRandomCrop.pad_values``; the reference asserts the same count, ``ext_transforms.py:489``).
 
 Not offered (outside the production configurations): the unpadded 512x1024 crops (``orig_*``, ``rescale``), ``load_smaller_spx``
-(a third map), the colour-jitter variant.  ``eval_spx_identity_ms`` (VOC) returns a LIST of ten pictures (five scales, then the same
+(a third map), the colour-jitter variant.  ``eval_spx_identity`` (VOC) keeps the picture and its two maps at their own size;
+``eval_spx_identity_ms`` (VOC) returns a LIST of ten pictures (five scales, then the same
 flipped) and takes no map (``n_maps == 0``)."""
-from .device_transforms import DeviceMultiScaleFlip, DeviceResize, DeviceResizeFlip, DeviceResizeThreeMaps, DeviceTrainAugment
+from .device_transforms import DeviceIdentity, DeviceMultiScaleFlip, DeviceResize, DeviceResizeFlip, DeviceResizeThreeMaps, DeviceTrainAugment
 
 
 def _with_maps(t, n):
@@ -62,6 +63,8 @@ def get_train_transform_voc(args, transform):
         return _with_maps(DeviceTrainAugment(pad_values=[args.nseg], **crop), 1)
     if transform == 'eval_spx':
         return _with_maps(DeviceResize(513, center_crop=513, pad_values=[args.ignore_idx, args.nseg]), 2)
+    if transform == 'eval_spx_identity':                            # ToTensor + Normalize at the picture's own size, [label, superpixel]
+        return _with_maps(DeviceIdentity(pad_values=[args.ignore_idx, args.nseg]), 2)
     if transform == 'eval_spx_identity_ms':                         # TestTimeAugmentation: 5 scales x {no flip, flip}, picture only
         return _with_maps(DeviceMultiScaleFlip(), 0)
     raise NotImplementedError("train_transform %r is outside the hot path (see dataloader/transform.py)" % transform)

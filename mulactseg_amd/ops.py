@@ -1106,6 +1106,119 @@ def naive_pseudo_labels(logits_q, size, spmask, th=0.0):
     return out.long()
 
 
+def _meaniou_counts_aten(labels, targets, K, ignore_label, counts):
+    """``MeanIoU(K, ignore_label)._after_step`` of the reference (``utils/miou.py:23-38``) in torch, added to ``counts`` [3K+3]."""
+    keep = targets != ignore_label
+    o, t = labels[keep], targets[keep]
+    for i in range(K):
+        counts[i] += int(torch.sum(t == i))
+        counts[K + i] += int(torch.sum((t == i) & (o == t)))
+        counts[2 * K + i] += int(torch.sum(o == i))
+    return counts
+
+
+def _ms_naive_aten(logits_q, sizes, flips, out_size):
+    """The reference's lines (``eval_save_cosplbl_naive_voc_ms.py:59-87``) on the quarter-resolution logits: ``feat_forward``'s x4
+    upsampling (``upsample_bilinear`` on the GPU, ``F.interpolate`` on the CPU), the flip back, ``F.interpolate`` to the original size,
+    the sum in source order, ``/ n``, ``max(1)``."""
+    import torch.nn.functional as F
+    acc = None
+    for z, (Hs, Ws), fl in zip(logits_q, sizes, flips):
+        if z.is_cuda:
+            s = upsample_bilinear(z.contiguous(), (Hs, Ws))
+        else:
+            s = F.interpolate(z, size=(Hs, Ws), mode='bilinear', align_corners=False)
+        if fl:
+            s = s.flip(-1)
+        v = F.interpolate(s, size=tuple(out_size), mode='bilinear', align_corners=False)
+        acc = v if acc is None else acc + v
+    return (acc / len(logits_q)).max(dim=1)[1]
+
+
+def ms_naive_labels(logits_q, scaled_sizes, flips, out_size, targets=None, counts=None, num_classes=None, ignore_label=255):
+    """Naive arg-max pseudo labels int64 ``[1,H,W]`` of the VOC generators (``trainer/eval_save_cosplbl_naive_voc[_ms].py``) from n <= 16
+    sources, each the network's quarter-resolution logits ``[1,C,hq,wq]`` (``net(x, lowres=True)``) on the picture scaled to
+    ``scaled_sizes[k] = (Hs, Ws)`` and flipped horizontally when ``flips[k]``: upsampled x4 to the scaled size, flipped back, resized to
+    ``out_size = (H, W)``, averaged, the first arg-max over the channels -- ``torch.max(ms_ensemble(...)[1], 1)[1]`` bit for bit.
+    ``counts`` (int64 ``[3K+3]``, K = ``num_classes``, required with it): ``MeanIoU(K, ignore_label)._after_step`` of the labels against
+    ``targets`` (int64 ``[1,H,W]`` or ``[H,W]``) is ADDED to it.  One launch (``csrc/ms_naive.hip``): neither the scaled-size nor the
+    full-resolution logits exist.  CPU tensors, and ``MAS_MS_NAIVE=aten``, take the reference's ATen chain."""
+    n = len(logits_q)
+    if not 1 <= n <= _lib.MS_MAX_SOURCES:
+        raise ValueError("ms_naive_labels takes 1 .. %d sources, got %d" % (_lib.MS_MAX_SOURCES, n))
+    if len(scaled_sizes) != n or len(flips) != n:
+        raise ValueError("logits_q, scaled_sizes and flips must have one entry per source")
+    H, W = int(out_size[0]), int(out_size[1])
+    if H < 1 or W < 1:
+        raise ValueError("out_size must be non-empty, got %r" % (tuple(out_size),))
+    if counts is not None:
+        if num_classes is None:
+            raise ValueError("num_classes is required with counts")
+        if targets is None:
+            raise ValueError("targets are required with counts")
+    dev = logits_q[0].device
+    C = None
+    geom = []
+    for k in range(n):
+        z = logits_q[k]
+        if z.device != dev:
+            raise ValueError("all sources must live on one device")
+        if z.dtype != torch.float32:
+            raise TypeError("logits_q[%d] must be torch.float32, got %s" % (k, z.dtype))
+        if z.dim() != 4 or z.shape[0] != 1:
+            raise ValueError("source %d: logits must be [1,C,hq,wq], got %s" % (k, tuple(z.shape)))
+        if C is None:
+            C = int(z.shape[1])
+        if z.shape[1] != C:
+            raise ValueError("source %d: channel count differs from source 0" % k)
+        hq, wq = int(z.shape[2]), int(z.shape[3])
+        Hs, Ws = int(scaled_sizes[k][0]), int(scaled_sizes[k][1])
+        if Hs < 1 or Ws < 1:
+            raise ValueError("source %d: empty scaled size %dx%d" % (k, Hs, Ws))
+        if (hq, wq) != (quarter_size(Hs), quarter_size(Ws)):
+            raise ValueError("source %d: quarter-resolution logits %dx%d are not what the network emits for %dx%d (%dx%d)"
+                             % (k, hq, wq, Hs, Ws, quarter_size(Hs), quarter_size(Ws)))
+        geom += [hq, wq, Hs, Ws, 1 if flips[k] else 0]
+    if not 1 <= C <= 255:
+        raise ValueError("ms_naive_labels takes 1 .. 255 channels, got %d" % C)
+    K = None if num_classes is None else int(num_classes)
+    if counts is not None and not C <= K <= _lib.MAX_CLASSES:
+        raise ValueError("num_classes %d must be within [%d, %d] (the channels .. MAX_CLASSES)" % (K, C, _lib.MAX_CLASSES))
+    if targets is not None:
+        if targets.dtype != torch.int64:
+            raise TypeError("targets must be torch.int64, got %s" % targets.dtype)
+        if tuple(targets.shape[-2:]) != (H, W) or targets.numel() != H * W:
+            raise ValueError("targets %s do not match the picture %dx%d" % (tuple(targets.shape), H, W))
+        if targets.device != dev:
+            raise ValueError("targets must live on the logits' device")
+    if counts is not None:
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (3 * K + 3,) or counts.device != dev:
+            raise ValueError("counts must be int64 [3K+3] = [%d] on the logits' device" % (3 * K + 3))
+    sizes = [(int(s[0]), int(s[1])) for s in scaled_sizes]
+    if not logits_q[0].is_cuda or os.environ.get("MAS_MS_NAIVE", "fused") == "aten":
+        labels = _ms_naive_aten(logits_q, sizes, [bool(f) for f in flips], (H, W))
+        if counts is not None:
+            t = targets.reshape(1, H, W)
+            if labels.is_cuda:
+                iou_counts(labels.contiguous(), None, t.contiguous(), K, int(ignore_label), counts)
+            else:
+                _meaniou_counts_aten(labels, t, K, int(ignore_label), counts)
+        return labels
+    for k in range(n):
+        _need(logits_q[k], "logits_q[%d]" % k, torch.float32)
+    if counts is not None:
+        _need(counts, "counts", torch.int64)
+        _need(targets, "targets", torch.int64)
+    out = torch.empty((1, H, W), dtype=torch.uint8, device=dev)
+    lp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in logits_q])
+    g = (ctypes.c_int32 * (5 * n))(*geom)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mas_ms_naive_plbl(lp, g, n, C, H, W, targets.data_ptr() if counts is not None else None,
+                                                 K if counts is not None else 0, int(ignore_label), out.data_ptr(),
+                                                 counts.data_ptr() if counts is not None else None, _stream(out)), "mas_ms_naive_plbl")
+    return out.long()
+
+
 # ------------------------------------------------------------------------------------------------
 # BatchNorm2d + ReLU + residual add, fused (csrc/bn.hip)
 # ------------------------------------------------------------------------------------------------

@@ -70,10 +70,7 @@ class ActiveTrainer(eval_within_multihot.ActiveTrainer):
         jobs, errors = queue.Queue(maxsize=2 * workers), []
 
         def one(batch):
-            images, labels, superpixels, spmasks, targets = self._batch(batch)
-            plbl = self.pseudo_labels(images, labels, targets, spmasks, superpixels)
-            meter._after_step({'outputs': plbl, 'targets': labels})
-            self.after_batch(batch, plbl)               # (ends with the label map on the host: this stream has drained)
+            self.generate_batch(batch, meter)           # (ends with the label map on the host: this stream has drained)
 
         def work(stream):
             torch.cuda.set_device(dev)

@@ -58,13 +58,17 @@ class ActiveTrainer(BaseTrainer):
         self.net.eval()
         with torch.no_grad():
             for _ in range(len(loader)):
-                batch = next(loader)
-                images, labels, superpixels, spmasks, targets = self._batch(batch)
-                plbl = self.pseudo_labels(images, labels, targets, spmasks, superpixels)
-                meter._after_step({'outputs': plbl, 'targets': labels})
-                self.after_batch(batch, plbl)
+                self.generate_batch(next(loader), meter)
         meter.all_reduce(self.device)
         return self.report(meter, prefix)
+
+    def generate_batch(self, batch, meter):
+        """One batch of the loop: pseudo labels, the IoU counters, ``after_batch``.  Generators whose kernel counts by itself, or whose
+        batches carry no ``images``, replace it."""
+        images, labels, superpixels, spmasks, targets = self._batch(batch)
+        plbl = self.pseudo_labels(images, labels, targets, spmasks, superpixels)
+        meter._after_step({'outputs': plbl, 'targets': labels})
+        self.after_batch(batch, plbl)
 
     def report(self, meter, prefix):
         """Print the IoU table of the generated labels (mIoU, then per class) and return (mIoU, table)."""
