@@ -35,6 +35,24 @@ def _need(t, name, dtype=None):
     return t
 
 
+def _opt(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _stream_key(dev):
+    return (dev, torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _stream_scratch(table, dev, alloc, n=0):
+    """``table``'s entry for the current stream of ``dev``, from ``alloc()`` when there is none yet or it holds fewer than ``n``
+    elements.  The launches of one stream run in order, so they can share scratch memory; two streams never do."""
+    key = _stream_key(dev)
+    ent = table.get(key)
+    if ent is None or (n and ent.numel() < n):
+        ent = table[key] = alloc()
+    return ent
+
+
 def _id_code(spx):
     try:
         return _ID_CODES[spx.dtype]
@@ -119,55 +137,105 @@ def _mask_u8(mask):
     return _need(mask, "spmasks", torch.uint8)
 
 
+def _partial_loss_fwd(z, size, spx, mask, bits, invT, flags, reduce_acc, weights):
+    """The step-by-step forward on ``z`` [N,C,H,W] (``size`` None) or on the bilinear upsampling of ``z`` [N,C,h,w] to ``size`` =
+    (H, W), which is never materialised: scan, group finalize, ``reduce_acc``, loss values."""
+    _need(z, "inputs", torch.float32)
+    _need(spx, "superpixels")
+    mask = _mask_u8(mask)
+    _need(bits, "bits", torch.int32)
+    N, C, h, w = z.shape
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    S = bits.shape[1]
+    if tuple(spx.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W) or bits.shape[0] != N:
+        raise ValueError("shape mismatch between inputs %s%s, superpixels %s, spmasks %s, targets %s"
+                         % (tuple(z.shape), "" if size is None else " at size %s" % ((H, W),), tuple(spx.shape), tuple(mask.shape),
+                            tuple(bits.shape)))
+    dev = z.device
+    if flags & _lib.LOSS_GROUP:             # accumulators and the arg-pixel table from ONE zero-filled allocation (one memset)
+        buf = torch.zeros(_lib.ACC_WORDS + N * S * C, dtype=torch.int64, device=dev)
+        acc, gmax = buf[:_lib.ACC_WORDS], buf[_lib.ACC_WORDS:].view(N, S, C)
+    else:
+        acc, gmax = torch.zeros(_lib.ACC_WORDS, dtype=torch.int64, device=dev), None
+    losses = torch.empty(3 if weights is None else 4, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = _stream(z)
+        if size is None:
+            _lib.check(lib.mas_partial_loss_fwd(z.data_ptr(), spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
+                                                N, C, H, W, S, invT, flags, _opt(gmax), acc.data_ptr(), st), "mas_partial_loss_fwd")
+        else:
+            _lib.check(lib.mas_partial_loss_fwd_lowres(z.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
+                                                       N, C, H, W, S, invT, flags, _opt(gmax), acc.data_ptr(), st),
+                       "mas_partial_loss_fwd_lowres")
+        if gmax is not None:
+            _lib.check(lib.mas_group_finalize(gmax.data_ptr(), gmax.numel(), acc.data_ptr(), st), "mas_group_finalize")
+        if reduce_acc is not None:
+            reduce_acc(acc)
+        if weights is None:
+            _lib.check(lib.mas_loss_values(acc.data_ptr(), flags, losses.data_ptr(), st), "mas_loss_values")
+        else:
+            _need(weights, "weights", torch.float32)
+            _lib.check(lib.mas_loss_values_weighted(acc.data_ptr(), flags, weights.data_ptr(), losses.data_ptr(), st), "mas_loss_values_weighted")
+    return losses, acc, gmax
+
+
+def _partial_loss_bwd(z, size, spx, mask, bits, gmax, acc, grad_out, invT, flags, want_fix, weights):
+    """The step-by-step backward of ``_partial_loss_fwd``: the gradient with respect to ``z``.  At low resolution (``size`` given) it
+    is summed in int64 fixed point and rounded to f32 by a pass of its own."""
+    mask = _mask_u8(mask)
+    _need(grad_out, "grad_out", torch.float32)
+    N, C, h, w = z.shape
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    S = bits.shape[1]
+    dev = z.device
+    scale = torch.empty(3, dtype=torch.float32, device=dev)
+    fix = None if size is None else torch.zeros((N, C, h, w), dtype=torch.int64, device=dev)
+    dz = torch.empty_like(z)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = _stream(z)
+        if weights is None:
+            _lib.check(lib.mas_loss_scales(acc.data_ptr(), grad_out.data_ptr(), flags, scale.data_ptr(), st), "mas_loss_scales")
+        else:               # grad_out is dL/d(total) [1]; the chain rule through the weighted sum happens in the kernel
+            _lib.check(lib.mas_loss_scales_weighted(acc.data_ptr(), grad_out.data_ptr(), weights.data_ptr(), flags, scale.data_ptr(), st),
+                       "mas_loss_scales_weighted")
+        if size is None:
+            _lib.check(lib.mas_partial_loss_bwd(z.data_ptr(), spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), _opt(gmax),
+                                                scale.data_ptr(), N, C, H, W, S, invT, flags, dz.data_ptr(), st), "mas_partial_loss_bwd")
+        else:
+            _lib.check(lib.mas_partial_loss_bwd_lowres(z.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
+                                                       _opt(gmax), scale.data_ptr(), N, C, H, W, S, invT, flags, fix.data_ptr(), st),
+                       "mas_partial_loss_bwd_lowres")
+            _lib.check(lib.mas_fix_to_float(fix.data_ptr(), fix.numel(), _lib.GRAD_FRAC, dz.data_ptr(), st), "mas_fix_to_float")
+    return (dz, fix) if want_fix else dz
+
+
 def partial_loss_fwd(z, spx, mask, bits, invT, flags, reduce_acc=None):
     """Forward scan + group finalize + loss values.  Returns (losses f32[3], acc i64[8], gmax i64[N,S,C])
     -- all on the device, no host synchronisation.  ``reduce_acc(acc)`` (optional) runs between the scans
     and the division: data-parallel training all-reduces the integer sums / counts there so that the
     normalisers 1 + n are global over the batch, as on one GPU."""
-    _need(z, "inputs", torch.float32)
-    _need(spx, "superpixels")
-    mask = _mask_u8(mask)
-    _need(bits, "bits", torch.int32)
-    N, C, H, W = z.shape
-    S = bits.shape[1]
-    if tuple(spx.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W) or bits.shape[0] != N:
-        raise ValueError("shape mismatch between inputs %s, superpixels %s, spmasks %s, targets %s"
-                         % (tuple(z.shape), tuple(spx.shape), tuple(mask.shape), tuple(bits.shape)))
-    dev = z.device
-    acc = torch.zeros(_lib.ACC_WORDS, dtype=torch.int64, device=dev)
-    gmax = torch.zeros((N, S, C), dtype=torch.int64, device=dev) if flags & _lib.LOSS_GROUP else None
-    losses = torch.empty(3, dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = _stream(z)
-        _lib.check(lib.mas_partial_loss_fwd(z.data_ptr(), spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
-                                            N, C, H, W, S, invT, flags, gmax.data_ptr() if gmax is not None else None,
-                                            acc.data_ptr(), st), "mas_partial_loss_fwd")
-        if gmax is not None:
-            _lib.check(lib.mas_group_finalize(gmax.data_ptr(), gmax.numel(), acc.data_ptr(), st), "mas_group_finalize")
-        if reduce_acc is not None:
-            reduce_acc(acc)
-        _lib.check(lib.mas_loss_values(acc.data_ptr(), flags, losses.data_ptr(), st), "mas_loss_values")
-    return losses, acc, gmax
+    return _partial_loss_fwd(z, None, spx, mask, bits, invT, flags, reduce_acc, None)
 
 
 def partial_loss_bwd(z, spx, mask, bits, gmax, acc, grad_out, invT, flags):
     """Backward scan: dz [N,C,H,W] for upstream gradients ``grad_out`` f32[3] (device tensor)."""
-    mask = _mask_u8(mask)
-    _need(grad_out, "grad_out", torch.float32)
-    N, C, H, W = z.shape
-    S = bits.shape[1]
-    dev = z.device
-    scale = torch.empty(3, dtype=torch.float32, device=dev)
-    dz = torch.empty_like(z)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = _stream(z)
-        _lib.check(lib.mas_loss_scales(acc.data_ptr(), grad_out.data_ptr(), flags, scale.data_ptr(), st), "mas_loss_scales")
-        _lib.check(lib.mas_partial_loss_bwd(z.data_ptr(), spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
-                                            gmax.data_ptr() if gmax is not None else None, scale.data_ptr(),
-                                            N, C, H, W, S, invT, flags, dz.data_ptr(), st), "mas_partial_loss_bwd")
-    return dz
+    return _partial_loss_bwd(z, None, spx, mask, bits, gmax, acc, grad_out, invT, flags, False, None)
+
+
+def partial_loss_fwd_lowres(zq, size, spx, mask, bits, invT, flags, reduce_acc=None, weights=None):
+    """As ``partial_loss_fwd`` for the logits ``F.interpolate(zq, size, 'bilinear', align_corners=False)`` without
+    materialising them: ``zq`` [N,C,h,w] quarter-resolution logits, ``size`` = (H, W) of ids / masks.  ``weights`` (f32 [3]
+    device tensor: w_ce, w_mc, w_group): ``losses`` gets a fourth entry, the weighted objective (w_ce*ce + w_mc*mc) + w_group*group."""
+    return _partial_loss_fwd(zq, size, spx, mask, bits, invT, flags, reduce_acc, weights)
+
+
+def partial_loss_bwd_lowres(zq, size, spx, mask, bits, gmax, acc, grad_out, invT, flags, want_fix=False, weights=None):
+    """Gradient of the losses with respect to the quarter-resolution logits: dzq [N,C,h,w] f32 (and the int64 fixed-point
+    sums it was rounded from when ``want_fix``).  With ``weights`` [3], ``grad_out`` is the upstream gradient of the weighted
+    objective, a one-element tensor."""
+    return _partial_loss_bwd(zq, size, spx, mask, bits, gmax, acc, grad_out, invT, flags, want_fix, weights)
 
 
 class LossState:
@@ -247,73 +315,6 @@ def partial_loss_bwd_fused(z, size, spx, mask, state, grad, invT, weights=None, 
 # ------------------------------------------------------------------------------------------------
 # K4: ordering + budgeted selection walk
 # ------------------------------------------------------------------------------------------------
-def partial_loss_fwd_lowres(zq, size, spx, mask, bits, invT, flags, reduce_acc=None, weights=None):
-    """As ``partial_loss_fwd`` for the logits ``F.interpolate(zq, size, 'bilinear', align_corners=False)`` without
-    materialising them: ``zq`` [N,C,h,w] quarter-resolution logits, ``size`` = (H, W) of ids / masks.  ``weights`` (f32 [3]
-    device tensor: w_ce, w_mc, w_group): ``losses`` gets a fourth entry, the weighted objective (w_ce*ce + w_mc*mc) + w_group*group."""
-    _need(zq, "inputs", torch.float32)
-    _need(spx, "superpixels")
-    mask = _mask_u8(mask)
-    _need(bits, "bits", torch.int32)
-    N, C, h, w = zq.shape
-    H, W = int(size[0]), int(size[1])
-    S = bits.shape[1]
-    if tuple(spx.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W) or bits.shape[0] != N:
-        raise ValueError("shape mismatch between inputs %s at size %s, superpixels %s, spmasks %s, targets %s"
-                         % (tuple(zq.shape), (H, W), tuple(spx.shape), tuple(mask.shape), tuple(bits.shape)))
-    dev = zq.device
-    if flags & _lib.LOSS_GROUP:             # accumulators and the arg-pixel table from ONE zero-filled allocation (one memset)
-        buf = torch.zeros(_lib.ACC_WORDS + N * S * C, dtype=torch.int64, device=dev)
-        acc, gmax = buf[:_lib.ACC_WORDS], buf[_lib.ACC_WORDS:].view(N, S, C)
-    else:
-        acc, gmax = torch.zeros(_lib.ACC_WORDS, dtype=torch.int64, device=dev), None
-    losses = torch.empty(3 if weights is None else 4, dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = _stream(zq)
-        _lib.check(lib.mas_partial_loss_fwd_lowres(zq.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
-                                                   N, C, H, W, S, invT, flags, gmax.data_ptr() if gmax is not None else None,
-                                                   acc.data_ptr(), st), "mas_partial_loss_fwd_lowres")
-        if gmax is not None:
-            _lib.check(lib.mas_group_finalize(gmax.data_ptr(), gmax.numel(), acc.data_ptr(), st), "mas_group_finalize")
-        if reduce_acc is not None:
-            reduce_acc(acc)
-        if weights is None:
-            _lib.check(lib.mas_loss_values(acc.data_ptr(), flags, losses.data_ptr(), st), "mas_loss_values")
-        else:
-            _need(weights, "weights", torch.float32)
-            _lib.check(lib.mas_loss_values_weighted(acc.data_ptr(), flags, weights.data_ptr(), losses.data_ptr(), st), "mas_loss_values_weighted")
-    return losses, acc, gmax
-
-
-def partial_loss_bwd_lowres(zq, size, spx, mask, bits, gmax, acc, grad_out, invT, flags, want_fix=False, weights=None):
-    """Gradient of the losses with respect to the quarter-resolution logits: dzq [N,C,h,w] f32 (and the int64 fixed-point
-    sums it was rounded from when ``want_fix``).  With ``weights`` [3], ``grad_out`` is the upstream gradient of the weighted
-    objective, a one-element tensor."""
-    mask = _mask_u8(mask)
-    _need(grad_out, "grad_out", torch.float32)
-    N, C, h, w = zq.shape
-    H, W = int(size[0]), int(size[1])
-    S = bits.shape[1]
-    dev = zq.device
-    scale = torch.empty(3, dtype=torch.float32, device=dev)
-    fix = torch.zeros((N, C, h, w), dtype=torch.int64, device=dev)
-    dzq = torch.empty_like(zq)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = _stream(zq)
-        if weights is None:
-            _lib.check(lib.mas_loss_scales(acc.data_ptr(), grad_out.data_ptr(), flags, scale.data_ptr(), st), "mas_loss_scales")
-        else:               # grad_out is dL/d(total) [1]; the chain rule through the weighted sum happens in the kernel
-            _lib.check(lib.mas_loss_scales_weighted(acc.data_ptr(), grad_out.data_ptr(), weights.data_ptr(), flags, scale.data_ptr(), st),
-                       "mas_loss_scales_weighted")
-        _lib.check(lib.mas_partial_loss_bwd_lowres(zq.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
-                                                   gmax.data_ptr() if gmax is not None else None, scale.data_ptr(), N, C, H, W, S,
-                                                   invT, flags, fix.data_ptr(), st), "mas_partial_loss_bwd_lowres")
-        _lib.check(lib.mas_fix_to_float(fix.data_ptr(), fix.numel(), _lib.GRAD_FRAC, dzq.data_ptr(), st), "mas_fix_to_float")
-    return (dzq, fix) if want_fix else dzq
-
-
 def path_ranks(paths):
     """Rank of every image's joined path string in ascending (Python ``str``) order -- the tie-break
     the reference's tuple sort applies after the score (``active_selection/base.py:37``).
@@ -1222,10 +1223,6 @@ def ms_naive_labels(logits_q, scaled_sizes, flips, out_size, targets=None, count
 # ------------------------------------------------------------------------------------------------
 # BatchNorm2d + ReLU + residual add, fused (csrc/bn.hip)
 # ------------------------------------------------------------------------------------------------
-def _opt(t):
-    return t.data_ptr() if t is not None else None
-
-
 _BN_COUNTERS = {}
 
 
@@ -1236,11 +1233,7 @@ def _bn_counters(dev, C):
     tail of every workgroup costs what the 115 five-microsecond launches did.  Kept for the A/B and its bit-identity test.)"""
     if os.environ.get("MAS_BN_LASTBLOCK", "off") != "on":
         return None
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    buf = _BN_COUNTERS.get(key)
-    if buf is None or buf.numel() < C:
-        buf = _BN_COUNTERS[key] = torch.zeros(max(4096, C), dtype=torch.int32, device=dev)
-    return buf
+    return _stream_scratch(_BN_COUNTERS, dev, lambda: torch.zeros(max(4096, C), dtype=torch.int32, device=dev), C)
 
 
 class _BNActTrain(torch.autograd.Function):
@@ -1275,7 +1268,7 @@ class _BNActTrain(torch.autograd.Function):
                                                     _stream(x)),
                            "mas_bn_act_train_fwd")
         # the kernel updated the running statistics through raw pointers: bump their version counters as an in-place
-        # torch op would, so caches keyed on (data_ptr, _version) -- _conv1x1_constants -- see the change
+        # torch op would, so caches keyed on (data_ptr, _version) -- _bn_fold -- see the change
         for buf in (running_mean, running_var, num_batches_tracked):
             if buf is not None:
                 torch.autograd.graph.increment_version(buf)
@@ -1481,22 +1474,11 @@ def conv1x1_bn_act_supported(conv, bn, x):
 
 
 def _conv1x1_constants(conv, bn):
-    """(transposed weight [K,M], scale [M], shift [M]) cached on the conv module until a parameter / statistic changes."""
-    tensors = (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-    key = _versions(tensors)
-    cache = getattr(conv, '_mas_conv1x1_cache', None)
-    if cache is None or cache[0] != key:
+    """(transposed weight [K,M], scale [M], shift [M]): the weight cached on the conv module until it changes, the rest from _bn_fold."""
+    def transposed():
         with torch.no_grad():
-            M, K = conv.out_channels, conv.in_channels
-            w_t = conv.weight.reshape(M, K).t().contiguous()
-            inv = torch.rsqrt(bn.running_var.double() + bn.eps)
-            g = bn.weight.double() if bn.weight is not None else torch.ones_like(inv)
-            b = bn.bias.double() if bn.bias is not None else torch.zeros_like(inv)
-            scale = (g * inv)
-            shift = (b - bn.running_mean.double() * scale)
-            cache = (key, w_t, scale.float().contiguous(), shift.float().contiguous())
-        conv._mas_conv1x1_cache = cache
-    return cache[1:]
+            return conv.weight.reshape(conv.out_channels, conv.in_channels).t().contiguous()
+    return (_cached(conv, '_mas_conv1x1_cache', (conv.weight,), transposed),) + _bn_fold(bn)
 
 
 def conv1x1_bn_act(conv, bn, x, relu=True, residual=None):
@@ -1505,8 +1487,7 @@ def conv1x1_bn_act(conv, bn, x, relu=True, residual=None):
     N, K, H, W = x.shape
     M = conv.out_channels
     w_t, scale, shift = _conv1x1_constants(conv, bn)
-    res = residual.contiguous() if residual is not None else None
-    y = torch.empty((N, M, H, W), dtype=torch.float32, device=x.device)
+    _, _, res, y = _fused_epilogue(None, residual, (N, M, H, W), x.device, strict=False)     # (the fold came with the weight)
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().mas_conv1x1_fwd(x.data_ptr(), w_t.data_ptr(), N, K, M, H * W, scale.data_ptr(), shift.data_ptr(), _opt(res),
                                                int(relu), y.data_ptr(), _stream(x)), "mas_conv1x1_fwd")
@@ -1516,21 +1497,34 @@ def conv1x1_bn_act(conv, bn, x, relu=True, residual=None):
 # ------------------------------------------------------------------------------------------------
 # dense convolutions on the f32 matrix cores (csrc/conv_mfma.hip)
 # ------------------------------------------------------------------------------------------------
+def _conv_geometry(conv, x):
+    """(kernel, stride, dilation, padding) of a dense square convolution this package can look at -- f32 NCHW input on the GPU with
+    the convolution's input channels, no groups, no bias, the same kernel size / stride / dilation / padding along both axes -- or
+    None."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.groups == 1 and conv.bias is None):
+        return None
+    k, s, d, pd = conv.kernel_size, conv.stride, conv.dilation, conv.padding
+    if k[0] != k[1] or s[0] != s[1] or d[0] != d[1] or pd[0] != pd[1] or x.shape[1] != conv.in_channels:
+        return None
+    return k[0], s[0], d[0], pd[0]
+
+
+def _is_1x1_or_3x3(k, s, d, pd, dilations):
+    """The network's two layer forms at stride 1 / 2: 3x3 with padding = dilation in ``dilations`` (undilated at stride 2), or plain 1x1."""
+    if s not in (1, 2):
+        return False
+    if k == 3:
+        return pd == d and d in dilations and (s == 1 or d == 1)
+    return k == 1 and pd == 0 and d == 1
+
+
 def conv_mfma_supported(conv, x):
     """Shapes the implicit-GEMM MFMA kernel takes: 1x1 / 3x3, stride 1 or 2 (3x3 stride 2 only undilated), padding =
     dilation for 3x3, no groups, no bias, Cin % 8 (3x3) / % 16 (1x1) == 0 (any Cout: padded to 64 inside), fp32 NCHW on the GPU."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.groups == 1 and conv.bias is None):
+    geom = _conv_geometry(conv, x)
+    if geom is None or not _is_1x1_or_3x3(*geom, dilations=(1, 2)):
         return False
-    k, s, d, pd = conv.kernel_size, conv.stride, conv.dilation, conv.padding
-    if k[0] != k[1] or s[0] != s[1] or d[0] != d[1] or pd[0] != pd[1] or k[0] not in (1, 3) or s[0] not in (1, 2):
-        return False
-    if k[0] == 3 and (pd[0] != d[0] or d[0] > 2 or (s[0] == 2 and d[0] != 1)):
-        return False
-    if k[0] == 1 and (pd[0] != 0 or d[0] != 1):
-        return False
-    if x.shape[1] != conv.in_channels:
-        return False
-    return _lib.load().mas_conv_chunk(k[0], conv.in_channels) > 0 and conv.in_channels * x.shape[2] * x.shape[3] < 2 ** 31
+    return _lib.load().mas_conv_chunk(geom[0], conv.in_channels) > 0 and conv.in_channels * x.shape[2] * x.shape[3] < 2 ** 31
 
 
 # Parameter epoch: advanced after EVERY optimizer step of the process.  The version counter of a tensor is not enough to key a
@@ -1567,13 +1561,26 @@ def _versions(tensors):
     return (_PARAM_EPOCH[0],) + tuple((t.data_ptr(), t._version) for t in tensors if t is not None)
 
 
+def _cached(module, attr, tensors, build):
+    """``build()``, kept in ``module.<attr>`` until one of ``tensors`` (parameters, running statistics) changes: its address, its
+    version counter, or the process's parameter epoch."""
+    key = _versions(tensors)
+    cache = getattr(module, attr, None)
+    if cache is None or cache[0] != key:
+        cache = (key, build())
+        setattr(module, attr, cache)
+    return cache[1]
+
+
+def _bn_tensors(bn):
+    return (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+
+
 def _conv_packed_weight(conv):
     """The weight as mas_conv_fwd reads it -- [Cin/CK][KC/8][2][Cout][4]: k-step kk = tap * (CK/2) + cp pairs the input
     channels c = 2 cp + h (h = lane half of the MFMA), four consecutive k-steps of one (half, output channel) are
     adjacent -- cached on the module until the parameter changes."""
-    key = _versions((conv.weight,))
-    cache = getattr(conv, '_mas_conv_pack', None)
-    if cache is None or cache[0] != key:
+    def pack():
         with torch.no_grad():
             M, K, kh, kw = conv.weight.shape
             ck = _lib.load().mas_conv_chunk(kh, K)
@@ -1584,25 +1591,37 @@ def _conv_packed_weight(conv):
                 M = w.shape[0]
             w = w.reshape(M, K // ck, ck // 2, 2, taps)                             # [m, chunk, cp, h, tap]
             w = w.permute(1, 4, 2, 3, 0).reshape(K // ck, taps * ck // 2, 2, M)     # [chunk, kk = tap * ck/2 + cp, h, m]
-            w = w.reshape(K // ck, taps * ck // 8, 4, 2, M).permute(0, 1, 3, 4, 2).contiguous()     # [chunk, q, h, m, j]
-        cache = conv._mas_conv_pack = (key, w)
-    return cache[1]
+            return w.reshape(K // ck, taps * ck // 8, 4, 2, M).permute(0, 1, 3, 4, 2).contiguous()      # [chunk, q, h, m, j]
+    return _cached(conv, '_mas_conv_pack', (conv.weight,), pack)
 
 
 def _bn_fold(bn):
     """(scale, shift) f32 [C] of an inference BatchNorm, cached on the module until a parameter or running statistic
     changes (the training kernels bump the buffers' version counters, _BNActTrain.forward)."""
-    key = _versions((bn.weight, bn.bias, bn.running_mean, bn.running_var))
-    cache = getattr(bn, '_mas_fold', None)
-    if cache is None or cache[0] != key:
+    def fold():
         with torch.no_grad():
             inv = torch.rsqrt(bn.running_var.double() + bn.eps)
             g = bn.weight.double() if bn.weight is not None else torch.ones_like(inv)
             b = bn.bias.double() if bn.bias is not None else torch.zeros_like(inv)
             scale = g * inv
             shift = b - bn.running_mean.double() * scale
-        cache = bn._mas_fold = (key, scale.float().contiguous(), shift.float().contiguous())
-    return cache[1], cache[2]
+        return scale.float().contiguous(), shift.float().contiguous()
+    return _cached(bn, '_mas_fold', _bn_tensors(bn), fold)
+
+
+def _fused_epilogue(bn, residual, shape, dev, strict=True):
+    """What the fused inference convolutions with output ``shape`` = (N, M, Ho, Wo) on ``dev`` share: (scale, shift, residual, y) --
+    the folded BatchNorm (None, None without one), the residual made contiguous, the empty output.  ``strict``: a BatchNorm of
+    another width or a residual that is not f32 ``shape`` on ``dev`` is a ValueError (the wrappers that always checked)."""
+    if strict and bn is not None and bn.num_features != shape[1]:
+        raise ValueError("BatchNorm has %d features, the convolution %d output channels" % (bn.num_features, shape[1]))
+    scale, shift = _bn_fold(bn) if bn is not None else (None, None)
+    if residual is not None:
+        if strict and (tuple(residual.shape) != shape or residual.dtype != torch.float32 or residual.device != dev):
+            raise ValueError("residual must be float32 %s on %s, got %s %s on %s"
+                             % (shape, dev, residual.dtype, tuple(residual.shape), residual.device))
+        residual = residual.contiguous()
+    return scale, shift, residual, torch.empty(shape, dtype=torch.float32, device=dev)
 
 
 def conv_mfma(conv, x, bn=None, relu=False, residual=None):
@@ -1612,15 +1631,7 @@ def conv_mfma(conv, x, bn=None, relu=False, residual=None):
     M = conv.out_channels
     ks, s, d = conv.kernel_size[0], conv.stride[0], conv.dilation[0]
     wt = _conv_packed_weight(conv)
-    if bn is not None and bn.num_features != M:
-        raise ValueError("BatchNorm has %d features, the convolution %d output channels" % (bn.num_features, M))
-    scale, shift = _bn_fold(bn) if bn is not None else (None, None)
-    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
-    if residual is not None and (tuple(residual.shape) != (N, M, Ho, Wo) or residual.dtype != torch.float32 or residual.device != x.device):
-        raise ValueError("residual must be float32 %s on %s, got %s %s on %s"
-                         % ((N, M, Ho, Wo), x.device, residual.dtype, tuple(residual.shape), residual.device))
-    res = residual.contiguous() if residual is not None else None
-    y = torch.empty((N, M, Ho, Wo), dtype=torch.float32, device=x.device)
+    scale, shift, res, y = _fused_epilogue(bn, residual, (N, M, (H - 1) // s + 1, (W - 1) // s + 1), x.device)
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().mas_conv_fwd(x.data_ptr(), wt.data_ptr(), N, K, H, W, M, ks, s, d, _opt(scale), _opt(shift), _opt(res),
                                             int(relu), y.data_ptr(), _stream(x)), "mas_conv_fwd")
@@ -1633,29 +1644,37 @@ def conv_mfma(conv, x, bn=None, relu=False, residual=None):
 BX_ROLE_S2 = 2          # mas_conv_bx_pack role: the forward image of a 3x3 stride-2 convolution (nine shifted 1x1 stride-2 products)
 
 
+def _train_bx():
+    """MAS_TRAIN_BX as (bf16 allowed, round-4 rule): auto (default) -> (True, False): every product of a training step the split-bf16
+    kernels take; r04 -> (True, True): only what round 4 gave them, for A/B runs; off -> (False, False)."""
+    mode = os.environ.get("MAS_TRAIN_BX", "auto")
+    return mode != "off", mode == "r04"
+
+
+def _bx_s2k3():
+    """MAS_BX_S2K3 (default on): may the 3x3 stride-2 convolutions run on the split-bf16 kernel?"""
+    return os.environ.get("MAS_BX_S2K3", "on") != "off"
+
+
 def conv_bx_supported(conv, x):
     """Shapes mas_conv_bx_fwd takes: 1x1 at stride 1 (any plane) / 2 (H even, W % 8 == 0), 3x3 stride 1 with dilation 1 / 2
     (padding = dilation) on planes at least 32 wide, 3x3 stride 2 (H even, W % 8 == 0, input channels a multiple of 32); any other
     channel counts; no groups, no bias."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.groups == 1 and conv.bias is None):
+    geom = _conv_geometry(conv, x)
+    if geom is None:
         return False
-    if conv.stride[0] == 2 and x.data_ptr() % 16:
+    k, s, d, pd = geom
+    if pd != (d if k == 3 else 0) or (s == 2 and x.data_ptr() % 16):
         return False
-    if conv.stride[0] == 2 and conv.kernel_size[0] == 3 and os.environ.get("MAS_BX_S2K3", "on") == "off":      # (A/B: the f32 pipe)
+    if s == 2 and k == 3 and not _bx_s2k3():                    # (A/B: the f32 pipe)
         return False
-    k, s, d, pd = conv.kernel_size, conv.stride, conv.dilation, conv.padding
-    if k[0] != k[1] or s[0] != s[1] or d[0] != d[1] or pd[0] != pd[1] or pd[0] != (d[0] if k[0] == 3 else 0) or x.shape[1] != conv.in_channels:
-        return False
-    return bool(_lib.load().mas_conv_bx_supported(conv.kernel_size[0], conv.stride[0], conv.dilation[0], conv.in_channels,
-                                                  conv.out_channels, x.shape[2], x.shape[3]))
+    return bool(_lib.load().mas_conv_bx_supported(k, s, d, conv.in_channels, conv.out_channels, x.shape[2], x.shape[3]))
 
 
 def _conv_bx_weight(conv):
     """The split weight image of mas_conv_bx_pack, cached on the module until the parameter changes (inference: once per
     checkpoint load)."""
-    key = _versions((conv.weight,))
-    cache = getattr(conv, '_mas_conv_bx_pack', None)
-    if cache is None or cache[0] != key:
+    def pack():
         lib = _lib.load()
         w = conv.weight.detach().contiguous()
         M, K, kh, _ = w.shape
@@ -1666,19 +1685,17 @@ def _conv_bx_weight(conv):
         wp = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
         with torch.cuda.device(w.device):
             _lib.check(lib.mas_conv_bx_pack(w.data_ptr(), None, M, K, kh, role, wp.data_ptr(), _stream(w)), "mas_conv_bx_pack")
-        cache = conv._mas_conv_bx_pack = (key, wp)
-    return cache[1]
+        return wp
+    return _cached(conv, '_mas_conv_bx_pack', (conv.weight,), pack)
 
 
 def _conv_bx_folded(conv, bn):
     """(weight image with the inference BatchNorm's scale folded into its rows, shift [Cout]) for mas_conv_bx_fwd_dual, cached on the
     convolution until a parameter or running statistic changes."""
-    key = _versions((conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var))
-    cache = getattr(conv, '_mas_conv_bx_folded', None)
-    if cache is None or cache[0] != key:
+    def fold():
         scale, shift = _bn_fold(bn)
-        cache = conv._mas_conv_bx_folded = (key, conv_bx_pack(conv.weight.detach(), 0, row_scale=scale), shift)
-    return cache[1], cache[2]
+        return conv_bx_pack(conv.weight.detach(), 0, row_scale=scale), shift
+    return _cached(conv, '_mas_conv_bx_folded', (conv.weight,) + _bn_tensors(bn), fold)
 
 
 def conv_bx_dual_supported(conv_a, xa, conv_b, xb):
@@ -1697,13 +1714,11 @@ def conv_bx_dual(conv_a, bn_a, xa, conv_b, bn_b, xb, relu=True):
     xa, xb = xa.contiguous(), xb.contiguous()
     N, Ka, H, W = xa.shape
     M = conv_a.out_channels
-    wa, sa = _conv_bx_folded(conv_a, bn_a)
-    wb, sb = _conv_bx_folded(conv_b, bn_b)
-    # the sum of the two shifts, cached with the folded images it belongs to (three ATen launches per call otherwise)
-    cache = getattr(conv_a, '_mas_conv_bx_dual_shift', None)
-    if cache is None or cache[0] is not sa or cache[1] is not sb:
-        cache = conv_a._mas_conv_bx_dual_shift = (sa, sb, (sa.double() + sb.double()).float())
-    shift = cache[2]
+    def fold():
+        # the two folded images and the sum of their shifts (three ATen launches per call if it were not kept)
+        (wa, sa), (wb, sb) = _conv_bx_folded(conv_a, bn_a), _conv_bx_folded(conv_b, bn_b)
+        return wa, wb, (sa.double() + sb.double()).float()
+    wa, wb, shift = _cached(conv_a, '_mas_conv_bx_dual', (conv_a.weight,) + _bn_tensors(bn_a) + (conv_b.weight,) + _bn_tensors(bn_b), fold)
     y = torch.empty((N, M, H, W), dtype=torch.float32, device=xa.device)
     with torch.cuda.device(xa.device):
         _lib.check(_lib.load().mas_conv_bx_fwd_dual(xa.data_ptr(), wa.data_ptr(), Ka, xb.data_ptr(), wb.data_ptr(), xb.shape[1], N, H, W, M,
@@ -1718,15 +1733,7 @@ def conv_bx(conv, x, bn=None, relu=False, residual=None):
     M = conv.out_channels
     ks, s, d = conv.kernel_size[0], conv.stride[0], conv.dilation[0]
     wp = _conv_bx_weight(conv)
-    if bn is not None and bn.num_features != M:
-        raise ValueError("BatchNorm has %d features, the convolution %d output channels" % (bn.num_features, M))
-    scale, shift = _bn_fold(bn) if bn is not None else (None, None)
-    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
-    if residual is not None and (tuple(residual.shape) != (N, M, Ho, Wo) or residual.dtype != torch.float32 or residual.device != x.device):
-        raise ValueError("residual must be float32 %s on %s, got %s %s on %s"
-                         % ((N, M, Ho, Wo), x.device, residual.dtype, tuple(residual.shape), residual.device))
-    res = residual.contiguous() if residual is not None else None
-    y = torch.empty((N, M, Ho, Wo), dtype=torch.float32, device=x.device)
+    scale, shift, res, y = _fused_epilogue(bn, residual, (N, M, (H - 1) // s + 1, (W - 1) // s + 1), x.device)
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().mas_conv_bx_fwd(x.data_ptr(), wp.data_ptr(), N, K, H, W, M, ks, s, d, _opt(scale), _opt(shift), _opt(res),
                                                int(relu), y.data_ptr(), _stream(x)), "mas_conv_bx_fwd")
@@ -1760,9 +1767,7 @@ def conv_bx_pre(conv, x3, bn=None, relu=False, residual=None):
     if s != 1 or K != conv.in_channels:
         raise ValueError("conv_bx_pre: stride-1 convolutions on a presplit tensor of their input channels")
     wp = _conv_bx_weight(conv)
-    scale, shift = _bn_fold(bn) if bn is not None else (None, None)
-    res = residual.contiguous() if residual is not None else None
-    y = torch.empty((N, M, H, W), dtype=torch.float32, device=x3.data.device)
+    scale, shift, res, y = _fused_epilogue(bn, residual, (N, M, H, W), x3.data.device, strict=False)
     with torch.cuda.device(y.device):
         _lib.check(_lib.load().mas_conv_bx_fwd_pre(x3.data.data_ptr(), wp.data_ptr(), N, K, H, W, M, ks, d, _opt(scale), _opt(shift), _opt(res),
                                                    int(relu), y.data_ptr(), _stream(y)), "mas_conv_bx_fwd_pre")
@@ -1782,8 +1787,7 @@ def stem_conv(conv, x, bn=None, relu=False):
     x = x.contiguous()
     N, _, H, W = x.shape
     M = conv.out_channels
-    scale, shift = _bn_fold(bn) if bn is not None else (None, None)
-    y = torch.empty((N, M, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
+    scale, shift, _, y = _fused_epilogue(bn, None, (N, M, (H - 1) // 2 + 1, (W - 1) // 2 + 1), x.device, strict=False)
     w = conv.weight.detach().contiguous()
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().mas_stem_conv_fwd(x.data_ptr(), w.data_ptr(), N, H, W, M, _opt(scale), _opt(shift), int(relu), y.data_ptr(),
@@ -1801,11 +1805,7 @@ _WGRAD_WS = {}
 def _wgrad_workspace(dev, nbytes):
     """One split-K workspace per (device, stream), grown on demand (the kernels of one stream run in order, so consecutive weight
     gradients can share it; the weight gradients of a backward pass run on a side stream, _ConvTrain.backward)."""
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _WGRAD_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _WGRAD_WS[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    return ws
+    return _stream_scratch(_WGRAD_WS, dev, lambda: torch.empty(int(nbytes), dtype=torch.uint8, device=dev), nbytes)
 
 
 def conv_wgrad(x, dy, ksize, stride, dil):
@@ -1819,18 +1819,19 @@ def conv_wgrad(x, dy, ksize, stride, dil):
     if tuple(dy.shape) != (N, Cout, Ho, Wo):
         raise ValueError("dy %s does not match x %s under stride %d" % (tuple(dy.shape), tuple(x.shape), stride))
     lib = _lib.load()
-    if (ksize == 1 and stride == 1 and os.environ.get("MAS_TRAIN_BX", "auto") != "off" and Cout >= 96 and Cin >= 64
+    bx, r04 = _train_bx()
+    if (ksize == 1 and stride == 1 and bx and Cout >= 96 and Cin >= 64
             and lib.mas_conv_wgrad_bx_supported(N, Cin, H, W, Cout)):
         # 1x1: split-bf16 kernel (csrc/conv_wgrad_bx.hip), 1.3-1.7x the f32 kernel (profiles/r04/k_bx_train_table.md); with 64 or
         # fewer output channels half of its 128 x 128 tile is padding and the f32 kernel stays ahead
         return conv_wgrad_bx(x, dy)
-    if (ksize == 1 and stride == 2 and os.environ.get("MAS_TRAIN_BX", "auto") not in ("off", "r04") and Cout >= 96 and Cin >= 64
+    if (ksize == 1 and stride == 2 and bx and not r04 and Cout >= 96 and Cin >= 64
             and lib.mas_conv_wgrad_bx_supported(N, Cin, Ho, Wo, Cout)):
         # 1x1 stride 2 (`downsample`): dW only sees the even pixels of x -- gather them once (a quarter of x, one strided copy) and the
         # product is the stride-1 one on the small plane (the f32 kernel's strided K axis ran at 29 TFLOP/s: 168 us per layer)
         return conv_wgrad_bx(x[:, :, ::2, ::2].contiguous(), dy)
     w3 = os.environ.get("MAS_WGRAD3", "auto")
-    if (ksize == 3 and stride == 1 and os.environ.get("MAS_TRAIN_BX", "auto") not in ("off", "r04") and w3 != "f32"
+    if (ksize == 3 and stride == 1 and bx and not r04 and w3 != "f32"
             and lib.mas_conv_wgrad_bx3_supported(N, Cin, H, W, Cout, dil)):
         # 3x3 stride 1: split-bf16 kernel with the X patch read through gfx950's transposing LDS read (csrc/conv_wgrad_bx3.hip)
         return conv_wgrad_bx3(x, dy, dil)
@@ -1845,9 +1846,9 @@ def conv_wgrad(x, dy, ksize, stride, dil):
     return dw
 
 
-def conv_wgrad_bx(x, dy):
-    """dW [Cout,Cin,1,1] of a 1x1 stride-1 convolution from x [N,Cin,H,W] and dy [N,Cout,H,W] on the bf16 matrix cores with exact
-    three-term splits of both f32 operands (mas_conv_wgrad_bx: split-K over the pixels, fixed-order reduction)."""
+def _conv_wgrad_bx(x, dy, ks, dil):
+    """The split-bf16 weight gradient of a stride-1 convolution: mas_conv_wgrad_bx (1x1) / mas_conv_wgrad_bx3 (3x3, which alone takes
+    a dilation)."""
     _need(x, "x", torch.float32)
     _need(dy, "dy", torch.float32)
     N, Cin, H, W = x.shape
@@ -1855,35 +1856,28 @@ def conv_wgrad_bx(x, dy):
     if tuple(dy.shape) != (N, Cout, H, W):
         raise ValueError("dy %s does not match x %s" % (tuple(dy.shape), tuple(x.shape)))
     lib = _lib.load()
-    if not lib.mas_conv_wgrad_bx_supported(N, Cin, H, W, Cout):
-        raise ValueError("unsupported geometry for mas_conv_wgrad_bx: x %s" % (tuple(x.shape),))
-    ws = _wgrad_workspace(x.device, lib.mas_conv_wgrad_bx_workspace_bytes(Cin, Cout))
-    dw = torch.empty((Cout, Cin, 1, 1), dtype=torch.float32, device=x.device)
+    name, geom, extra = ("mas_conv_wgrad_bx", (), "") if ks == 1 else ("mas_conv_wgrad_bx3", (dil,), ", dilation %d" % dil)
+    if not getattr(lib, name + "_supported")(N, Cin, H, W, Cout, *geom):
+        raise ValueError("unsupported geometry for %s: x %s%s" % (name, tuple(x.shape), extra))
+    ws = _wgrad_workspace(x.device, getattr(lib, name + "_workspace_bytes")(Cin, Cout))
+    dw = torch.empty((Cout, Cin, ks, ks), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(lib.mas_conv_wgrad_bx(x.data_ptr(), dy.data_ptr(), N, Cin, H, W, Cout, dw.data_ptr(), ws.data_ptr(), ws.numel(),
-                                         _stream(x)), "mas_conv_wgrad_bx")
+        _lib.check(getattr(lib, name)(x.data_ptr(), dy.data_ptr(), N, Cin, H, W, Cout, *[int(d) for d in geom], dw.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), _stream(x)), name)
     return dw
+
+
+def conv_wgrad_bx(x, dy):
+    """dW [Cout,Cin,1,1] of a 1x1 stride-1 convolution from x [N,Cin,H,W] and dy [N,Cout,H,W] on the bf16 matrix cores with exact
+    three-term splits of both f32 operands (mas_conv_wgrad_bx: split-K over the pixels, fixed-order reduction)."""
+    return _conv_wgrad_bx(x, dy, 1, None)
 
 
 def conv_wgrad_bx3(x, dy, dil=1):
     """dW [Cout,Cin,3,3] of a 3x3 stride-1 convolution (padding = dilation = 1 | 2) from x [N,Cin,H,W] and dy [N,Cout,H,W] on the bf16
     matrix cores with exact three-term splits of both f32 operands (mas_conv_wgrad_bx3: the X patch staged channel-contiguous as the
     forward kernel stages it, read with ds_read_b64_tr_b16; split-K over chunks of 4 x 16 pixels, fixed-order reduction)."""
-    _need(x, "x", torch.float32)
-    _need(dy, "dy", torch.float32)
-    N, Cin, H, W = x.shape
-    Cout = dy.shape[1]
-    if tuple(dy.shape) != (N, Cout, H, W):
-        raise ValueError("dy %s does not match x %s" % (tuple(dy.shape), tuple(x.shape)))
-    lib = _lib.load()
-    if not lib.mas_conv_wgrad_bx3_supported(N, Cin, H, W, Cout, dil):
-        raise ValueError("unsupported geometry for mas_conv_wgrad_bx3: x %s, dilation %d" % (tuple(x.shape), dil))
-    ws = _wgrad_workspace(x.device, lib.mas_conv_wgrad_bx3_workspace_bytes(Cin, Cout))
-    dw = torch.empty((Cout, Cin, 3, 3), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.mas_conv_wgrad_bx3(x.data_ptr(), dy.data_ptr(), N, Cin, H, W, Cout, int(dil), dw.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          _stream(x)), "mas_conv_wgrad_bx3")
-    return dw
+    return _conv_wgrad_bx(x, dy, 3, dil)
 
 
 _SK_WS = {}
@@ -1892,10 +1886,7 @@ _SK_WS = {}
 def _sk_workspace(dev):
     """(workspace, epoch) of the stream-K convolution for the current stream of `dev`: partial-tile slots + epoch flags, zero-filled
     once; launches of one stream run in order and may share it, the epoch differs from launch to launch."""
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    ent = _SK_WS.get(key)
-    if ent is None:
-        ent = _SK_WS[key] = [torch.zeros(int(_lib.load().mas_conv_sk_workspace_bytes()), dtype=torch.uint8, device=dev), 0]
+    ent = _stream_scratch(_SK_WS, dev, lambda: [torch.zeros(int(_lib.load().mas_conv_sk_workspace_bytes()), dtype=torch.uint8, device=dev), 0])
     ent[1] = ent[1] % 0xfffffff0 + 1
     return ent[0], ent[1]
 
@@ -2056,11 +2047,7 @@ _BX_WS = {}
 def _bx_workspace(dev, nbytes):
     """Per-(device, stream) scratch for the partial tiles of a split-K mas_conv_bx_train launch (grown on demand, never shrunk; the
     launches of one stream run in order, so they can share it)."""
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _BX_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _BX_WS[key] = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=dev)
-    return ws
+    return _stream_scratch(_BX_WS, dev, lambda: torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=dev), nbytes)
 
 
 def conv_bx_train_plan(x_shape, w_shape, dil=1, dgrad=False):
@@ -2144,10 +2131,10 @@ def conv_bx_train_ok(x_shape, w_shape, stride, dil, dgrad):
     over several workgroups and use 16 x 16 pixel tiles (mas_conv_bx_train_plan; profiles/r05/k_bx_train_table.md); r04: round 4's
     rule (1x1 everywhere, 3x3 on planes of at least 96 x 96 or with at least 320 tiles -- the others on the persistent stream-K
     kernel), for A/B runs; off: never."""
-    mode = os.environ.get("MAS_TRAIN_BX", "auto")
+    bx, r04 = _train_bx()
     Cout, Cin, ks, _ = w_shape
     N, _, H, W = x_shape
-    if mode not in ("off", "r04") and stride == 2 and not dgrad and (ks == 1 or (ks == 3 and dil == 1 and os.environ.get("MAS_BX_S2K3", "on") != "off")):
+    if bx and not r04 and stride == 2 and not dgrad and (ks == 1 or (ks == 3 and dil == 1 and _bx_s2k3())):
         # the 1x1 stride-2 `downsample` convolutions (resnet.py:215-223) and the 3x3 stride-2 conv2 of layer2.0 / layer3.0 (:140-150):
         # the stride-2 form of the forward kernel (planes with even H and W % 8 == 0 -- the 768 crop; the 769 crop's odd planes stay
         # on the stream-K kernel)
@@ -2158,12 +2145,12 @@ def conv_bx_train_ok(x_shape, w_shape, stride, dil, dgrad):
         bm = 128 if Cout % 128 == 0 else 64
         wgs = (N * (H // 2) * (W // 2) + (16384 // bm) - 1) // (16384 // bm) * ((Cout + bm - 1) // bm)      # (pixel tile: 128 / 256)
         return ks == 1 or wgs >= 256
-    if mode == "off" or stride != 1:
+    if not bx or stride != 1:
         return False
     K, M = (Cout, Cin) if dgrad else (Cin, Cout)
     if not _lib.load().mas_conv_bx_supported(ks, 1, dil, K, M, H, W):
         return False
-    if mode != "r04" or ks == 1 or H * W >= 96 * 96:
+    if not r04 or ks == 1 or H * W >= 96 * 96:
         return True
     return N * ((H + 7) // 8) * ((W + 31) // 32) * ((M + 63) // 64) >= 320
 
@@ -2256,17 +2243,24 @@ def conv_sk(x, w, stride=1, dil=1, dgrad=False, scale=None, shift=None, residual
     return y
 
 
+def _dgrad_s2_operands(dy, w, H, W, ks):
+    """(N, Cin, Cout) of the input gradient of a ks x ks stride-2 convolution of an H x W plane, its operands checked."""
+    _need(dy, "dy", torch.float32)
+    _need(w, "w", torch.float32)
+    Cout, Cin, k, _ = w.shape
+    N = dy.shape[0]
+    if k != ks or tuple(dy.shape) != (N, Cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1):
+        raise ValueError("dy %s does not belong to a %dx%d stride-2 convolution of a %dx%d plane with weight %s"
+                         % (tuple(dy.shape), ks, ks, H, W, tuple(w.shape)))
+    return N, Cin, Cout
+
+
 def conv_sk_dgrad_s2(dy, w, H, W, packed=None, flags=None, spin_limit=0):
     """dX [N,Cin,H,W] of y = conv2d(x, w, stride 2, padding 1) for a 3x3 weight `w` [Cout,Cin,3,3] from dY [N,Cout,(H-1)//2+1,
     (W-1)//2+1]: four launches of the stream-K kernel, one per parity class of the dX pixels (mas_conv_sk_dgrad_s2) -- each a
     stride-1 product over the dY plane with 1 / 2 / 2 / 4 taps, together the exact FLOPs of the gradient (no zero insertion).
     ``packed``: the four class images (conv_sk_pack(w, 2, 2 + sub))."""
-    _need(dy, "dy", torch.float32)
-    _need(w, "w", torch.float32)
-    Cout, Cin, ks, _ = w.shape
-    N = dy.shape[0]
-    if ks != 3 or tuple(dy.shape) != (N, Cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1):
-        raise ValueError("dy %s does not belong to a 3x3 stride-2 convolution of a %dx%d plane with weight %s" % (tuple(dy.shape), H, W, tuple(w.shape)))
+    N, Cin, Cout = _dgrad_s2_operands(dy, w, H, W, 3)
     dx = torch.empty((N, Cin, H, W), dtype=torch.float32, device=dy.device)
     lib = _lib.load()
     opts, _ = _sk_opts(flags, spin_limit)
@@ -2285,12 +2279,7 @@ def conv_sk_dgrad_1x1s2(dy, w, H, W, packed=None):
     strided store of the stride-2 parity classes (class 0 of mas_conv_sk_dgrad_s2 is exactly a one-tap product written to the pixels
     (2i, 2j); it takes the 1x1 weight's input-gradient image) into a zero-filled dX.  (Until round 4: the product into a temporary,
     then zeros_like + a strided ATen copy.)"""
-    _need(dy, "dy", torch.float32)
-    _need(w, "w", torch.float32)
-    Cout, Cin, ks, _ = w.shape
-    N = dy.shape[0]
-    if ks != 1 or tuple(dy.shape) != (N, Cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1):
-        raise ValueError("dy %s does not belong to a 1x1 stride-2 convolution of a %dx%d plane with weight %s" % (tuple(dy.shape), H, W, tuple(w.shape)))
+    N, Cin, Cout = _dgrad_s2_operands(dy, w, H, W, 1)
     dx = torch.zeros((N, Cin, H, W), dtype=torch.float32, device=dy.device)
     img = packed if packed is not None else conv_sk_pack(w, 1, True)
     lib = _lib.load()
@@ -2314,7 +2303,7 @@ def conv_sk_error(dev=None):
     """Non-zero when a stream-K launch on the current stream's workspace gave up waiting for another workgroup (synchronises)."""
     import ctypes
     dev = torch.device('cuda', torch.cuda.current_device()) if dev is None else dev
-    ent = _SK_WS.get((dev, torch.cuda.current_stream(dev).cuda_stream))
+    ent = _SK_WS.get(_stream_key(dev))
     if ent is None:
         return 0
     torch.cuda.synchronize(dev)
@@ -2419,18 +2408,20 @@ def _async_wgrad_ok(w):
     return not (dist.is_available() and dist.is_initialized())      # (any process group: a reducer hooks the AccumulateGrad nodes, not the tensors)
 
 
+def _join_side(dev):
+    """The main stream of `dev` waits for the weight gradients queued on the side stream."""
+    _JOIN_QUEUED.discard(dev)
+    torch.cuda.current_stream(dev).wait_stream(_side_stream(dev))
+    _KEEP_UNTIL_JOIN.pop(dev, None)                 # (only now may the operands of the weight gradients be freed: see _ConvTrain.backward)
+
+
 def _join_side_after_backward(dev):
     """Queue ONE callback per backward pass (torch.autograd's engine runs it when the pass has finished, before .backward() returns):
     the main stream waits for the side stream there."""
     if dev in _JOIN_QUEUED:
         return
     _JOIN_QUEUED.add(dev)
-
-    def join():
-        _JOIN_QUEUED.discard(dev)
-        torch.cuda.current_stream(dev).wait_stream(_side_stream(dev))
-        _KEEP_UNTIL_JOIN.pop(dev, None)             # (only now may the operands of the weight gradients be freed: see _ConvTrain.backward)
-    torch.autograd.Variable._execution_engine.queue_callback(join)
+    torch.autograd.Variable._execution_engine.queue_callback(lambda: _join_side(dev))
 
 
 def _aten_pad(ks, dil):
@@ -2451,9 +2442,7 @@ class _ConvTrain(torch.autograd.Function):
     def forward(ctx, x, w, stride, dil, own, stats=False, fork=False):
         if _JOIN_QUEUED:                    # a backward pass that raised before its end-of-pass callback ran: join the side stream now
             for dev in list(_JOIN_QUEUED):
-                _JOIN_QUEUED.discard(dev)
-                torch.cuda.current_stream(dev).wait_stream(_side_stream(dev))
-                _KEEP_UNTIL_JOIN.pop(dev, None)
+                _join_side(dev)
         x = x.contiguous()
         ks = w.shape[2]
         part = None
@@ -2533,17 +2522,15 @@ class _ConvTrain(torch.autograd.Function):
             else:
                 dw = conv_wgrad(x, dy, ks, stride, dil)
         if need_dx:
-            if own[1] and stride == 1 and conv_bx_train_ok(dy.shape, w.shape, 1, dil, True):
+            if own[1] and stride == 1:
+                # the gradient of x's other consumer is added in the epilogue of either kernel, where it can be
                 fuse = g_other is not None and g_other.shape == x.shape and g_other.dtype == torch.float32
-                dx = conv_bx_raw(dy, w, dil, dgrad=True, residual=g_other.contiguous() if fuse else None, packed=bx_packed_weight(w, 1))
+                if conv_bx_train_ok(dy.shape, w.shape, 1, dil, True):
+                    dx = conv_bx_raw(dy, w, dil, dgrad=True, residual=g_other.contiguous() if fuse else None, packed=bx_packed_weight(w, 1))
+                else:
+                    dx = conv_sk(dy, w, 1, dil, dgrad=True, packed=packed_weight(w, 1, True), residual=g_other.contiguous() if fuse else None)
                 if fuse:
                     g_other = None
-            elif own[1] and stride == 1:
-                if g_other is not None and g_other.shape == x.shape and g_other.dtype == torch.float32:
-                    dx = conv_sk(dy, w, 1, dil, dgrad=True, packed=packed_weight(w, 1, True), residual=g_other.contiguous())
-                    g_other = None
-                else:
-                    dx = conv_sk(dy, w, 1, dil, dgrad=True, packed=packed_weight(w, 1, True))
             elif own[1] and ks == 1:
                 # 1x1, stride 2: the input gradient lives on the even positions only -- the stride-1 product over the small plane,
                 # stored with stride 2 into a zero-filled tensor by the kernel itself
@@ -2570,16 +2557,10 @@ class _ConvTrain(torch.autograd.Function):
 def conv_wgrad_supported(conv, x):
     """mas_conv_wgrad takes every dense 1x1 / 3x3 convolution of the network: any channel counts and plane sizes, stride 1 / 2,
     padding = dilation (3x3) / 0 (1x1), dilation 1 / 2 / 4 at stride 1."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.groups == 1 and conv.bias is None):
+    geom = _conv_geometry(conv, x)
+    if geom is None or not _is_1x1_or_3x3(*geom, dilations=(1, 2, 4)):
         return False
-    k, s, d, pd = conv.kernel_size, conv.stride, conv.dilation, conv.padding
-    if k[0] != k[1] or s[0] != s[1] or d[0] != d[1] or pd[0] != pd[1] or k[0] not in (1, 3) or s[0] not in (1, 2):
-        return False
-    if k[0] == 3 and (pd[0] != d[0] or d[0] not in (1, 2, 4) or (s[0] == 2 and d[0] != 1)):
-        return False
-    if k[0] == 1 and (pd[0] != 0 or d[0] != 1):
-        return False
-    return x.shape[1] == conv.in_channels and max(conv.in_channels, conv.out_channels) * x.shape[2] * x.shape[3] < 2 ** 31
+    return max(conv.in_channels, conv.out_channels) * x.shape[2] * x.shape[3] < 2 ** 31
 
 
 def conv_train_plan(conv, x):
