@@ -54,7 +54,8 @@ extern "C" {
  * mas_conv_bx_fwd); 6 = role 2 of mas_conv_bx_pack / _packed_bytes / _pack_job and ksize 3 at stride 2 in mas_conv_bx_supported /
  * mas_conv_bx_fwd (a library of version 5 answers "unsupported" to both); 8 = the region-label entry points of the data-generation
  * step (mas_region_label_counts, mas_region_multi_hot, mas_region_dominant, mas_region_paint); 9 = mas_ms_ensemble.  mas_naive_plbl and
- * mas_spx_max_onehot came later under 9, then mas_lowres_iou_counts, then mas_render_labels and mas_render_lowres_pred, then mas_ms_naive_plbl: new entry
+ * mas_spx_max_onehot came later under 9, then mas_lowres_iou_counts, then mas_render_labels and mas_render_lowres_pred, then mas_ms_naive_plbl, then mas_ms_iou_counts and
+ * mas_ms_iou_lds_bytes: new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -479,6 +480,24 @@ int mas_naive_plbl(const float* logits_q, int N, int C, int h, int w, int H, int
 int mas_ms_naive_plbl(const float* const* logits_q, const int32_t* geometry /* [n,5] */, int n, int C, int H, int W,
                       const int64_t* targets /* [H,W] or NULL */, int num_classes, int64_t ignore_label, uint8_t* labels /* [H,W] */,
                       uint64_t* counts /* [3K+3] or NULL, accumulated */, void* stream);
+
+/* Multi-scale + flip evaluation of a checkpoint (--method eval_naive_ms): the counters of mas_logits_iou_counts on the mean logits of
+ * mas_ms_ensemble, in one launch per picture.  Sources, geometry and mean exactly those of mas_ms_naive_plbl (n <= MAS_MS_MAX_SOURCES,
+ * logits_q[k] f32 [CH,hq,wq], geometry[5k..5k+4] = (hq, wq, Hs, Ws, flip); m = the sum in source order / (float)n, bit for bit
+ * mas_ms_ensemble's logit_out).  K = num_classes, CH = K or K + 1 (MAS_ERR_CLASSES otherwise; 1 <= K <= MAS_MAX_CLASSES): o_cls = the
+ * first arg-max of m over the channels [0, K), o_all = the first arg-max over all CH channels (strict '>'; a NaN takes the place and keeps
+ * it, as torch.max).  counts int64 [3K+3] in the layout of mas_iou_counts, ADDED to, not reset: MeanIoU(K, ignore_label)._after_step(o_cls,
+ * targets) and, when CH == K + 1, IoUIgnore._after_step(o_all, targets) (trainer/eval_naive.py:61-63 on the mean logits); with CH == K the
+ * "undefined" triple stays untouched.  targets int64 [H,W] and counts are required (MAS_ERR_NULL); pred u8 [H,W] (optional) receives
+ * o_cls.  MAS_ERR_RANGE when n is out of range or a stage-2 downsample needs more LDS than one tile may use (factors up to 2.0 fit);
+ * MAS_ERR_SHAPE for the geometry rules of mas_ms_ensemble.  Nothing is written when an argument is refused. */
+int mas_ms_iou_counts(const float* const* logits_q, const int32_t* geometry /* [n,5] */, int n, int CH, int H, int W,
+                      const int64_t* targets /* [H,W] */, int num_classes, int64_t ignore_label,
+                      uint64_t* counts /* [3K+3], accumulated */, uint8_t* pred /* [H,W] or NULL */, void* stream);
+
+/* The LDS in bytes one workgroup of mas_ms_iou_counts / mas_ms_naive_plbl needs for these sources (the launch's own sizing code; no
+ * device is touched), or a negative argument error.  The entry points refuse more than 65536 with MAS_ERR_RANGE. */
+int64_t mas_ms_iou_lds_bytes(const int32_t* geometry /* [n,5] */, int n, int H, int W);
 
 /* Colour images of label maps (--save_vis of the stage-2 generators, trainer/eval_save_cosplbl_prop.py:77-86; eval_naive_vis.py:70-83).
  * labels [N,H,W] of label_dtype MAS_ID_I64 or MAS_MAP_U8; palette u8 [P,3], 1 <= P <= 256; a label 255 takes the colour of `fill`

@@ -74,6 +74,8 @@ SIGNATURES = {
     "mas_ms_ensemble": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mas_naive_plbl": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp]),
     "mas_ms_naive_plbl": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i64, _vp, _vp, _vp]),
+    "mas_ms_iou_counts": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i64, _vp, _vp, _vp]),
+    "mas_ms_iou_lds_bytes": (_i64, [_vp, _i, _i, _i]),
     "mas_render_labels": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "mas_render_lowres_pred": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "mas_bn_workspace_bytes": (_i64, [_i, _i, _i]),

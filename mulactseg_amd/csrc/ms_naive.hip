@@ -1,5 +1,6 @@
 // ms_naive.hip -- naive arg-max pseudo labels of the VOC generators (single-scale and multi-scale + flip) and their IoU counters, in
-// one launch per picture from the network's quarter-resolution logits.
+// one launch per picture from the network's quarter-resolution logits (mas_ms_naive_plbl); and, from the same sources and the same mean
+// logits, the counters of the evaluation loop (mas_ms_iou_counts: multi-scale + flip evaluation of a checkpoint, eval_naive_ms).
 //
 // Reference: trainer/eval_save_cosplbl_naive_voc.py:54-67 and trainer/eval_save_cosplbl_naive_voc_ms.py:55-92.  Every source k (the
 // picture itself, or one of the ten TestTimeAugmentation copies) went through feat_forward (logits upsampled x4 to the scaled size
@@ -19,6 +20,13 @@
 //      global atomic per non-zero counter, added to the caller's buffer.  Integer sums: deterministic.
 // So labels == torch.max(mas_ms_ensemble's logits, 1)[1] for any input, and with n = 1 and the geometry (hq, wq, H, W, 0) labels ==
 // torch.max(mas_upsample_bilinear_fwd(z_q, H, W), 1)[1].
+//
+// Evaluation mode (k_ms_naive<true>, mas_ms_iou_counts; tests/ms_eval_restated.py restates it).  Steps 1-4 unchanged; C = K or K + 1
+// channels with K = num_classes (the stage-2 model of eval_naive carries one "undefined" channel):
+//   5'. o_cls = the first arg-max of m over the channels [0, K), o_all = the first arg-max over all C channels, both with the rule of
+//       step 5.  One walk: channel K moves o_all away from o_cls exactly when arg_update would move the arg-max.
+//   6'. tally(K, t, o_cls, o_all, ignore_label, C == K + 1): the MeanIoU(K) triples and, with the extra channel, the "undefined" triple
+//       of IoUIgnore (reference trainer/eval_naive.py:61-63 applied to the mean logits).  pred (optional) receives o_cls.
 //
 // Shape: the tiling of k_ms_ensemble.  A workgroup owns an 8 x 32 output tile, one pixel per thread, and walks the channels in blocks
 // of kCB, sources innermost; per (block, source):
@@ -40,8 +48,9 @@ constexpr int kThreads = kTH * kTW;        // one output pixel per thread
 constexpr int kCB = 8;                     // channels per LDS block
 constexpr int kPos = 2;                    // (quarter row, stage-1 column) positions per thread and load round in A
 constexpr int kWaves = kThreads / MAS_WAVE;
-constexpr size_t kMaxLds = 64 * 1024;
+constexpr size_t kMaxLds = 64 * 1024;      // of one workgroup: the dynamic buffers and the static counters together
 constexpr int kMaxCnt = 3 * (MAS_MAX_CLASSES + 1);
+constexpr size_t kStaticLds = sizeof(unsigned) * kMaxCnt;
 
 struct NvSrc {
     const float* logit;           // [C, hq, wq]
@@ -52,8 +61,8 @@ struct NvSrc {
 struct NvArgs {
     NvSrc src[MAS_MS_MAX_SOURCES];
     const long long* t;           // [H, W] or NULL (no counters)
-    unsigned char* labels;        // [H, W]
-    mas_u64* counts;              // [3K+3] or NULL
+    unsigned char* labels;        // [H, W]; evaluation mode: o_cls, or NULL
+    mas_u64* counts;              // [3K+3] or NULL (evaluation mode: never NULL)
     long long ignore_label;
     int n, C, K, H, W;
     int nrq, nr1, nc1;            // LDS extents: quarter rows, stage-1 rows, stage-1 columns of one tile
@@ -83,7 +92,9 @@ __device__ __forceinline__ void arg_update(float v, int c, float& best, int& idx
     }
 }
 
-// grid: (ceil(W / kTW), ceil(H / kTH)); dynamic LDS: kCB * (nrq + nr1) * nc1 floats
+// grid: (ceil(W / kTW), ceil(H / kTH)); dynamic LDS: kCB * (nrq + nr1) * nc1 floats.  kEval: the two arg-maxes and the tally of the
+// evaluation loop instead of the one arg-max of the pseudo labels; staging and stage 2 are the same code.
+template <bool kEval>
 __global__ __launch_bounds__(kThreads) void k_ms_naive(const NvArgs a) {
     extern __shared__ float lds[];
     __shared__ unsigned s_cnt[kMaxCnt];
@@ -103,6 +114,7 @@ __global__ __launch_bounds__(kThreads) void k_ms_naive(const NvArgs a) {
         for (int i = tid; i < 3 * a.K + 3; i += kThreads) s_cnt[i] = 0;   // (the first barrier below orders it before the tally)
     float best = 0.0f;
     int idx = 0;
+    bool all_is_k = false;                               // (kEval) channel K holds the arg-max over all channels
     for (int ch0 = 0; ch0 < C; ch0 += kCB) {
         const int nb = min(kCB, C - ch0);
         float acc[kCB];
@@ -185,16 +197,56 @@ __global__ __launch_bounds__(kThreads) void k_ms_naive(const NvArgs a) {
             if (cb < nb) {
                 const float m = acc[cb] / fn;
                 if (ch0 + cb == 0) best = m;
-                else arg_update(m, ch0 + cb, best, idx);
+                else if (!kEval || ch0 + cb < a.K) arg_update(m, ch0 + cb, best, idx);
+                else all_is_k = best == best && (m > best || m != m);   // (C == K + 1: the last channel; arg_update's rule)
             }
         }
     }
-    if (live) a.labels[pix] = (unsigned char)idx;
+    if (live && (!kEval || a.labels)) a.labels[pix] = (unsigned char)idx;
     if (!counting) return;
-    if (live) tally(s_cnt, a.K, t, idx, idx, a.ignore_label, false);
+    if (live) tally(s_cnt, a.K, t, idx, kEval && all_is_k ? a.K : idx, a.ignore_label, kEval && C > a.K);
     __syncthreads();
     for (int i = tid; i < 3 * a.K + 3; i += kThreads)
         if (s_cnt[i]) atomicAdd(&a.counts[i], (mas_u64)s_cnt[i]);
+}
+
+// The sources of a.n, a.H, a.W from the caller's tables and the LDS extents of one tile: the exact maxima over tiles and sources (same
+// tap arithmetic as the kernel).  logits_q == NULL: geometry only (mas_ms_iou_lds_bytes).  *lds: the dynamic LDS of the launch.
+static int set_sources(NvArgs& a, const float* const* logits_q, const int32_t* geometry, size_t* lds) {
+    const int n = a.n, H = a.H, W = a.W;
+    for (int k = 0; k < MAS_MS_MAX_SOURCES; ++k) a.src[k] = NvSrc{};
+    for (int k = 0; k < n; ++k) {
+        const int32_t* g = geometry + 5 * k;
+        NvSrc& s = a.src[k];
+        if (logits_q) {
+            if (!logits_q[k]) return MAS_ERR_NULL;
+            s.logit = logits_q[k];
+        }
+        s.hq = g[0], s.wq = g[1], s.hs = g[2], s.ws = g[3], s.flip = g[4] != 0;
+        // stage 1 is an upsampling (the network's x4); the scaled picture is not empty (the rules of mas_ms_ensemble)
+        if (s.hq < 1 || s.wq < 1 || s.hs < 1 || s.ws < 1 || s.hq > s.hs || s.wq > s.ws) return MAS_ERR_SHAPE;
+        s.s1h = (float)s.hq / (float)s.hs, s.s1w = (float)s.wq / (float)s.ws;
+        s.s2h = (float)s.hs / (float)H, s.s2w = (float)s.ws / (float)W;
+    }
+    int nrq = 1, nr1 = 1, nc1 = 1;
+    for (int k = 0; k < n; ++k) {
+        const NvSrc& s = a.src[k];
+        for (int y0 = 0; y0 < H; y0 += kTH) {
+            int r_lo, r_hi, q_lo, q_hi;
+            row_span(s, y0, (y0 + kTH < H ? y0 + kTH : H) - 1, r_lo, r_hi, q_lo, q_hi);
+            nr1 = r_hi - r_lo + 1 > nr1 ? r_hi - r_lo + 1 : nr1;
+            nrq = q_hi - q_lo + 1 > nrq ? q_hi - q_lo + 1 : nrq;
+        }
+        for (int x0 = 0; x0 < W; x0 += kTW) {
+            int c_lo, c_hi;
+            col_span(s, x0, (x0 + kTW < W ? x0 + kTW : W) - 1, c_lo, c_hi);
+            nc1 = c_hi - c_lo + 1 > nc1 ? c_hi - c_lo + 1 : nc1;
+        }
+    }
+    a.nrq = nrq, a.nr1 = nr1, a.nc1 = nc1;
+    *lds = sizeof(float) * kCB * (size_t)(nrq + nr1) * nc1;
+    // a stage-2 downsample beyond what one tile's LDS holds (x2, the largest factor of an evaluation, fits; the VOC factors stop at 1.5)
+    return *lds + kStaticLds > kMaxLds ? MAS_ERR_RANGE : 0;
 }
 }  // namespace
 
@@ -211,38 +263,41 @@ extern "C" int mas_ms_naive_plbl(const float* const* logits_q, const int32_t* ge
     a.counts = reinterpret_cast<mas_u64*>(counts);
     a.ignore_label = (long long)ignore_label;
     a.n = n, a.C = C, a.K = counts ? num_classes : 0, a.H = H, a.W = W;
-    for (int k = 0; k < MAS_MS_MAX_SOURCES; ++k) a.src[k] = NvSrc{};
-    for (int k = 0; k < n; ++k) {
-        const int32_t* g = geometry + 5 * k;
-        NvSrc& s = a.src[k];
-        if (!logits_q[k]) return MAS_ERR_NULL;
-        s.logit = logits_q[k];
-        s.hq = g[0], s.wq = g[1], s.hs = g[2], s.ws = g[3], s.flip = g[4] != 0;
-        // stage 1 is an upsampling (the network's x4); the scaled picture is not empty (the rules of mas_ms_ensemble)
-        if (s.hq < 1 || s.wq < 1 || s.hs < 1 || s.ws < 1 || s.hq > s.hs || s.wq > s.ws) return MAS_ERR_SHAPE;
-        s.s1h = (float)s.hq / (float)s.hs, s.s1w = (float)s.wq / (float)s.ws;
-        s.s2h = (float)s.hs / (float)H, s.s2w = (float)s.ws / (float)W;
-    }
-    // LDS extents: the exact maxima over tiles and sources (same tap arithmetic as the kernel)
-    int nrq = 1, nr1 = 1, nc1 = 1;
-    for (int k = 0; k < n; ++k) {
-        const NvSrc& s = a.src[k];
-        for (int y0 = 0; y0 < H; y0 += kTH) {
-            int r_lo, r_hi, q_lo, q_hi;
-            row_span(s, y0, (y0 + kTH < H ? y0 + kTH : H) - 1, r_lo, r_hi, q_lo, q_hi);
-            nr1 = r_hi - r_lo + 1 > nr1 ? r_hi - r_lo + 1 : nr1;
-            nrq = q_hi - q_lo + 1 > nrq ? q_hi - q_lo + 1 : nrq;
-        }
-        for (int x0 = 0; x0 < W; x0 += kTW) {
-            int c_lo, c_hi;
-            col_span(s, x0, (x0 + kTW < W ? x0 + kTW : W) - 1, c_lo, c_hi);
-            nc1 = c_hi - c_lo + 1 > nc1 ? c_hi - c_lo + 1 : nc1;
-        }
-    }
-    const size_t lds = sizeof(float) * kCB * (size_t)(nrq + nr1) * nc1;
-    if (lds > kMaxLds) return MAS_ERR_RANGE;         // a stage-2 downsample far beyond the 1.5 of the VOC factors
-    a.nrq = nrq, a.nr1 = nr1, a.nc1 = nc1;
-    hipLaunchKernelGGL(k_ms_naive, dim3((unsigned)((W + kTW - 1) / kTW), (unsigned)((H + kTH - 1) / kTH)), dim3(kThreads), lds,
+    size_t lds;
+    const int st = set_sources(a, logits_q, geometry, &lds);
+    if (st != 0) return st;
+    hipLaunchKernelGGL(k_ms_naive<false>, dim3((unsigned)((W + kTW - 1) / kTW), (unsigned)((H + kTH - 1) / kTH)), dim3(kThreads), lds,
                        static_cast<hipStream_t>(stream), a);
     return mas_launch_status();
+}
+
+extern "C" int mas_ms_iou_counts(const float* const* logits_q, const int32_t* geometry, int n, int CH, int H, int W, const int64_t* targets,
+                                 int num_classes, int64_t ignore_label, uint64_t* counts, uint8_t* pred, void* stream) {
+    if (!logits_q || !geometry || !targets || !counts) return MAS_ERR_NULL;
+    if (n < 1 || n > MAS_MS_MAX_SOURCES) return MAS_ERR_RANGE;
+    if (num_classes < 1 || num_classes > MAS_MAX_CLASSES || (CH != num_classes && CH != num_classes + 1)) return MAS_ERR_CLASSES;
+    if (H < 1 || W < 1 || H > 65535 * kTH) return MAS_ERR_SHAPE;
+    NvArgs a;
+    a.t = reinterpret_cast<const long long*>(targets);
+    a.labels = pred;
+    a.counts = reinterpret_cast<mas_u64*>(counts);
+    a.ignore_label = (long long)ignore_label;
+    a.n = n, a.C = CH, a.K = num_classes, a.H = H, a.W = W;
+    size_t lds;
+    const int st = set_sources(a, logits_q, geometry, &lds);
+    if (st != 0) return st;
+    hipLaunchKernelGGL(k_ms_naive<true>, dim3((unsigned)((W + kTW - 1) / kTW), (unsigned)((H + kTH - 1) / kTH)), dim3(kThreads), lds,
+                       static_cast<hipStream_t>(stream), a);
+    return mas_launch_status();
+}
+
+extern "C" int64_t mas_ms_iou_lds_bytes(const int32_t* geometry, int n, int H, int W) {
+    if (!geometry) return MAS_ERR_NULL;
+    if (n < 1 || n > MAS_MS_MAX_SOURCES) return MAS_ERR_RANGE;
+    if (H < 1 || W < 1 || H > 65535 * kTH) return MAS_ERR_SHAPE;
+    NvArgs a;
+    a.n = n, a.H = H, a.W = W;
+    size_t lds;
+    const int st = set_sources(a, nullptr, geometry, &lds);
+    return st == 0 || st == MAS_ERR_RANGE ? (int64_t)(lds + kStaticLds) : (int64_t)st;
 }

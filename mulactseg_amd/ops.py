@@ -1118,10 +1118,10 @@ def _meaniou_counts_aten(labels, targets, K, ignore_label, counts):
     return counts
 
 
-def _ms_naive_aten(logits_q, sizes, flips, out_size):
+def _ms_mean_aten(logits_q, sizes, flips, out_size):
     """The reference's lines (``eval_save_cosplbl_naive_voc_ms.py:59-87``) on the quarter-resolution logits: ``feat_forward``'s x4
     upsampling (``upsample_bilinear`` on the GPU, ``F.interpolate`` on the CPU), the flip back, ``F.interpolate`` to the original size,
-    the sum in source order, ``/ n``, ``max(1)``."""
+    the sum in source order, ``/ n`` -> the mean logits [1,C,H,W]."""
     import torch.nn.functional as F
     acc = None
     for z, (Hs, Ws), fl in zip(logits_q, sizes, flips):
@@ -1133,30 +1133,19 @@ def _ms_naive_aten(logits_q, sizes, flips, out_size):
             s = s.flip(-1)
         v = F.interpolate(s, size=tuple(out_size), mode='bilinear', align_corners=False)
         acc = v if acc is None else acc + v
-    return (acc / len(logits_q)).max(dim=1)[1]
+    return acc / len(logits_q)
 
 
-def ms_naive_labels(logits_q, scaled_sizes, flips, out_size, targets=None, counts=None, num_classes=None, ignore_label=255):
-    """Naive arg-max pseudo labels int64 ``[1,H,W]`` of the VOC generators (``trainer/eval_save_cosplbl_naive_voc[_ms].py``) from n <= 16
-    sources, each the network's quarter-resolution logits ``[1,C,hq,wq]`` (``net(x, lowres=True)``) on the picture scaled to
-    ``scaled_sizes[k] = (Hs, Ws)`` and flipped horizontally when ``flips[k]``: upsampled x4 to the scaled size, flipped back, resized to
-    ``out_size = (H, W)``, averaged, the first arg-max over the channels -- ``torch.max(ms_ensemble(...)[1], 1)[1]`` bit for bit.
-    ``counts`` (int64 ``[3K+3]``, K = ``num_classes``, required with it): ``MeanIoU(K, ignore_label)._after_step`` of the labels against
-    ``targets`` (int64 ``[1,H,W]`` or ``[H,W]``) is ADDED to it.  One launch (``csrc/ms_naive.hip``): neither the scaled-size nor the
-    full-resolution logits exist.  CPU tensors, and ``MAS_MS_NAIVE=aten``, take the reference's ATen chain."""
+def _ms_sources(name, logits_q, scaled_sizes, flips, out_size):
+    """The argument checks the multi-scale ops share -> (n, device, C, the [n,5] geometry table as a flat list, H, W)."""
     n = len(logits_q)
     if not 1 <= n <= _lib.MS_MAX_SOURCES:
-        raise ValueError("ms_naive_labels takes 1 .. %d sources, got %d" % (_lib.MS_MAX_SOURCES, n))
+        raise ValueError("%s takes 1 .. %d sources, got %d" % (name, _lib.MS_MAX_SOURCES, n))
     if len(scaled_sizes) != n or len(flips) != n:
         raise ValueError("logits_q, scaled_sizes and flips must have one entry per source")
     H, W = int(out_size[0]), int(out_size[1])
     if H < 1 or W < 1:
         raise ValueError("out_size must be non-empty, got %r" % (tuple(out_size),))
-    if counts is not None:
-        if num_classes is None:
-            raise ValueError("num_classes is required with counts")
-        if targets is None:
-            raise ValueError("targets are required with counts")
     dev = logits_q[0].device
     C = None
     geom = []
@@ -1180,6 +1169,23 @@ def ms_naive_labels(logits_q, scaled_sizes, flips, out_size, targets=None, count
             raise ValueError("source %d: quarter-resolution logits %dx%d are not what the network emits for %dx%d (%dx%d)"
                              % (k, hq, wq, Hs, Ws, quarter_size(Hs), quarter_size(Ws)))
         geom += [hq, wq, Hs, Ws, 1 if flips[k] else 0]
+    return n, dev, C, geom, H, W
+
+
+def ms_naive_labels(logits_q, scaled_sizes, flips, out_size, targets=None, counts=None, num_classes=None, ignore_label=255):
+    """Naive arg-max pseudo labels int64 ``[1,H,W]`` of the VOC generators (``trainer/eval_save_cosplbl_naive_voc[_ms].py``) from n <= 16
+    sources, each the network's quarter-resolution logits ``[1,C,hq,wq]`` (``net(x, lowres=True)``) on the picture scaled to
+    ``scaled_sizes[k] = (Hs, Ws)`` and flipped horizontally when ``flips[k]``: upsampled x4 to the scaled size, flipped back, resized to
+    ``out_size = (H, W)``, averaged, the first arg-max over the channels -- ``torch.max(ms_ensemble(...)[1], 1)[1]`` bit for bit.
+    ``counts`` (int64 ``[3K+3]``, K = ``num_classes``, required with it): ``MeanIoU(K, ignore_label)._after_step`` of the labels against
+    ``targets`` (int64 ``[1,H,W]`` or ``[H,W]``) is ADDED to it.  One launch (``csrc/ms_naive.hip``): neither the scaled-size nor the
+    full-resolution logits exist.  CPU tensors, and ``MAS_MS_NAIVE=aten``, take the reference's ATen chain."""
+    if counts is not None:
+        if num_classes is None:
+            raise ValueError("num_classes is required with counts")
+        if targets is None:
+            raise ValueError("targets are required with counts")
+    n, dev, C, geom, H, W = _ms_sources("ms_naive_labels", logits_q, scaled_sizes, flips, out_size)
     if not 1 <= C <= 255:
         raise ValueError("ms_naive_labels takes 1 .. 255 channels, got %d" % C)
     K = None if num_classes is None else int(num_classes)
@@ -1197,7 +1203,7 @@ def ms_naive_labels(logits_q, scaled_sizes, flips, out_size, targets=None, count
             raise ValueError("counts must be int64 [3K+3] = [%d] on the logits' device" % (3 * K + 3))
     sizes = [(int(s[0]), int(s[1])) for s in scaled_sizes]
     if not logits_q[0].is_cuda or os.environ.get("MAS_MS_NAIVE", "fused") == "aten":
-        labels = _ms_naive_aten(logits_q, sizes, [bool(f) for f in flips], (H, W))
+        labels = _ms_mean_aten(logits_q, sizes, [bool(f) for f in flips], (H, W)).max(dim=1)[1]
         if counts is not None:
             t = targets.reshape(1, H, W)
             if labels.is_cuda:
@@ -1218,6 +1224,102 @@ def ms_naive_labels(logits_q, scaled_sizes, flips, out_size, targets=None, count
                                                  K if counts is not None else 0, int(ignore_label), out.data_ptr(),
                                                  counts.data_ptr() if counts is not None else None, _stream(out)), "mas_ms_naive_plbl")
     return out.long()
+
+
+MS_MAX_LDS = 64 * 1024      # the LDS one workgroup of csrc/ms_naive.hip may use
+
+
+def _ms_geometry(logits_q, scaled_sizes, flips):
+    return [v for z, s, f in zip(logits_q, scaled_sizes, flips)
+            for v in (int(z.shape[-2]), int(z.shape[-1]), int(s[0]), int(s[1]), 1 if f else 0)]
+
+
+def ms_iou_lds_bytes(geometry, out_size):
+    """The LDS one workgroup of ``mas_ms_iou_counts`` needs for the flat ``[n,5]`` geometry table ``(hq, wq, Hs, Ws, flip)`` and
+    ``out_size`` -- the launch's own sizing code (``mas_ms_iou_lds_bytes``; no device is touched) -- or a negative status."""
+    n = len(geometry) // 5
+    g = (ctypes.c_int32 * (5 * n))(*[int(v) for v in geometry])
+    return int(_lib.load().mas_ms_iou_lds_bytes(g, n, int(out_size[0]), int(out_size[1])))
+
+
+def ms_iou_supported(logits_q, scaled_sizes, flips, out_size):
+    """True on GPU tensors when ``mas_ms_iou_counts`` accepts the sources: 1 .. 16 of them, each an upsampling to its scaled size, and a
+    stage-2 downsample whose tile fits the LDS (factors up to 2.0 do), by the entry point's own sizing code."""
+    n = len(logits_q)
+    if not 1 <= n <= _lib.MS_MAX_SOURCES or len(scaled_sizes) != n or len(flips) != n:
+        return False
+    if not all(torch.is_tensor(z) and z.is_cuda and z.dim() == 4 for z in logits_q):
+        return False
+    if int(out_size[0]) < 1 or int(out_size[1]) < 1:
+        return False
+    return 0 <= ms_iou_lds_bytes(_ms_geometry(logits_q, scaled_sizes, flips), out_size) <= MS_MAX_LDS
+
+
+def _iou_counts_aten(m, targets, K, ignore_label, counts):
+    """``MeanIoU(K)._after_step(m[:, :K].max(1)[1])`` and, with K + 1 channels, ``IoUIgnore(K)._after_step(m.max(1)[1])`` of the reference
+    (``trainer/eval_naive.py:61-63``, ``utils/miou.py:23-38``, ``utils/miou_evalignore.py:20-32``) in torch, added to ``counts`` [3K+3]."""
+    o_cls = m[:, :K].max(dim=1)[1]
+    _meaniou_counts_aten(o_cls, targets, K, ignore_label, counts)
+    if m.shape[1] > K:
+        tig, oig = targets == ignore_label, m.max(dim=1)[1] == K
+        counts[3 * K] += int(torch.sum(tig))
+        counts[3 * K + 1] += int(torch.sum(tig & oig))
+        counts[3 * K + 2] += int(torch.sum(oig))
+    return o_cls
+
+
+def ms_iou_counts(logits_q, scaled_sizes, flips, out_size, targets, num_classes, ignore_label, counts=None, pred=None):
+    """The evaluation counters (``logits_iou_counts``: ``MeanIoU`` + ``IoUIgnore``) of the mean logits of n <= 16 scaled and flipped copies
+    of one picture -- multi-scale + flip evaluation.  Sources as ``ms_naive_labels``: ``logits_q[k]`` f32 ``[1,CH,hq,wq]`` is the
+    network's quarter-resolution output on the picture scaled to ``scaled_sizes[k]`` and flipped when ``flips[k]``; the mean is that of
+    ``ms_ensemble`` bit for bit.  ``CH`` = K or K + 1 with K = ``num_classes``: the class arg-max runs over the first K channels, the
+    "undefined" triple (only with K + 1 channels) over all of them; the first maximum wins and a NaN takes the place and keeps it
+    (``torch.max``).  ``targets`` int64 ``[1,H,W]`` or ``[H,W]``; ``counts`` int64 ``[3K+3]`` is ADDED to (made when None) and
+    returned; ``pred`` (optional, uint8 ``[H,W]``) receives the class arg-max.  One launch (``csrc/ms_naive.hip``): neither the
+    scaled-size nor the full-resolution logits exist; a geometry ``ms_iou_supported`` declines raises.  CPU tensors, and
+    ``MAS_MS_EVAL=aten``, take the ATen chain: the materialised mean logits, then ``logits_iou_counts`` (on the CPU the reference's
+    ``torch.sum`` loops).  ``logits_iou_counts`` never lets a NaN win, so with NaN logits the two GPU paths differ."""
+    n, dev, CH, geom, H, W = _ms_sources("ms_iou_counts", logits_q, scaled_sizes, flips, out_size)
+    K = int(num_classes)
+    if not 1 <= K <= _lib.MAX_CLASSES or CH not in (K, K + 1):
+        raise ValueError("ms_iou_counts: %d channels are neither num_classes = %d (<= %d) nor num_classes + 1" % (CH, K, _lib.MAX_CLASSES))
+    if targets is None or targets.dtype != torch.int64:
+        raise TypeError("targets must be torch.int64")
+    if tuple(targets.shape[-2:]) != (H, W) or targets.numel() != H * W:
+        raise ValueError("targets %s do not match the picture %dx%d" % (tuple(targets.shape), H, W))
+    if targets.device != dev:
+        raise ValueError("targets must live on the logits' device")
+    if counts is None:
+        counts = torch.zeros(3 * K + 3, dtype=torch.int64, device=dev)
+    elif counts.dtype != torch.int64 or tuple(counts.shape) != (3 * K + 3,) or counts.device != dev:
+        raise ValueError("counts must be int64 [3K+3] = [%d] on the logits' device" % (3 * K + 3))
+    if pred is not None and (pred.dtype != torch.uint8 or pred.numel() != H * W or pred.device != dev or not pred.is_contiguous()):
+        raise ValueError("pred must be a contiguous uint8 [H,W] = [%d,%d] tensor on the logits' device" % (H, W))
+    sizes = [(int(s[0]), int(s[1])) for s in scaled_sizes]
+    if not logits_q[0].is_cuda or os.environ.get("MAS_MS_EVAL", "fused") == "aten":
+        m = _ms_mean_aten(logits_q, sizes, [bool(f) for f in flips], (H, W))
+        t = targets.reshape(1, H, W)
+        if m.is_cuda:
+            logits_iou_counts(m.contiguous(), t.contiguous(), K, int(ignore_label), counts)
+            if pred is not None:
+                pred.view(H, W).copy_(m[0, :K].max(dim=0)[1])
+        else:
+            o_cls = _iou_counts_aten(m, t, K, int(ignore_label), counts)
+            if pred is not None:
+                pred.view(H, W).copy_(o_cls[0])
+        return counts
+    if not ms_iou_supported(logits_q, sizes, flips, (H, W)):
+        raise ValueError("ms_iou_counts: a stage-2 downsample of these sources to %dx%d needs more LDS than one tile may use" % (H, W))
+    for k in range(n):
+        _need(logits_q[k], "logits_q[%d]" % k, torch.float32)
+    _need(targets, "targets", torch.int64)
+    _need(counts, "counts", torch.int64)
+    lp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in logits_q])
+    g = (ctypes.c_int32 * (5 * n))(*geom)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mas_ms_iou_counts(lp, g, n, CH, H, W, targets.data_ptr(), K, int(ignore_label), counts.data_ptr(),
+                                                 pred.data_ptr() if pred is not None else None, _stream(counts)), "mas_ms_iou_counts")
+    return counts
 
 
 # ------------------------------------------------------------------------------------------------

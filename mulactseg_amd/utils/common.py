@@ -53,6 +53,17 @@ def seed_everything(seed):
         torch.cuda.manual_seed(seed)
 
 
+def scale_factors(text):
+    """``'0.5,0.75,1.0'`` -> ``(0.5, 0.75, 1.0)``: positive, at least one."""
+    try:
+        factors = tuple(float(v) for v in str(text).split(',') if v.strip())
+    except ValueError:
+        raise argparse.ArgumentTypeError("comma-separated numbers expected, got %r" % (text,))
+    if not factors or min(factors) <= 0:
+        raise argparse.ArgumentTypeError("at least one positive scale factor expected, got %r" % (text,))
+    return factors
+
+
 def get_parser():
     p = argparse.ArgumentParser(description="MulActSeg hot path on MI355X")
     a = p.add_argument
@@ -142,6 +153,9 @@ def get_parser():
     a('--trim_kernel_size', type=int, default=3)
     a('--trim_multihot_boundary', action='store_true', default=False)
     a('--save_vis', action='store_true', default=False)  # stage-2 generators / eval_naive_vis: also write colour images
+    # eval_naive_ms: the scales of the test-time copies (comma-separated), and no flipped copies
+    a('--ms_factors', type=scale_factors, default='0.5,0.75,1.0,1.25,1.5')
+    a('--ms_noflip', action='store_true', default=False)
     a('--wandb_tags', nargs='+', default=None)
     a('--wandb_group', default=None)
     return p

@@ -8,6 +8,8 @@ on the device (``csrc/metrics.hip``) instead of 19 x 3 host-synchronising reduct
 ``LogitsIoU`` (new): both meters from one read of the logits (fused arg-max).
 ``LowresLogitsIoU`` (new): the same counters from the quarter-resolution logits (``net(x, lowres=True)``), upsampled per pixel in
 registers: the full-resolution logits never exist.
+``MultiScaleLogitsIoU`` (new): the same counters of the mean logits of scaled and flipped copies of a picture, from their
+quarter-resolution logits in one launch.
 The only host synchronisation is in ``_after_epoch`` / ``total_*`` (one copy of 3C+3 integers).
 """
 import numpy as np
@@ -149,3 +151,13 @@ class LowresLogitsIoU(LogitsIoU):
     def step_lowres(self, z_q, labels):
         ops.lowres_iou_counts(z_q.contiguous(), labels.contiguous(), labels.shape[-2:], self.num_classes, self.ignore_label,
                               self._ensure(z_q.device))
+
+
+class MultiScaleLogitsIoU(LogitsIoU):
+    """``LogitsIoU`` for multi-scale + flip evaluation: ``step_ms(logits_q, sizes, flips, labels)`` counts what ``step`` counts on the
+    mean logits of the copies (``ops.ms_ensemble``'s logits) against ``labels`` [1,H,W], from the copies' quarter-resolution logits
+    (``ops.ms_iou_counts``)."""
+
+    def step_ms(self, logits_q, sizes, flips, labels):
+        ops.ms_iou_counts([z.contiguous() for z in logits_q], sizes, flips, labels.shape[-2:], labels.contiguous(), self.num_classes,
+                          self.ignore_label, self._ensure(logits_q[0].device))
