@@ -470,7 +470,7 @@ int mas_naive_plbl(const float* logits_q, int N, int C, int h, int w, int H, int
 /* Naive arg-max pseudo labels of the VOC generators (trainer/eval_save_cosplbl_naive_voc.py:54-67, single-scale, and
  * trainer/eval_save_cosplbl_naive_voc_ms.py:55-92, multi-scale + flip) with their IoU counters, in one launch per picture.  Sources as
  * mas_ms_ensemble's logits: n <= MAS_MS_MAX_SOURCES, logits_q[k] f32 [C,hq,wq], geometry[5k..5k+4] = (hq, wq, Hs, Ws, flip) with the
- * same rules (MAS_ERR_SHAPE otherwise).  Per pixel and channel the source values of mas_ms_ensemble (bit for bit), summed in source
+ * same rules (MAS_ERR_SHAPE otherwise).  Per pixel and channel the source values of mas_ms_ensemble (bit for bit: one code, csrc/ms_tile.h), summed in source
  * order, m = sum / (float)n; labels u8 [H,W] = the first arg-max of m over the C channels (a NaN wins where it first appears, as
  * torch.max), i.e. torch.max(mas_ms_ensemble's logit_out, 1)[1]; n = 1 with the geometry (hq, wq, H, W, 0) gives the arg-max of
  * mas_upsample_bilinear_fwd's output.  counts (optional, int64 [3K+3] with K = num_classes, the layout of mas_iou_counts without the

@@ -36,15 +36,6 @@ struct PlblArgs {
     int vec_ok;                   // mask and labels are 4-byte aligned and W % 4 == 0: 32-bit mask loads and label stores
 };
 
-// first maximum wins; a NaN replaces a number and is never replaced (torch.max)
-__device__ __forceinline__ void arg_update(float v, int c, float& best, int& idx) {
-    if (best != best) return;
-    if (v > best || v != v) {
-        best = v;
-        idx = c;
-    }
-}
-
 __device__ __forceinline__ void store4(unsigned char* dst, const unsigned char (&v)[kPix], int n, bool vec) {
     if (vec) {
         *reinterpret_cast<unsigned*>(dst) = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);

@@ -5,26 +5,14 @@
 // gradient into four inputs with float atomics: 1.1 ms for the [4,20,768,768] logit gradient and a result whose last bits
 // depend on the atomic order.  Here every INPUT pixel gathers the <= ~(2/scale + 3)^2 outputs that touch it, in a fixed
 // order (rows ascending, columns ascending): one read of the gradient (L2 serves the 4x reuse), no atomics, bit-identical
-// from run to run.  Index / weight arithmetic is ATen's (area_pixel_compute_source_index): src = max(0, s*(o+0.5)-0.5),
+// from run to run.  Index / weight arithmetic (upsample_tap.h) is ATen's (area_pixel_compute_source_index): src = max(0, s*(o+0.5)-0.5),
 // i0 = (int)src, i1 = i0 + (i0 < n-1), l1 = src - i0, l0 = 1 - l1;  y = l0h*(l0w*v00 + l1w*v01) + l1h*(l0w*v10 + l1w*v11).
 #include "common.h"
+#include "upsample_tap.h"
 
 namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxTaps = 16;
-
-struct Tap { int i0, i1; float l0, l1; };
-
-__device__ __forceinline__ Tap make_tap(float scale, int o, int n_in) {
-    float s = scale * ((float)o + 0.5f) - 0.5f;
-    s = s < 0.0f ? 0.0f : s;
-    Tap t;
-    t.i0 = (int)s;
-    t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
-    t.l1 = s - (float)t.i0;
-    t.l0 = 1.0f - t.l1;
-    return t;
-}
 
 // grid: (ceil(Wo / (4*256)), Ho, NC); a thread writes four consecutive outputs of one row
 __global__ __launch_bounds__(kThreads) void k_upsample_fwd(const float* __restrict__ x, int Hi, int Wi, int Ho, int Wo, float sh, float sw,

@@ -1,5 +1,7 @@
 // upsample_tap.h -- the bilinear tap of k_upsample_fwd (upsample.hip) for kernels that upsample quarter-resolution maps in registers
-// (naive_plbl.hip, lowres_iou.hip), and the host computation of a tile's quarter-resolution footprint.
+// (naive_plbl.hip, lowres_iou.hip) or in LDS (ms_tile.h), the host computation of a tile's quarter-resolution footprint, and the
+// arg-max rule of the label kernels (naive_plbl.hip, ms_naive.hip).  upsample.hip itself includes it: one copy of the arithmetic every
+// bit-exactness claim of this family rests on.
 //
 // Tap (F.interpolate, bilinear, align_corners=False): s = max(scale * (o + 0.5) - 0.5, 0), i0 = (int)s, i1 = i0 + (i0 < n_in - 1),
 // l1 = s - i0, l0 = 1 - l1, with scale = (float)n_in / (float)n_out computed on the host.  A value is then
@@ -18,6 +20,16 @@ __host__ __device__ __forceinline__ Tap make_tap(float scale, int o, int n_in) {
     t.l1 = s - (float)t.i0;
     t.l0 = 1.0f - t.l1;
     return t;
+}
+
+// torch.max over the channels, walked in channel order from best = channel 0's value, idx = 0: the first maximum wins; a NaN replaces
+// a number and is never replaced.
+__device__ __forceinline__ void arg_update(float v, int c, float& best, int& idx) {
+    if (best != best) return;
+    if (v > best || v != v) {
+        best = v;
+        idx = c;
+    }
 }
 
 // Extents of the quarter-resolution footprint of a tile_h x tile_w output tile: the exact maxima over the tiles of an H x W output of

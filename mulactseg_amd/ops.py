@@ -1012,44 +1012,11 @@ def ms_ensemble(feats_q, logits_q, scaled_sizes, flips, out_size):
     network on a picture scaled to ``scaled_sizes[k] = (Hs, Ws)`` and flipped horizontally when ``flips[k]``.  -> (features
     [1,Ch,H,W] unit-norm per pixel, logits [1,C,H,W]) at ``out_size = (H, W)``: upsampled x4 to the scaled size, flipped back, resized
     to (H, W), averaged; the features re-normalised over the channels.  The scaled-size maps never exist in memory."""
-    n = len(feats_q)
-    if not 1 <= n <= _lib.MS_MAX_SOURCES:
-        raise ValueError("ms_ensemble takes 1 .. %d sources, got %d" % (_lib.MS_MAX_SOURCES, n))
-    if len(logits_q) != n or len(scaled_sizes) != n or len(flips) != n:
-        raise ValueError("feats_q, logits_q, scaled_sizes and flips must have one entry per source")
-    H, W = int(out_size[0]), int(out_size[1])
-    if H < 1 or W < 1:
-        raise ValueError("out_size must be non-empty, got %r" % (tuple(out_size),))
-    dev = feats_q[0].device
-    Ch, C = None, None
-    geom = []
-    for k in range(n):
-        f, z = feats_q[k], logits_q[k]
-        _need(f, "feats_q[%d]" % k, torch.float32)
-        _need(z, "logits_q[%d]" % k, torch.float32)
-        if f.device != dev or z.device != dev:
-            raise ValueError("all sources must live on one device")
-        if f.dim() != 4 or z.dim() != 4 or f.shape[0] != 1 or z.shape[0] != 1:
-            raise ValueError("source %d: features and logits must be [1,Ch,hq,wq] / [1,C,hq,wq]" % k)
-        if Ch is None:
-            Ch, C = int(f.shape[1]), int(z.shape[1])
-        if f.shape[1] != Ch or z.shape[1] != C:
-            raise ValueError("source %d: channel counts differ from source 0" % k)
-        hq, wq = int(f.shape[2]), int(f.shape[3])
-        if tuple(z.shape[2:]) != (hq, wq):
-            raise ValueError("source %d: features %s and logits %s differ in size" % (k, tuple(f.shape), tuple(z.shape)))
-        Hs, Ws = int(scaled_sizes[k][0]), int(scaled_sizes[k][1])
-        if Hs < 1 or Ws < 1:
-            raise ValueError("source %d: empty scaled size %dx%d" % (k, Hs, Ws))
-        if (hq, wq) != (quarter_size(Hs), quarter_size(Ws)):
-            raise ValueError("source %d: quarter-resolution maps %dx%d are not what the network emits for %dx%d (%dx%d)"
-                             % (k, hq, wq, Hs, Ws, quarter_size(Hs), quarter_size(Ws)))
-        geom += [hq, wq, Hs, Ws, 1 if flips[k] else 0]
+    n, dev, C, geom, H, W = _ms_sources("ms_ensemble", logits_q, scaled_sizes, flips, out_size, feats_q)
+    Ch = int(feats_q[0].shape[1])
+    g, fp, lp = _ms_pack(geom, feats_q=feats_q, logits_q=logits_q)
     feat = torch.empty((1, Ch, H, W), dtype=torch.float32, device=dev)
     logit = torch.empty((1, C, H, W), dtype=torch.float32, device=dev)
-    fp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in feats_q])
-    lp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in logits_q])
-    g = (ctypes.c_int32 * (5 * n))(*geom)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().mas_ms_ensemble(fp, lp, g, n, Ch, C, H, W, feat.data_ptr(), logit.data_ptr(), _stream(feat)),
                    "mas_ms_ensemble")
@@ -1136,40 +1103,65 @@ def _ms_mean_aten(logits_q, sizes, flips, out_size):
     return acc / len(logits_q)
 
 
-def _ms_sources(name, logits_q, scaled_sizes, flips, out_size):
-    """The argument checks the multi-scale ops share -> (n, device, C, the [n,5] geometry table as a flat list, H, W)."""
+def _ms_sources(name, logits_q, scaled_sizes, flips, out_size, feats_q=None):
+    """The argument checks the multi-scale ops share -> (n, device, C, the [n,5] geometry table as a flat list, H, W).  ``feats_q``
+    (``ms_ensemble``): a second tensor per source, ``[1,Ch,hq,wq]``, held to the same rules and to the size of its logits."""
     n = len(logits_q)
     if not 1 <= n <= _lib.MS_MAX_SOURCES:
         raise ValueError("%s takes 1 .. %d sources, got %d" % (name, _lib.MS_MAX_SOURCES, n))
-    if len(scaled_sizes) != n or len(flips) != n:
-        raise ValueError("logits_q, scaled_sizes and flips must have one entry per source")
+    lists = [("logits_q", logits_q)] + ([] if feats_q is None else [("feats_q", feats_q)])
+    if len(scaled_sizes) != n or len(flips) != n or any(len(ts) != n for _, ts in lists):
+        raise ValueError("%s, scaled_sizes and flips must have one entry per source" % ", ".join(what for what, _ in lists))
     H, W = int(out_size[0]), int(out_size[1])
     if H < 1 or W < 1:
         raise ValueError("out_size must be non-empty, got %r" % (tuple(out_size),))
     dev = logits_q[0].device
-    C = None
     geom = []
     for k in range(n):
-        z = logits_q[k]
-        if z.device != dev:
-            raise ValueError("all sources must live on one device")
-        if z.dtype != torch.float32:
-            raise TypeError("logits_q[%d] must be torch.float32, got %s" % (k, z.dtype))
-        if z.dim() != 4 or z.shape[0] != 1:
-            raise ValueError("source %d: logits must be [1,C,hq,wq], got %s" % (k, tuple(z.shape)))
-        if C is None:
-            C = int(z.shape[1])
-        if z.shape[1] != C:
-            raise ValueError("source %d: channel count differs from source 0" % k)
-        hq, wq = int(z.shape[2]), int(z.shape[3])
+        for what, ts in lists:
+            z = ts[k]
+            if z.device != dev:
+                raise ValueError("all sources must live on one device")
+            if z.dtype != torch.float32:
+                raise TypeError("%s[%d] must be torch.float32, got %s" % (what, k, z.dtype))
+            if z.dim() != 4 or z.shape[0] != 1:
+                raise ValueError("source %d: %s must be [1,C,hq,wq], got %s" % (k, what, tuple(z.shape)))
+            if z.shape[1] != ts[0].shape[1]:
+                raise ValueError("source %d: channel count of %s differs from source 0" % (k, what))
+            if z.shape[2:] != logits_q[k].shape[2:]:
+                raise ValueError("source %d: %s %s and logits_q %s differ in size" % (k, what, tuple(z.shape), tuple(logits_q[k].shape)))
+        hq, wq = int(logits_q[k].shape[2]), int(logits_q[k].shape[3])
         Hs, Ws = int(scaled_sizes[k][0]), int(scaled_sizes[k][1])
         if Hs < 1 or Ws < 1:
             raise ValueError("source %d: empty scaled size %dx%d" % (k, Hs, Ws))
         if (hq, wq) != (quarter_size(Hs), quarter_size(Ws)):
-            raise ValueError("source %d: quarter-resolution logits %dx%d are not what the network emits for %dx%d (%dx%d)"
+            raise ValueError("source %d: quarter-resolution maps %dx%d are not what the network emits for %dx%d (%dx%d)"
                              % (k, hq, wq, Hs, Ws, quarter_size(Hs), quarter_size(Ws)))
         geom += [hq, wq, Hs, Ws, 1 if flips[k] else 0]
-    return n, dev, C, geom, H, W
+    return n, dev, int(logits_q[0].shape[1]), geom, H, W
+
+
+def _ms_targets_counts(targets, counts, K, H, W, dev):
+    """The checks ``ms_naive_labels`` and ``ms_iou_counts`` share on ``targets`` (int64, H * W elements ending in ``[H,W]``) and
+    ``counts`` (int64 ``[3K+3]``), both on the logits' device; either may be None."""
+    if targets is not None:
+        if targets.dtype != torch.int64:
+            raise TypeError("targets must be torch.int64, got %s" % targets.dtype)
+        if tuple(targets.shape[-2:]) != (H, W) or targets.numel() != H * W:
+            raise ValueError("targets %s do not match the picture %dx%d" % (tuple(targets.shape), H, W))
+        if targets.device != dev:
+            raise ValueError("targets must live on the logits' device")
+    if counts is not None and (counts.dtype != torch.int64 or tuple(counts.shape) != (3 * K + 3,) or counts.device != dev):
+        raise ValueError("counts must be int64 [3K+3] = [%d] on the logits' device" % (3 * K + 3))
+
+
+def _ms_pack(geom, **tensor_lists):
+    """-> [the ``(c_int32 * 5n)`` geometry table, one ``(c_void_p * n)`` pointer array per tensor list]; the tensors must be contiguous
+    f32 on the GPU."""
+    out = [(ctypes.c_int32 * len(geom))(*geom)]
+    for name, ts in tensor_lists.items():
+        out.append((ctypes.c_void_p * len(ts))(*[_need(t, "%s[%d]" % (name, k), torch.float32).data_ptr() for k, t in enumerate(ts)]))
+    return out
 
 
 def ms_naive_labels(logits_q, scaled_sizes, flips, out_size, targets=None, counts=None, num_classes=None, ignore_label=255):
@@ -1191,16 +1183,7 @@ def ms_naive_labels(logits_q, scaled_sizes, flips, out_size, targets=None, count
     K = None if num_classes is None else int(num_classes)
     if counts is not None and not C <= K <= _lib.MAX_CLASSES:
         raise ValueError("num_classes %d must be within [%d, %d] (the channels .. MAX_CLASSES)" % (K, C, _lib.MAX_CLASSES))
-    if targets is not None:
-        if targets.dtype != torch.int64:
-            raise TypeError("targets must be torch.int64, got %s" % targets.dtype)
-        if tuple(targets.shape[-2:]) != (H, W) or targets.numel() != H * W:
-            raise ValueError("targets %s do not match the picture %dx%d" % (tuple(targets.shape), H, W))
-        if targets.device != dev:
-            raise ValueError("targets must live on the logits' device")
-    if counts is not None:
-        if counts.dtype != torch.int64 or tuple(counts.shape) != (3 * K + 3,) or counts.device != dev:
-            raise ValueError("counts must be int64 [3K+3] = [%d] on the logits' device" % (3 * K + 3))
+    _ms_targets_counts(targets, counts, K, H, W, dev)
     sizes = [(int(s[0]), int(s[1])) for s in scaled_sizes]
     if not logits_q[0].is_cuda or os.environ.get("MAS_MS_NAIVE", "fused") == "aten":
         labels = _ms_mean_aten(logits_q, sizes, [bool(f) for f in flips], (H, W)).max(dim=1)[1]
@@ -1211,14 +1194,11 @@ def ms_naive_labels(logits_q, scaled_sizes, flips, out_size, targets=None, count
             else:
                 _meaniou_counts_aten(labels, t, K, int(ignore_label), counts)
         return labels
-    for k in range(n):
-        _need(logits_q[k], "logits_q[%d]" % k, torch.float32)
+    g, lp = _ms_pack(geom, logits_q=logits_q)
     if counts is not None:
         _need(counts, "counts", torch.int64)
         _need(targets, "targets", torch.int64)
     out = torch.empty((1, H, W), dtype=torch.uint8, device=dev)
-    lp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in logits_q])
-    g = (ctypes.c_int32 * (5 * n))(*geom)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().mas_ms_naive_plbl(lp, g, n, C, H, W, targets.data_ptr() if counts is not None else None,
                                                  K if counts is not None else 0, int(ignore_label), out.data_ptr(),
@@ -1229,30 +1209,23 @@ def ms_naive_labels(logits_q, scaled_sizes, flips, out_size, targets=None, count
 MS_MAX_LDS = 64 * 1024      # the LDS one workgroup of csrc/ms_naive.hip may use
 
 
-def _ms_geometry(logits_q, scaled_sizes, flips):
-    return [v for z, s, f in zip(logits_q, scaled_sizes, flips)
-            for v in (int(z.shape[-2]), int(z.shape[-1]), int(s[0]), int(s[1]), 1 if f else 0)]
-
-
 def ms_iou_lds_bytes(geometry, out_size):
     """The LDS one workgroup of ``mas_ms_iou_counts`` needs for the flat ``[n,5]`` geometry table ``(hq, wq, Hs, Ws, flip)`` and
     ``out_size`` -- the launch's own sizing code (``mas_ms_iou_lds_bytes``; no device is touched) -- or a negative status."""
-    n = len(geometry) // 5
-    g = (ctypes.c_int32 * (5 * n))(*[int(v) for v in geometry])
-    return int(_lib.load().mas_ms_iou_lds_bytes(g, n, int(out_size[0]), int(out_size[1])))
+    g, = _ms_pack([int(v) for v in geometry])
+    return int(_lib.load().mas_ms_iou_lds_bytes(g, len(g) // 5, int(out_size[0]), int(out_size[1])))
 
 
 def ms_iou_supported(logits_q, scaled_sizes, flips, out_size):
-    """True on GPU tensors when ``mas_ms_iou_counts`` accepts the sources: 1 .. 16 of them, each an upsampling to its scaled size, and a
-    stage-2 downsample whose tile fits the LDS (factors up to 2.0 do), by the entry point's own sizing code."""
-    n = len(logits_q)
-    if not 1 <= n <= _lib.MS_MAX_SOURCES or len(scaled_sizes) != n or len(flips) != n:
+    """True on GPU tensors when ``ms_iou_counts`` accepts the sources: 1 .. 16 of them, each what the network emits for its scaled size,
+    and a stage-2 downsample whose tile fits the LDS (factors up to 2.0 do), by the entry point's own sizing code."""
+    if not all(torch.is_tensor(z) and z.is_cuda for z in logits_q):
         return False
-    if not all(torch.is_tensor(z) and z.is_cuda and z.dim() == 4 for z in logits_q):
+    try:
+        _, _, _, geom, H, W = _ms_sources("ms_iou_supported", logits_q, scaled_sizes, flips, out_size)
+    except (TypeError, ValueError):
         return False
-    if int(out_size[0]) < 1 or int(out_size[1]) < 1:
-        return False
-    return 0 <= ms_iou_lds_bytes(_ms_geometry(logits_q, scaled_sizes, flips), out_size) <= MS_MAX_LDS
+    return 0 <= ms_iou_lds_bytes(geom, (H, W)) <= MS_MAX_LDS
 
 
 def _iou_counts_aten(m, targets, K, ignore_label, counts):
@@ -1283,16 +1256,11 @@ def ms_iou_counts(logits_q, scaled_sizes, flips, out_size, targets, num_classes,
     K = int(num_classes)
     if not 1 <= K <= _lib.MAX_CLASSES or CH not in (K, K + 1):
         raise ValueError("ms_iou_counts: %d channels are neither num_classes = %d (<= %d) nor num_classes + 1" % (CH, K, _lib.MAX_CLASSES))
-    if targets is None or targets.dtype != torch.int64:
+    if targets is None:
         raise TypeError("targets must be torch.int64")
-    if tuple(targets.shape[-2:]) != (H, W) or targets.numel() != H * W:
-        raise ValueError("targets %s do not match the picture %dx%d" % (tuple(targets.shape), H, W))
-    if targets.device != dev:
-        raise ValueError("targets must live on the logits' device")
+    _ms_targets_counts(targets, counts, K, H, W, dev)
     if counts is None:
         counts = torch.zeros(3 * K + 3, dtype=torch.int64, device=dev)
-    elif counts.dtype != torch.int64 or tuple(counts.shape) != (3 * K + 3,) or counts.device != dev:
-        raise ValueError("counts must be int64 [3K+3] = [%d] on the logits' device" % (3 * K + 3))
     if pred is not None and (pred.dtype != torch.uint8 or pred.numel() != H * W or pred.device != dev or not pred.is_contiguous()):
         raise ValueError("pred must be a contiguous uint8 [H,W] = [%d,%d] tensor on the logits' device" % (H, W))
     sizes = [(int(s[0]), int(s[1])) for s in scaled_sizes]
@@ -1308,14 +1276,11 @@ def ms_iou_counts(logits_q, scaled_sizes, flips, out_size, targets, num_classes,
             if pred is not None:
                 pred.view(H, W).copy_(o_cls[0])
         return counts
-    if not ms_iou_supported(logits_q, sizes, flips, (H, W)):
+    if not 0 <= ms_iou_lds_bytes(geom, (H, W)) <= MS_MAX_LDS:
         raise ValueError("ms_iou_counts: a stage-2 downsample of these sources to %dx%d needs more LDS than one tile may use" % (H, W))
-    for k in range(n):
-        _need(logits_q[k], "logits_q[%d]" % k, torch.float32)
+    g, lp = _ms_pack(geom, logits_q=logits_q)
     _need(targets, "targets", torch.int64)
     _need(counts, "counts", torch.int64)
-    lp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in logits_q])
-    g = (ctypes.c_int32 * (5 * n))(*geom)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().mas_ms_iou_counts(lp, g, n, CH, H, W, targets.data_ptr(), K, int(ignore_label), counts.data_ptr(),
                                                  pred.data_ptr() if pred is not None else None, _stream(counts)), "mas_ms_iou_counts")

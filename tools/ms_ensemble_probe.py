@@ -50,7 +50,8 @@ def aten_chain(feats_q, logits_q, sizes, flips, size):
     return F.normalize(feats / n, dim=1), outs / n
 
 
-def timed(fn, reps, warmup=2):
+def timed(fn, reps, warmup=2, spread=False):
+    """Median (ms) of fn over reps, by device events; spread: (median, [min, max])."""
     import torch
     for _ in range(warmup):
         fn()
@@ -62,7 +63,7 @@ def timed(fn, reps, warmup=2):
         b.record()
         b.synchronize()
         ts.append(a.elapsed_time(b))
-    return float(np.median(ts))
+    return (float(np.median(ts)), [float(np.min(ts)), float(np.max(ts))]) if spread else float(np.median(ts))
 
 
 def main():
@@ -107,9 +108,10 @@ def main():
             targets = torch.from_numpy((trs.uniform(size=(S, 22)) < 0.15).astype(np.uint8)).cuda()
             spmask = torch.from_numpy(trs.uniform(size=S) < 0.5).cuda()[spx]
             k9 = lambda: ops.stage2_pseudo_labels(f1, z1.contiguous(), targets[None], spmask[None], spx[None], True)   # noqa: E731
+            fused_ms, fused_span = timed(fused, args.reps, spread=True)
             row = {'picture': '%dx%d' % (W, H), 'tta_ms': timed(lambda: tta(pic), args.reps),
                    'forwards_ms': timed(lambda: [net.feat_forward_quarter(im[None]) for im in images], args.reps),
-                   'ensemble_fused_ms': timed(fused, args.reps), 'ensemble_aten_ms': timed(aten, args.reps), 'k9_ms': timed(k9, args.reps)}
+                   'ensemble_fused_ms': fused_ms, 'ensemble_fused_ms_min_max': fused_span, 'ensemble_aten_ms': timed(aten, args.reps), 'k9_ms': timed(k9, args.reps)}
             plbl = k9()
             t = []
             for _ in range(args.reps):

@@ -38,7 +38,8 @@ def byte_floor(sizes, C, H, W):
     return 4 * q + 8 * H * W + H * W
 
 
-def timed(fn, reps, warmup=2):
+def timed(fn, reps, warmup=2, spread=False):
+    """Median (ms) of fn over reps, by device events; spread: (median, [min, max])."""
     import torch
     for _ in range(warmup):
         fn()
@@ -50,7 +51,7 @@ def timed(fn, reps, warmup=2):
         b.record()
         b.synchronize()
         ts.append(a.elapsed_time(b))
-    return float(np.median(ts))
+    return (float(np.median(ts)), [float(np.min(ts)), float(np.max(ts))]) if spread else float(np.median(ts))
 
 
 class _Loader:
@@ -145,9 +146,10 @@ def main():
             top = torch.topk(m, 2, dim=1)[0]
             gap = top[:, 0] - top[:, 1]
             differ = l1 != l0
+            fused_ms, fused_span = timed(fused, args.reps, spread=True)
             row = {'picture': '%dx%d' % (W, H),
                    'forwards_ms': timed(lambda: [net(im[None], lowres=True) for im in images], args.reps),
-                   'fused_ms': timed(fused, args.reps), 'aten_ms': timed(aten, args.reps), 'ensemble_argmax_count_ms': timed(ensemble, args.reps),
+                   'fused_ms': fused_ms, 'fused_ms_min_max': fused_span, 'aten_ms': timed(aten, args.reps), 'ensemble_argmax_count_ms': timed(ensemble, args.reps),
                    'fused_equals_ensemble_argmax': bool(torch.equal(l1, le)),
                    'fused_vs_aten_labels_differ': int(differ.sum()), 'fused_vs_aten_max_gap_where_differ': float(gap[differ].max()) if bool(differ.any()) else 0.0}
             t = []
