@@ -400,6 +400,20 @@ int mas_stage2_propagate(const float* feat, int Ch, int fh, int fw, int H, int W
                          const int32_t* proto_start, const int32_t* proto_cls, const float* P, const float* thr,
                          const int32_t* nn_proto, int64_t* out, void* stream);
 
+/* thr [n_proto] between mas_stage2_assign and mas_stage2_propagate (:243-254, --cosprop_threshold_method): over the similarities
+ * {nn_sim[i] : nn_proto[i] == k} of the pixels prototype k attracted, the smallest (MIN) or the lower median, the element of rank
+ * (cnt - 1) / 2 in ascending order (MEDIAN); 1.0 for a prototype without pixels.  Pixels with nn_proto < 0 (or >= n_proto) take no
+ * part.  The result is one of the input floats, picked by rank on integer keys of sim + 0.0f (-0.0 and +0.0 are one value; NaNs
+ * order by their bits): integer atomics only, the same bytes on every run, no sort and no host synchronisation.
+ * scratch: mas_stage2_thresholds_scratch_bytes(n_proto, method) bytes, 16-byte aligned (MAS_ERR_ALIGN), contents ignored and
+ * overwritten (MAS_ERR_WORKSPACE when smaller).  An unknown method is MAS_ERR_SHAPE (the size query returns it too);
+ * n_proto < 1 or >= 2^23 is MAS_ERR_RANGE.  Nothing is launched when an argument is refused. */
+#define MAS_STAGE2_THR_MEDIAN 0
+#define MAS_STAGE2_THR_MIN 1
+int64_t mas_stage2_thresholds_scratch_bytes(int n_proto, int method);
+int mas_stage2_thresholds(const int32_t* nn_proto, const float* nn_sim, int HW, int n_proto, int method, void* scratch,
+                          int64_t scratch_bytes, float* thr, void* stream);
+
 /* =============================================================================================
  * K7  ASPP: the three dilated depthwise 3x3 convolutions from one read of the feature map
  * (models/segmentation/deeplabv3.py:168-201,216-245 after convert_to_separable_conv :249-261; dilations 6/12/18 at

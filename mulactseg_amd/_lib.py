@@ -22,6 +22,7 @@ MS_MAX_SOURCES = 16
 
 SK_DMA, SK_NOSPLIT = 1, 2
 LOWRES_GENERIC = 1
+STAGE2_THR_MEDIAN, STAGE2_THR_MIN = 0, 1
 ABI_VERSION = 9        # MAS_ABI_VERSION of include/mulactseg_hip.h this table was written against (load() refuses any other library)
 
 _c = ctypes
@@ -64,6 +65,8 @@ SIGNATURES = {
     "mas_stage2_assign": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "mas_stage2_adjacency": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "mas_stage2_propagate": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mas_stage2_thresholds_scratch_bytes": (_i64, [_i, _i]),
+    "mas_stage2_thresholds": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
     "mas_aspp_dw3_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mas_aspp_dw3_bwd_x": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "mas_aspp_dw3_bwd_w": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

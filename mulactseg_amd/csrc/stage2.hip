@@ -11,6 +11,9 @@
 //   * k_stage2_propagate   every pixel looks at the valid superpixels adjacent to its own superpixel in ascending id
 //                          order; the last one whose prototype similarity passes that prototype's threshold wins --
 //                          exactly the result of the reference's sequential overwrite.
+//   * k_s2thr_*            per-prototype threshold between assign and propagate: the minimum or the lower median of the
+//                          similarities of the pixels a prototype attracted, picked by rank on integer keys (no sort,
+//                          no arithmetic on the similarities but sim + 0.0f, integer atomics only).
 // Dot products are sequential fma chains over the channels (normative, mirrored by oracle/exact.c).
 #include "common.h"
 
@@ -164,6 +167,149 @@ __global__ __launch_bounds__(kThreads) void k_stage2_propagate(FeatMap m, const 
     if (own >= 0) label = p_cls[own];
     out[i] = label;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Per-prototype thresholds (trainer/eval_save_cosplbl_prop.py:243-254): thr[k] over {nn_sim[i] : nn_proto[i] == k}.
+// Similarities are ordered by the monotone 32-bit key of sim + 0.0f (-0.0 and +0.0 are one key): negatives with all
+// bits flipped, non-negatives with the sign bit set.  The result is the float whose key was picked.
+//   min:    atomicMin on the key.
+//   median: 4 x 8-bit radix select of the key of rank (cnt - 1) / 2.  Per prototype the state is {prefix, rank}; a round
+//           counts, per prototype, the next digit of the keys that share the prefix found so far (k_s2thr_hist), then
+//           one wave per prototype scans the 256 bins, appends the digit that holds the rank, takes the bins below it
+//           off the rank and zeroes the bins for the next round (k_s2thr_pick).  The first round matches every key, so
+//           its bins also give cnt.
+// Neighbouring pixels mostly share prototype and digit (round 0 hits a handful of bins: similarities lie in a narrow
+// band), so a wave first merges its lanes on the bin and one lane adds the count; lanes left after kMergeRounds
+// distinct bins add on their own.
+// ------------------------------------------------------------------------------------------------
+constexpr int kMergeRounds = 4;
+constexpr unsigned kNoKey = 0xffffffffu;       // min: no pixel yet; median: rank of a prototype without pixels
+// min: one key per 128-byte line.  Packed, the ~500 keys of a picture share 18 lines and every wave's atomic queues on one of them
+// (42 us for the 2 M pixels of a 1024 x 2048 picture); a line each, and a coherent read that skips what cannot lower the key: 15 us.
+constexpr int kMinStride = 32;
+
+__device__ __forceinline__ unsigned sim_key(float v) {
+    const unsigned u = mas_f2u(v + 0.0f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float key_sim(unsigned key) {
+    return mas_u2f((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+
+// state [n_proto] {prefix, rank} = {0, 0}; hist [n_proto * 256] = 0   (median)  /  keys [n_proto * kMinStride] = kNoKey   (min)
+__global__ __launch_bounds__(kThreads) void k_s2thr_init(unsigned* __restrict__ words, long long n, unsigned value) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) words[i] = value;
+}
+
+// merged(same, writer, s): for up to kMergeRounds distinct slots s of the wave, `same` marks the lanes that hold s and `writer` one
+// of them; called by every lane of the wave (so the caller returns from no lane before this, and merged() may use wave operations).
+// single(): called by the lanes whose slot was not served, each for itself.
+template <typename Merged, typename Single>
+__device__ __forceinline__ void wave_merge(bool todo, int slot, Merged merged, Single single) {
+    const int lane = threadIdx.x & (MAS_WAVE - 1);
+    for (int r = 0; r < kMergeRounds; ++r) {
+        const mas_u64 open = __ballot(todo);
+        if (!open) return;
+        const int leader = __ffsll((long long)open) - 1;
+        const int s = __shfl(slot, leader);
+        const bool same = todo && slot == s;
+        merged(same, lane == leader, s);
+        todo = todo && !same;
+    }
+    if (todo) single();
+}
+
+__global__ __launch_bounds__(kThreads) void k_s2thr_min(const int* __restrict__ nn, const float* __restrict__ nn_sim, int HW,
+                                                         int n_proto, unsigned* __restrict__ keys) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    int k = -1;
+    unsigned key = kNoKey;
+    if (i < HW) {
+        k = nn[i];
+        if (k >= 0 && k < n_proto) key = sim_key(nn_sim[i]);
+        else k = -1;
+    }
+    wave_merge(k >= 0, k, [&](bool same, bool writer, int s) {
+        unsigned m = same ? key : kNoKey;
+#pragma unroll
+        for (int d = 1; d < MAS_WAVE; d <<= 1) {
+            const unsigned o = (unsigned)__shfl_xor((int)m, d);
+            m = o < m ? o : m;
+        }
+        // (keys only go down: an old value read here costs an atomic, never a result)
+        if (writer && m < __hip_atomic_load(&keys[(size_t)s * kMinStride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            atomicMin(&keys[(size_t)s * kMinStride], m);
+    }, [&]() { atomicMin(&keys[(size_t)k * kMinStride], key); });
+}
+
+__global__ __launch_bounds__(kThreads) void k_s2thr_min_out(const unsigned* __restrict__ keys, int n_proto, float* __restrict__ thr) {
+    const int k = blockIdx.x * kThreads + threadIdx.x;
+    if (k < n_proto) {
+        const unsigned key = keys[(size_t)k * kMinStride];
+        thr[k] = key == kNoKey ? 1.0f : key_sim(key);
+    }
+}
+
+// round with digit at bit `shift` (24, 16, 8, 0): hist[k][digit] += 1 for every pixel of k whose key continues k's prefix
+__global__ __launch_bounds__(kThreads) void k_s2thr_hist(const int* __restrict__ nn, const float* __restrict__ nn_sim, int HW,
+                                                          int n_proto, int shift, const uint2* __restrict__ state,
+                                                          unsigned* __restrict__ hist) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    int slot = -1;
+    if (i < HW) {
+        const int k = nn[i];
+        if (k >= 0 && k < n_proto) {
+            const unsigned key = sim_key(nn_sim[i]);
+            // (shift == 24: no digit is fixed yet.  A prototype without pixels is never looked up here.)
+            if (shift == 24 || ((key ^ state[k].x) >> (shift + 8)) == 0) slot = k * 256 + (int)((key >> shift) & 255u);
+        }
+    }
+    wave_merge(slot >= 0, slot, [&](bool same, bool writer, int s) {
+        const mas_u64 m = __ballot(same);
+        if (writer) atomicAdd(&hist[s], (unsigned)__popcll(m));
+    }, [&]() { atomicAdd(&hist[slot], 1u); });
+}
+
+// one wave per prototype: lane l owns bins 4 l .. 4 l + 3
+__global__ __launch_bounds__(MAS_WAVE) void k_s2thr_pick(int shift, uint2* __restrict__ state, unsigned* __restrict__ hist,
+                                                          float* __restrict__ thr) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    uint4* bins = reinterpret_cast<uint4*>(hist + (size_t)k * 256) + lane;
+    const uint4 b = *bins;
+    *bins = make_uint4(0u, 0u, 0u, 0u);
+    const unsigned own = b.x + b.y + b.z + b.w;
+    unsigned upto = own;                                        // inclusive scan over the lanes
+#pragma unroll
+    for (int d = 1; d < MAS_WAVE; d <<= 1) {
+        const unsigned o = (unsigned)__shfl_up((int)upto, d);
+        if (lane >= d) upto += o;
+    }
+    uint2 st = state[k];
+    if (shift == 24) {
+        const unsigned cnt = (unsigned)__shfl((int)upto, MAS_WAVE - 1);
+        st.y = cnt ? (cnt - 1u) / 2u : kNoKey;
+    }
+    if (st.y == kNoKey) {                                       // no pixel: 1.0 (:245)
+        if (lane == 0) {
+            if (shift == 24) state[k] = st;
+            if (shift == 0) thr[k] = 1.0f;
+        }
+        return;
+    }
+    const unsigned below = upto - own;
+    if (st.y >= below && st.y < upto) {                         // exactly one lane: the bins up to it hold the rank, those before do not
+        unsigned r = st.y - below, digit = 4u * (unsigned)lane;
+        if (r >= b.x) { r -= b.x; ++digit;
+            if (r >= b.y) { r -= b.y; ++digit;
+                if (r >= b.z) { r -= b.z; ++digit; } } }
+        st.x |= digit << shift;
+        st.y = r;
+        state[k] = st;
+        if (shift == 0) thr[k] = key_sim(st.x);
+    }
+}
 }  // namespace
 
 static int stage2_check(const float* feat, int Ch, int fh, int fw, int H, int W) {
@@ -210,5 +356,46 @@ extern "C" int mas_stage2_propagate(const float* feat, int Ch, int fh, int fw, i
     hipLaunchKernelGGL(k_stage2_propagate, dim3((unsigned)((H * W + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        static_cast<hipStream_t>(stream), (FeatMap{feat, Ch, fh, fw, H, W}), reinterpret_cast<const long long*>(spx), S, adj,
                        proto_start, proto_cls, P, thr, nn_proto, reinterpret_cast<long long*>(out));
+    return mas_launch_status();
+}
+
+static int64_t thresholds_words(int n_proto, int method) {
+    if (n_proto <= 0 || n_proto > (0x7fffffff >> 8)) return MAS_ERR_RANGE;
+    if (method == MAS_STAGE2_THR_MIN) return (int64_t)n_proto * kMinStride;
+    if (method == MAS_STAGE2_THR_MEDIAN) return (int64_t)n_proto * (256 + 2);
+    return MAS_ERR_SHAPE;
+}
+
+extern "C" int64_t mas_stage2_thresholds_scratch_bytes(int n_proto, int method) {
+    const int64_t w = thresholds_words(n_proto, method);
+    return w < 0 ? w : w * 4;
+}
+
+extern "C" int mas_stage2_thresholds(const int32_t* nn_proto, const float* nn_sim, int HW, int n_proto, int method, void* scratch,
+                                     int64_t scratch_bytes, float* thr, void* stream) {
+    if (method != MAS_STAGE2_THR_MEDIAN && method != MAS_STAGE2_THR_MIN) return MAS_ERR_SHAPE;
+    if (!nn_proto || !nn_sim || !scratch || !thr) return MAS_ERR_NULL;
+    if (HW <= 0 || HW > 0x7fffffff - kThreads) return MAS_ERR_SHAPE;
+    const int64_t words = thresholds_words(n_proto, method);
+    if (words < 0) return (int)words;
+    if (scratch_bytes < words * 4) return MAS_ERR_WORKSPACE;
+    if ((uintptr_t)scratch & 15) return MAS_ERR_ALIGN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 px((unsigned)((HW + kThreads - 1) / kThreads)), tb(kThreads);
+    unsigned* w = static_cast<unsigned*>(scratch);
+    const bool is_min = method == MAS_STAGE2_THR_MIN;
+    hipLaunchKernelGGL(k_s2thr_init, dim3((unsigned)((words + kThreads - 1) / kThreads)), tb, 0, st, w, (long long)words,
+                       is_min ? kNoKey : 0u);
+    if (is_min) {
+        hipLaunchKernelGGL(k_s2thr_min, px, tb, 0, st, nn_proto, nn_sim, HW, n_proto, w);
+        hipLaunchKernelGGL(k_s2thr_min_out, dim3((unsigned)((n_proto + kThreads - 1) / kThreads)), tb, 0, st, w, n_proto, thr);
+        return mas_launch_status();
+    }
+    unsigned* hist = w;                                         // [n_proto, 256], 16-byte aligned rows
+    uint2* state = reinterpret_cast<uint2*>(w + (size_t)n_proto * 256);
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        hipLaunchKernelGGL(k_s2thr_hist, px, tb, 0, st, nn_proto, nn_sim, HW, n_proto, shift, state, hist);
+        hipLaunchKernelGGL(k_s2thr_pick, dim3((unsigned)n_proto), dim3(MAS_WAVE), 0, st, shift, state, hist, thr);
+    }
     return mas_launch_status();
 }

@@ -787,13 +787,73 @@ def spx_max_onehot(target, superpixel, nseg, num_classes=20):
 # ------------------------------------------------------------------------------------------------
 # K9: stage-2 cosine pseudo labels
 # ------------------------------------------------------------------------------------------------
-def stage2_pseudo_labels(feats, logits, targets, spmasks, superpixels, include_onehot=True):
+_STAGE2_METHODS = {'median': _lib.STAGE2_THR_MEDIAN, 'min': _lib.STAGE2_THR_MIN}
+_STAGE2_THR_WS = {}
+
+
+def stage2_threshold_method(method):
+    """The ABI code of ``--cosprop_threshold_method``; anything but ``'median'`` / ``'min'`` is the reference's
+    ``NotImplementedError`` (``trainer/eval_save_cosplbl_prop.py:253-254``)."""
+    try:
+        return _STAGE2_METHODS[method]
+    except (KeyError, TypeError):
+        raise NotImplementedError("cosprop_threshold_method must be 'median' or 'min', got %r" % (method,))
+
+
+def _stage2_thresholds_aten(nn, nn_sim, n_proto, method):
+    """``MAS_STAGE2_THRESHOLD=aten`` (A/B): the torch chain the kernels replaced -- a ``nonzero`` (host sync) and, for the median, two
+    stable sorts by (prototype, similarity); an ``amin`` scatter for the minimum."""
+    dev = nn.device
+    thr = torch.ones(n_proto, dtype=torch.float32, device=dev)
+    sel = (nn >= 0).nonzero().squeeze(1)
+    if sel.numel():
+        pid, sim = nn[sel].long(), nn_sim[sel]
+        if method == 'min':
+            return thr.scatter_reduce_(0, pid, sim, 'amin', include_self=False)
+        order = torch.argsort(sim, stable=True)
+        order = order[torch.argsort(pid[order], stable=True)]            # sorted by (prototype, similarity)
+        pid_s, sim_s = pid[order], sim[order]
+        cnt = torch.bincount(pid_s, minlength=n_proto)
+        first = torch.cumsum(cnt, 0) - cnt
+        has = cnt > 0
+        thr[has] = sim_s[(first + (cnt - 1) // 2)[has]]
+    return thr
+
+
+def stage2_thresholds(nn, nn_sim, n_proto, method='median'):
+    """float32 ``[n_proto]``: per prototype the lower median (``'median'``) or the minimum (``'min'``) of the similarities of the
+    pixels assigned to it, 1.0 where there is none -- ``trainer/eval_save_cosplbl_prop.py:243-254``.  ``nn`` int32 / ``nn_sim``
+    float32 ``[H*W]``: the outputs of ``mas_stage2_assign`` (``nn < 0``: the pixel takes no part).  One of the input values, picked
+    by rank on the device (``csrc/stage2.hip``); ``MAS_STAGE2_THRESHOLD=aten`` runs the torch chain instead (A/B)."""
+    code = stage2_threshold_method(method)
+    _need(nn, "nn", torch.int32)
+    _need(nn_sim, "nn_sim", torch.float32)
+    if nn.numel() != nn_sim.numel() or nn.numel() == 0:
+        raise ValueError("nn and nn_sim must hold one element per pixel, got %d and %d" % (nn.numel(), nn_sim.numel()))
+    if os.environ.get("MAS_STAGE2_THRESHOLD", "kernel") == "aten":
+        return _stage2_thresholds_aten(nn.reshape(-1), nn_sim.reshape(-1), n_proto, method)
+    dev = nn.device
+    with torch.cuda.device(dev):
+        lib = _lib.load()
+        nbytes = int(lib.mas_stage2_thresholds_scratch_bytes(n_proto, code))
+        if nbytes < 0:
+            _lib.check(nbytes, "mas_stage2_thresholds_scratch_bytes")
+        ws = _stream_scratch(_STAGE2_THR_WS, dev, lambda: torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=dev), nbytes)
+        thr = torch.empty(n_proto, dtype=torch.float32, device=dev)
+        _lib.check(lib.mas_stage2_thresholds(nn.data_ptr(), nn_sim.data_ptr(), nn.numel(), n_proto, code, ws.data_ptr(), ws.numel(),
+                                             thr.data_ptr(), _stream(nn)), "mas_stage2_thresholds")
+    return thr
+
+
+def stage2_pseudo_labels(feats, logits, targets, spmasks, superpixels, include_onehot=True, threshold_method='median'):
     """Pseudo-label maps int64 [N,H,W] (255 = none) -- trainer/eval_save_cosplbl_prop[_includeonehot].py:121-314.
 
     feats [N,Ch,fh,fw]: the L2-normalised point features of ``feat_forward`` BEFORE the bilinear upsampling (full
     resolution is accepted too); logits [N,C,H,W]; targets u8 [N,S,C]; spmasks bool [N,H,W]; superpixels int64.
-    The small index bookkeeping (prototype list, per-prototype medians) uses torch ops on the device; feature
-    interpolation, similarities, adjacency and propagation are HIP kernels."""
+    ``threshold_method``: ``'median'`` or ``'min'`` (``--cosprop_threshold_method``, :243-254), ``NotImplementedError`` otherwise.
+    The prototype list uses torch ops on the device; feature interpolation, similarities, the per-prototype
+    thresholds, adjacency and propagation are HIP kernels."""
+    stage2_threshold_method(threshold_method)
     _need(feats, "feats", torch.float32)
     _need(logits, "logits", torch.float32)
     _need(superpixels, "superpixels", torch.int64)
@@ -832,18 +892,7 @@ def stage2_pseudo_labels(feats, logits, targets, spmasks, superpixels, include_o
             nn_sim = torch.empty(H * W, dtype=torch.float32, device=dev)
             _lib.check(lib.mas_stage2_assign(f.data_ptr(), Ch, fh, fw, H, W, sp.data_ptr(), mk.data_ptr(), S, p_start.data_ptr(),
                                              P.data_ptr(), nn.data_ptr(), nn_sim.data_ptr(), st), "mas_stage2_assign")
-            # per-prototype lower median of the assigned similarities (1.0 when a prototype attracts no pixel)
-            sel = (nn >= 0).nonzero().squeeze(1)
-            thr = torch.ones(n_proto, dtype=torch.float32, device=dev)
-            if sel.numel():
-                pid, sim = nn[sel].long(), nn_sim[sel]
-                order = torch.argsort(sim, stable=True)
-                order = order[torch.argsort(pid[order], stable=True)]            # sorted by (prototype, similarity)
-                pid_s, sim_s = pid[order], sim[order]
-                cnt = torch.bincount(pid_s, minlength=n_proto)
-                first = torch.cumsum(cnt, 0) - cnt
-                has = cnt > 0
-                thr[has] = sim_s[(first + (cnt - 1) // 2)[has]]
+            thr = stage2_thresholds(nn, nn_sim, n_proto, threshold_method)
             adj = torch.zeros((S, words), dtype=torch.int32, device=dev)
             _lib.check(lib.mas_stage2_adjacency(sp.data_ptr(), H, W, S, p_start.data_ptr(), adj.data_ptr(), st), "mas_stage2_adjacency")
             _lib.check(lib.mas_stage2_propagate(f.data_ptr(), Ch, fh, fw, H, W, sp.data_ptr(), S, adj.data_ptr(), p_start.data_ptr(),

@@ -25,6 +25,7 @@ class ActiveTrainer(eval_within_multihot.ActiveTrainer):
     def __init__(self, args, logger, selection_iter):
         super().__init__(args, logger, selection_iter)
         assert args.val_batch_size == 1
+        ops.stage2_threshold_method(getattr(args, 'cosprop_threshold_method', 'median'))     # (not at the first picture)
         self.save_dir = None
 
     def _save_dir(self):
@@ -43,9 +44,11 @@ class ActiveTrainer(eval_within_multihot.ActiveTrainer):
         return self.pseudo_label_generation(labels, feats, outputs, targets, spmasks, superpixels)
 
     def pseudo_label_generation(self, labels, feats, inputs, targets, spmasks, superpixels):
-        """Same signature as the reference (:121); ``feats`` may be the quarter-resolution map."""
+        """Same signature as the reference (:121); ``feats`` may be the quarter-resolution map.  The prototype thresholds follow
+        ``--cosprop_threshold_method`` (:243-254), for every generator that derives from this one."""
         return ops.stage2_pseudo_labels(feats.contiguous(), inputs.contiguous(), targets.contiguous(), spmasks.contiguous(),
-                                        superpixels.contiguous(), include_onehot=self.include_onehot)
+                                        superpixels.contiguous(), include_onehot=self.include_onehot,
+                                        threshold_method=getattr(getattr(self, 'args', None), 'cosprop_threshold_method', 'median'))
 
     def inference(self, loader, prefix=''):
         """The loop of ``eval_within_multihot.inference`` (:55-71) with the pictures dealt to ``MAS_STAGE2_WORKERS`` (default 4) threads,

@@ -242,6 +242,8 @@ def arg_assert(args):
     if 'deeplabv3pluswn_resnet50' in args.model and args.ce_temp == 1:
         print("Check CE temp: {}".format(args.ce_temp))
     assert args.ignore_size == 0 and args.mark_topk == -1            # deprecated options
+    from ..ops import stage2_threshold_method       # NotImplementedError here; the reference raises it at the first picture
+    stage2_threshold_method(getattr(args, 'cosprop_threshold_method', 'median'))            # (trainer/eval_save_cosplbl_prop.py:253)
 
 
 def worker_init_fn(worker_id):
