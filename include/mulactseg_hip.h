@@ -55,7 +55,7 @@ extern "C" {
  * mas_conv_bx_fwd (a library of version 5 answers "unsupported" to both); 8 = the region-label entry points of the data-generation
  * step (mas_region_label_counts, mas_region_multi_hot, mas_region_dominant, mas_region_paint); 9 = mas_ms_ensemble.  mas_naive_plbl and
  * mas_spx_max_onehot came later under 9, then mas_lowres_iou_counts, then mas_render_labels and mas_render_lowres_pred, then mas_ms_naive_plbl, then mas_ms_iou_counts and
- * mas_ms_iou_lds_bytes: new entry
+ * mas_ms_iou_lds_bytes, then mas_candidate_plbl and mas_stage2_assign_labels: new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -389,6 +389,11 @@ int mas_stage2_assign(const float* feat, int Ch, int fh, int fw, int H, int W, c
                       const int32_t* proto_start, const float* P, int32_t* nn_proto /* [H*W] */, float* nn_sim /* [H*W] */,
                       void* stream);
 
+/* The label map of the generator that stops after the assignment (trainer/eval_save_cosplbl.py:186-192, no expansion): out [HW]
+ * int64 = proto_cls[nn_proto[i]] where nn_proto[i] >= 0, 255 elsewhere.  nn_proto [HW] is mas_stage2_assign's output (every
+ * non-negative entry indexes proto_cls).  HW < 1 is MAS_ERR_SHAPE; nothing is launched when an argument is refused. */
+int mas_stage2_assign_labels(const int32_t* nn_proto, const int32_t* proto_cls, int HW, int64_t* out /* [HW] */, void* stream);
+
 /* adj [S, ceil(S/32)] (caller-zeroed bit matrix): bit g of row t set iff superpixel g owns prototypes and some pixel
  * of g lies in the 3x3 neighbourhood of a pixel of t -- the binary_dilation + unique of :259-266, for all superpixels. */
 int mas_stage2_adjacency(const int64_t* spx, int H, int W, int S, const int32_t* proto_start, uint32_t* adj, void* stream);
@@ -480,6 +485,27 @@ int mas_ms_ensemble(const float* const* feats_q, const float* const* logits_q, c
  * mas_upsample_bilinear_fwd accepts); MAS_ERR_SHAPE otherwise.  C <= 255. */
 int mas_naive_plbl(const float* logits_q, int N, int C, int h, int w, int H, int W, const uint8_t* mask /* [N,H,W] or NULL */, float th,
                    uint8_t* labels /* [N,H,W] */, void* stream);
+
+/* Stage-2 labels without expansion (trainer/eval_save_candidateplbl.py, eval_save_candidateplbl_prop.py, eval_save_cosplbl_naiveprop.py)
+ * without materialising the full-resolution logits.  z_q f32 [N,C,h,w]; labels u8 [N,H,W]; mask u8 [N,H,W] (required).  Per pixel
+ * y_c = the C values of mas_upsample_bilinear_fwd's output to H x W, bit for bit (the identity geometry reads the logits themselves).
+ * Under the mask, exactly one of
+ *   candidate mode (spx int64 [N,H,W], bits int32 [N,S] from mas_target_bits, inner NULL, C <= 32): label = the first maximum in channel
+ *     order (a NaN wins where it first appears, as torch.max) of y_c * (float)((bits[n, spx[p]] >> c) & 1), the product taken literally
+ *     (eval_within_multihot.py:137-138); an id outside [0, S) reads no row and gives 255;
+ *   map mode (inner int64 [N,H,W], spx and bits NULL, C <= 255): label = inner[p] narrowed to u8.
+ * Outside the mask: 255, or with fallback != 0 the first arg-max of y_c if 1 / sum_c expf((y_c - y_max) * inv_T) > th (channel
+ * order; th >= 0, MAS_ERR_RANGE otherwise; not bit-equal to torch.softmax; a NaN logit gives 255), else 255.
+ * counts (optional, int64 [3K+3] with K = num_classes <= MAS_MAX_CLASSES, the layout of mas_iou_counts without the "undefined"
+ * triple): ADDED to, not reset -- MeanIoU(K, ignore_label)._after_step(labels, targets); targets int64 [N,H,W] required with counts,
+ * unused without.  Integer atomics only: the same counters on every run.
+ * Geometry: what mas_naive_plbl accepts, MAS_ERR_SHAPE otherwise.  Both or neither of (spx, bits) / inner is MAS_ERR_NULL, a channel
+ * count out of range MAS_ERR_CLASSES.  Nothing is launched when an argument is refused. */
+int mas_candidate_plbl(const float* z_q, int N, int C, int h, int w, int H, int W, const uint8_t* mask /* [N,H,W] */,
+                       const int64_t* spx /* [N,H,W] or NULL */, const int32_t* bits /* [N,S] or NULL */, int S,
+                       const int64_t* inner /* [N,H,W] or NULL */, int fallback, float th, float inv_T,
+                       const int64_t* targets /* [N,H,W] or NULL */, int num_classes, int64_t ignore_label,
+                       uint64_t* counts /* [3K+3] or NULL, accumulated */, uint8_t* labels /* [N,H,W] */, void* stream);
 
 /* Naive arg-max pseudo labels of the VOC generators (trainer/eval_save_cosplbl_naive_voc.py:54-67, single-scale, and
  * trainer/eval_save_cosplbl_naive_voc_ms.py:55-92, multi-scale + flip) with their IoU counters, in one launch per picture.  Sources as

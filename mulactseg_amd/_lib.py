@@ -63,6 +63,7 @@ SIGNATURES = {
     "mas_region_finalize_weighted": (_i, [_vp, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "mas_stage2_gather_protos": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "mas_stage2_assign": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mas_stage2_assign_labels": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mas_stage2_adjacency": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "mas_stage2_propagate": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mas_stage2_thresholds_scratch_bytes": (_i64, [_i, _i]),
@@ -76,6 +77,7 @@ SIGNATURES = {
     "mas_upsample_bilinear_bwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "mas_ms_ensemble": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mas_naive_plbl": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp]),
+    "mas_candidate_plbl": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _f, _f, _vp, _i, _i64, _vp, _vp, _vp]),
     "mas_ms_naive_plbl": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i64, _vp, _vp, _vp]),
     "mas_ms_iou_counts": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i64, _vp, _vp, _vp]),
     "mas_ms_iou_lds_bytes": (_i64, [_vp, _i, _i, _i]),

@@ -7,6 +7,7 @@
 //   * features are read from the QUARTER-resolution map and interpolated in registers (align_corners=False, same
 //     operation order as F.interpolate) -- the 2.1 GB tensor is never materialised;
 //   * k_stage2_assign      nearest prototype of the own superpixel for every valid pixel;
+//   * k_stage2_assign_labels  the label map of that assignment alone (eval_save_cosplbl.py: no expansion);
 //   * k_stage2_adjacency   3x3-dilation adjacency of superpixels as an S x S bit matrix (one pass over the id map);
 //   * k_stage2_propagate   every pixel looks at the valid superpixels adjacent to its own superpixel in ascending id
 //                          order; the last one whose prototype similarity passes that prototype's threshold wins --
@@ -113,6 +114,15 @@ __global__ __launch_bounds__(kThreads) void k_stage2_assign(FeatMap m, const lon
     }
     nn[i] = arg;
     nn_sim[i] = best;
+}
+
+// the label map of the generator that stops after the assignment (trainer/eval_save_cosplbl.py:186-192)
+__global__ __launch_bounds__(kThreads) void k_stage2_assign_labels(const int* __restrict__ nn, const int* __restrict__ p_cls, int HW,
+                                                                    long long* __restrict__ out) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= HW) return;
+    const int own = nn[i];
+    out[i] = own >= 0 ? p_cls[own] : 255;
 }
 
 __global__ __launch_bounds__(kThreads) void k_stage2_adjacency(const long long* __restrict__ spx, int H, int W, int S,
@@ -337,6 +347,14 @@ extern "C" int mas_stage2_assign(const float* feat, int Ch, int fh, int fw, int 
     hipLaunchKernelGGL(k_stage2_assign, dim3((unsigned)((H * W + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        static_cast<hipStream_t>(stream), (FeatMap{feat, Ch, fh, fw, H, W}), reinterpret_cast<const long long*>(spx), mask,
                        S, proto_start, P, nn_proto, nn_sim);
+    return mas_launch_status();
+}
+
+extern "C" int mas_stage2_assign_labels(const int32_t* nn_proto, const int32_t* proto_cls, int HW, int64_t* out, void* stream) {
+    if (!nn_proto || !proto_cls || !out) return MAS_ERR_NULL;
+    if (HW <= 0 || HW > 0x7fffffff - kThreads) return MAS_ERR_SHAPE;
+    hipLaunchKernelGGL(k_stage2_assign_labels, dim3((unsigned)((HW + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream), nn_proto, proto_cls, HW, reinterpret_cast<long long*>(out));
     return mas_launch_status();
 }
 

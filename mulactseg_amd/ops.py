@@ -845,8 +845,10 @@ def stage2_thresholds(nn, nn_sim, n_proto, method='median'):
     return thr
 
 
-def stage2_pseudo_labels(feats, logits, targets, spmasks, superpixels, include_onehot=True, threshold_method='median'):
+def stage2_pseudo_labels(feats, logits, targets, spmasks, superpixels, include_onehot=True, threshold_method='median', expand=True):
     """Pseudo-label maps int64 [N,H,W] (255 = none) -- trainer/eval_save_cosplbl_prop[_includeonehot].py:121-314.
+    ``expand=False`` stops after the assignment (``trainer/eval_save_cosplbl.py:99-196``: no thresholds, no adjacency, no propagation):
+    every selected pixel whose superpixel owns prototypes gets the class of its nearest one, everything else 255.
 
     feats [N,Ch,fh,fw]: the L2-normalised point features of ``feat_forward`` BEFORE the bilinear upsampling (full
     resolution is accepted too); logits [N,C,H,W]; targets u8 [N,S,C]; spmasks bool [N,H,W]; superpixels int64.
@@ -892,6 +894,10 @@ def stage2_pseudo_labels(feats, logits, targets, spmasks, superpixels, include_o
             nn_sim = torch.empty(H * W, dtype=torch.float32, device=dev)
             _lib.check(lib.mas_stage2_assign(f.data_ptr(), Ch, fh, fw, H, W, sp.data_ptr(), mk.data_ptr(), S, p_start.data_ptr(),
                                              P.data_ptr(), nn.data_ptr(), nn_sim.data_ptr(), st), "mas_stage2_assign")
+            if not expand:
+                _lib.check(lib.mas_stage2_assign_labels(nn.data_ptr(), p_cls.data_ptr(), H * W, out[i].data_ptr(), st),
+                           "mas_stage2_assign_labels")
+                continue
             thr = stage2_thresholds(nn, nn_sim, n_proto, threshold_method)
             adj = torch.zeros((S, words), dtype=torch.int32, device=dev)
             _lib.check(lib.mas_stage2_adjacency(sp.data_ptr(), H, W, S, p_start.data_ptr(), adj.data_ptr(), st), "mas_stage2_adjacency")
@@ -1132,6 +1138,133 @@ def _meaniou_counts_aten(labels, targets, K, ignore_label, counts):
         counts[K + i] += int(torch.sum((t == i) & (o == t)))
         counts[2 * K + i] += int(torch.sum(o == i))
     return counts
+
+
+def _candidate_plbl_aten(logits_q, size, spmask, rows, superpixels, inner, fallback, th, ce_temp):
+    """The reference's lines on the upsampled logits (``upsample_bilinear`` on the GPU, ``F.interpolate`` on the CPU):
+    ``top_pseudo_label_generation`` (``eval_within_multihot.py:110-146``; an id outside the rows gives 255 where the reference would
+    raise) or the given map under the mask, then ``eval_save_candidateplbl_prop.py:50-59`` outside it."""
+    import torch.nn.functional as F
+    H, W = int(size[0]), int(size[1])
+    if tuple(logits_q.shape[2:]) == (H, W):
+        z = logits_q
+    elif logits_q.is_cuda:
+        z = upsample_bilinear(logits_q, (H, W))
+    else:
+        z = F.interpolate(logits_q, size=(H, W), mode='bilinear', align_corners=False)
+    N, C = z.shape[:2]
+    spmask = spmask.bool()
+    if inner is not None:
+        plbl = torch.where(spmask, inner, torch.full_like(inner, 255)).reshape(N, -1)
+    else:
+        S = rows.shape[1]
+        plbl = torch.full((N, H * W), 255, dtype=torch.int64, device=z.device)
+        outputs = z.permute(0, 2, 3, 1).reshape(N, -1, C)
+        for i in range(N):
+            valid = spmask[i].reshape(-1)
+            if not torch.any(valid):
+                continue
+            ids = superpixels[i].reshape(-1)[valid]
+            known = (ids >= 0) & (ids < S)
+            trg_pixel = rows[i][ids.clamp(0, S - 1)]
+            lab = (outputs[i][valid] * trg_pixel).max(dim=1)[1]
+            plbl[i, valid.nonzero().squeeze(dim=1)] = torch.where(known, lab, torch.full_like(lab, 255))
+    plbl = plbl.reshape(N, H, W)
+    if fallback:
+        top1, cls = torch.max(torch.softmax(z / ce_temp, dim=1), dim=1)
+        keep = torch.logical_and(top1 > th, torch.logical_not(spmask))
+        plbl = torch.where(keep, cls, plbl)
+    return plbl
+
+
+def candidate_pseudo_labels(logits_q, size, spmask, *, targets_rows=None, superpixels=None, inner=None, fallback=False, th=0.0,
+                            ce_temp=1.0, targets=None, counts=None, num_classes=None, ignore_label=255):
+    """Stage-2 labels without expansion, int64 ``[N,H,W]`` (255 = none) -- ``trainer/eval_save_candidateplbl.py``,
+    ``eval_save_candidateplbl_prop.py`` and ``eval_save_cosplbl_naiveprop.py``.  logits_q f32 ``[N,C,h,w]``: the network's
+    quarter-resolution logits (``net(x, lowres=True)``) or full-resolution ones; per pixel the C values of the bilinear upsampling to
+    ``size`` (bit for bit that of ``upsample_bilinear``).  Under ``spmask`` (bool ``[N,H,W]``) exactly one of
+
+    * ``targets_rows`` u8 ``[N,S,C]`` with ``superpixels`` int64 ``[N,H,W]``: the first arg-max of ``logit * row`` over the superpixel's
+      multi-hot row (``top_pseudo_label_generation``, the quirk for all-negative candidate logits included; C <= 32);
+    * ``inner`` int64 ``[N,H,W]``: labels decided elsewhere (``stage2_pseudo_labels(expand=False)``).
+
+    Outside it 255, or with ``fallback`` the top-1 where ``1 / sum_c exp((y_c - y_max) / ce_temp) > th`` (``th >= 0``; 0 keeps every
+    pixel; not bit-equal to ``torch.softmax``).  ``counts`` (int64 ``[3K+3]``, K = ``num_classes``, required with it):
+    ``MeanIoU(K, ignore_label)._after_step`` of the labels against ``targets`` (int64 ``[N,H,W]``) is ADDED to it.  One launch
+    (``csrc/candidate_plbl.hip``): the full-resolution logits never exist.  CPU tensors, and ``MAS_CANDIDATE_PLBL=aten``, take the
+    reference's ATen chain."""
+    H, W = int(size[0]), int(size[1])
+    th, ce_temp, fallback = float(th), float(ce_temp), bool(fallback)
+    cand = targets_rows is not None or superpixels is not None
+    if cand == (inner is not None) or (cand and (targets_rows is None or superpixels is None)):
+        raise ValueError("candidate_pseudo_labels takes exactly one of (targets_rows and superpixels) or inner")
+    if logits_q.dim() != 4 or logits_q.dtype != torch.float32:
+        raise TypeError("logits_q must be float32 [N,C,h,w], got %s %s" % (logits_q.dtype, tuple(logits_q.shape)))
+    if not naive_plbl_supported(logits_q, (H, W)):
+        raise ValueError("candidate_pseudo_labels: logits %s cannot be upsampled to %dx%d (an upsampling with W <= 6 w, or the identity)"
+                         % (tuple(logits_q.shape), H, W))
+    N, C, h, w = logits_q.shape
+    if spmask is None or tuple(spmask.shape) != (N, H, W):
+        raise ValueError("spmask must be [N,H,W] = [%d,%d,%d]" % (N, H, W))
+    if cand:
+        if C > 32:
+            raise ValueError("candidate mode takes at most 32 channels (one int32 of bits per row), got %d" % C)
+        if superpixels.dtype != torch.int64:
+            raise TypeError("superpixels must be torch.int64, got %s" % superpixels.dtype)
+        if tuple(superpixels.shape) != (N, H, W):
+            raise ValueError("superpixels %s do not match [N,H,W] = [%d,%d,%d]" % (tuple(superpixels.shape), N, H, W))
+        if targets_rows.dim() != 3 or targets_rows.shape[0] != N or targets_rows.shape[2] != C or targets_rows.shape[1] < 1:
+            raise ValueError("targets_rows %s must be [N,S,C] = [%d,S,%d]" % (tuple(targets_rows.shape), N, C))
+    else:
+        if inner.dtype != torch.int64:
+            raise TypeError("inner must be torch.int64, got %s" % inner.dtype)
+        if tuple(inner.shape) != (N, H, W):
+            raise ValueError("inner %s does not match [N,H,W] = [%d,%d,%d]" % (tuple(inner.shape), N, H, W))
+        if not 1 <= C <= 255:
+            raise ValueError("candidate_pseudo_labels takes 1 .. 255 channels, got %d" % C)
+    if fallback and not (th >= 0.0 and ce_temp > 0.0):
+        raise ValueError("the fallback needs th >= 0 and ce_temp > 0, got %r and %r" % (th, ce_temp))
+    K = None if num_classes is None else int(num_classes)
+    if counts is not None:
+        if K is None:
+            raise ValueError("num_classes is required with counts")
+        if targets is None:
+            raise ValueError("targets are required with counts")
+        if not 1 <= K <= _lib.MAX_CLASSES:
+            raise ValueError("num_classes %d must be within [1, %d]" % (K, _lib.MAX_CLASSES))
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (3 * K + 3,) or counts.device != logits_q.device:
+            raise ValueError("counts must be int64 [3K+3] = [%d] on the logits' device" % (3 * K + 3))
+    if targets is not None:
+        if targets.dtype != torch.int64:
+            raise TypeError("targets must be torch.int64, got %s" % targets.dtype)
+        if tuple(targets.shape) != (N, H, W):
+            raise ValueError("targets %s do not match [N,H,W] = [%d,%d,%d]" % (tuple(targets.shape), N, H, W))
+    if not logits_q.is_cuda or os.environ.get("MAS_CANDIDATE_PLBL", "fused") == "aten":
+        labels = _candidate_plbl_aten(logits_q, (H, W), spmask, targets_rows, superpixels, inner, fallback, th, ce_temp)
+        if counts is not None:
+            _meaniou_counts_aten(labels, targets, K, int(ignore_label), counts)
+        return labels
+    _need(logits_q, "logits_q", torch.float32)
+    mask = _mask_u8(spmask.contiguous())
+    spx = bits = None
+    S = 0
+    if cand:
+        spx = _need(superpixels, "superpixels", torch.int64)
+        rows = targets_rows if targets_rows.dtype == torch.uint8 else targets_rows.to(torch.uint8)
+        bits = target_bits(rows.contiguous())
+        S = int(rows.shape[1])
+    else:
+        _need(inner, "inner", torch.int64)
+    if counts is not None:
+        _need(counts, "counts", torch.int64)
+        _need(targets, "targets", torch.int64)
+    out = torch.empty((N, H, W), dtype=torch.uint8, device=logits_q.device)
+    with torch.cuda.device(logits_q.device):
+        _lib.check(_lib.load().mas_candidate_plbl(
+            logits_q.data_ptr(), N, C, h, w, H, W, mask.data_ptr(), _opt(spx), _opt(bits), S, _opt(inner), int(fallback), th,
+            inv_temperature(ce_temp), targets.data_ptr() if counts is not None else None, K if counts is not None else 0,
+            int(ignore_label), _opt(counts), out.data_ptr(), _stream(logits_q)), "mas_candidate_plbl")
+    return out.long()
 
 
 def _ms_mean_aten(logits_q, sizes, flips, out_size):
