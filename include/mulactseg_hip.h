@@ -55,7 +55,8 @@ extern "C" {
  * mas_conv_bx_fwd (a library of version 5 answers "unsupported" to both); 8 = the region-label entry points of the data-generation
  * step (mas_region_label_counts, mas_region_multi_hot, mas_region_dominant, mas_region_paint); 9 = mas_ms_ensemble.  mas_naive_plbl and
  * mas_spx_max_onehot came later under 9, then mas_lowres_iou_counts, then mas_render_labels and mas_render_lowres_pred, then mas_ms_naive_plbl, then mas_ms_iou_counts and
- * mas_ms_iou_lds_bytes, then mas_candidate_plbl and mas_stage2_assign_labels: new entry
+ * mas_ms_iou_lds_bytes, then mas_candidate_plbl and mas_stage2_assign_labels, then mas_uncertainty_accum,
+ * mas_uncertainty_accum_lowres and mas_uncertainty_reference: new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -351,6 +352,30 @@ int mas_single_pass_accum_lowres(const float* zq, int h, int w, const void* spx,
 #define MAS_LOWRES_GENERIC 1u
 int mas_single_pass_accum_lowres_opt(const float* zq, int h, int w, const void* spx, int spx_dtype, int B, int C, int H, int W, int S,
                                      float invT, uint64_t* prob_sum, uint64_t* class_sum, uint32_t* hist, unsigned flags, void* stream);
+
+/* The scan for the acquisition measures beyond BvSB.  Same accumulators and contracts as mas_single_pass_accum (+= into caller-zeroed
+ * prob_sum [B,C] with 23 fractional bits, class_sum [B,S,C] with 40, hist [B,S,C]; ids outside [0,S) skipped), with the per-pixel
+ * value of csrc/uncertainty.h in place of the BvSB margin:
+ *   MAS_UNC_BVSB p2 / p1 (class_sum then equals mas_single_pass_accum's bit for bit), MAS_UNC_MARGIN 1 - (p1 - p2),
+ *   MAS_UNC_LEAST_CONFIDENCE 1 - p1, MAS_UNC_ENTROPY -sum_c p_c ln p_c / ln C; each + 1e-8f, in (0, 1.0000001].
+ * prob_sum and hist do not depend on the measure and equal mas_single_pass_accum's.  2 <= C <= MAS_MAX_CLASSES (MAS_ERR_CLASSES); an
+ * unknown measure is MAS_ERR_RANGE.  mas_region_finalize_weighted, mas_class_weight and the rest of the round apply unchanged. */
+#define MAS_UNC_BVSB 0
+#define MAS_UNC_MARGIN 1
+#define MAS_UNC_LEAST_CONFIDENCE 2
+#define MAS_UNC_ENTROPY 3
+int mas_uncertainty_accum(const float* z, const void* spx, int spx_dtype, int B, int C, int H, int W, int S, float invT, int measure,
+                          uint64_t* prob_sum, uint64_t* class_sum, uint32_t* hist, void* stream);
+/* the same scan of F.interpolate(zq, (H, W), 'bilinear', align_corners=False), zq f32 [B,C,h,w], evaluated per pixel in registers in
+ * the operation order of mas_upsample_bilinear_fwd: the accumulators equal mas_uncertainty_accum's on the materialised tensor bit for
+ * bit.  Geometries: the identity, or an upsampling with W <= 6 w (those of mas_naive_plbl); anything else is MAS_ERR_RANGE, returned
+ * before anything is launched. */
+int mas_uncertainty_accum_lowres(const float* zq, int h, int w, const void* spx, int spx_dtype, int B, int C, int H, int W, int S,
+                                 float invT, int measure, uint64_t* prob_sum, uint64_t* class_sum, uint32_t* hist, void* stream);
+/* mas_uncertainty_accum on HOST pointers: a plain loop over the pixels through csrc/uncertainty.h, the CPU-side statement of the
+ * arithmetic (the kernel equals it bit for bit).  Touches no device. */
+int mas_uncertainty_reference(const float* z, const void* spx, int spx_dtype, int B, int C, int H, int W, int S, float invT, int measure,
+                              uint64_t* prob_sum, uint64_t* class_sum, uint32_t* hist);
 
 /* score[r] = floor(((sum_c class_sum[r,c] * w31[c]) >> 31) / n_r) * 2^-40, w31[c] = floor(cls_weight[c] * 2^31)
  * (exact integer arithmetic); dominant class, ban and optional outputs as mas_region_finalize.

@@ -22,6 +22,7 @@ MS_MAX_SOURCES = 16
 
 SK_DMA, SK_NOSPLIT = 1, 2
 LOWRES_GENERIC = 1
+UNC_BVSB, UNC_MARGIN, UNC_LEAST_CONFIDENCE, UNC_ENTROPY = 0, 1, 2, 3
 STAGE2_THR_MEDIAN, STAGE2_THR_MIN = 0, 1
 ABI_VERSION = 9        # MAS_ABI_VERSION of include/mulactseg_hip.h this table was written against (load() refuses any other library)
 
@@ -59,6 +60,9 @@ SIGNATURES = {
     "mas_single_pass_accum": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "mas_single_pass_accum_lowres": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "mas_single_pass_accum_lowres_opt": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _c.c_uint, _vp]),
+    "mas_uncertainty_accum": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "mas_uncertainty_accum_lowres": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "mas_uncertainty_reference": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "mas_class_weight": (_i, [_vp, _i, _i, _i64, _i, _i, _d, _vp, _vp, _vp, _vp]),
     "mas_region_finalize_weighted": (_i, [_vp, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "mas_stage2_gather_protos": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),

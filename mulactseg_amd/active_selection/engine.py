@@ -130,6 +130,12 @@ class HipBackend:
     def single_pass_lowres(self, zq, size, spx, S, invT, prob_sum, class_sum, hist):
         self.ops.single_pass_accum_lowres(zq, size, spx, S, invT, prob_sum=prob_sum, class_sum=class_sum, hist=hist)
 
+    def uncertainty_pass(self, logits, spx, S, invT, measure, prob_sum, class_sum, hist):
+        self.ops.uncertainty_accum(logits, spx, S, invT, measure, prob_sum=prob_sum, class_sum=class_sum, hist=hist)
+
+    def uncertainty_pass_lowres(self, zq, size, spx, S, invT, measure, prob_sum, class_sum, hist):
+        self.ops.uncertainty_accum_lowres(zq, size, spx, S, invT, measure, prob_sum=prob_sum, class_sum=class_sum, hist=hist)
+
     def class_weight(self, prob_sum, hw, batch_size, n_batches, coeff):
         """(cum f64 [C], cls_w f32 [C]) on the device from the gathered per-picture class sums; the integer form of the
         weights rides along on the tensor so that ``finalize_weighted`` needs no conversion (and no host round trip)."""
@@ -276,31 +282,51 @@ class AcquisitionRound:
         self.backend.single_pass(logits.contiguous(), spx.contiguous(), self.S, self.invT, self.prob_sum[r],
                                  self.class_sum[r], self.hist[r])
 
-    def add_single_pass_lowres(self, row0, zq, size, spx):
-        """As ``add_single_pass`` for the logits ``F.interpolate(zq, size, 'bilinear', align_corners=False)`` (the model's final
-        upsampling, ``models/segmentation/utils.py:25``) evaluated inside the scan: same accumulators, bit for bit."""
-        B = zq.shape[0]
+    def _rows_lowres(self, row0, B, size):
+        """(slice of this rank's rows, H*W) of a batch of ``B`` low-resolution pictures scanned at ``size``, checked like ``_rows``;
+        the caller records H*W."""
         if row0 < 0 or row0 + B > self.plan.n_local:
             raise IndexError("batch rows [%d,%d) outside this rank's shard of %d images" % (row0, row0 + B, self.plan.n_local))
         hw = int(size[0]) * int(size[1])
-        if self.hw is None:
-            self.hw = hw
-        elif self.hw != hw:
+        if self.hw is not None and self.hw != hw:
             raise ValueError("all pool images of one round must share H*W (the class prior is a pixel mean)")
-        r = slice(row0, row0 + B)
+        return slice(row0, row0 + B), hw
+
+    def add_single_pass_lowres(self, row0, zq, size, spx):
+        """As ``add_single_pass`` for the logits ``F.interpolate(zq, size, 'bilinear', align_corners=False)`` (the model's final
+        upsampling, ``models/segmentation/utils.py:25``) evaluated inside the scan: same accumulators, bit for bit."""
+        r, self.hw = self._rows_lowres(row0, zq.shape[0], size)
         self.backend.single_pass_lowres(zq.contiguous(), (int(size[0]), int(size[1])), spx.contiguous(), self.S, self.invT,
                                         self.prob_sum[r], self.class_sum[r], self.hist[r])
 
-    def scores_single_pass(self, cls_w, ban_class=-1, want_hist=False):
+    def add_uncertainty(self, row0, logits, spx, measure):
+        """``add_single_pass`` with the per-pixel value of ``measure`` (``ops.UNCERTAINTY``) in place of the BvSB margin: the same
+        three accumulators, so class weights, finaliser, ban and selection apply unchanged."""
+        r = self._rows(row0, logits)
+        self.backend.uncertainty_pass(logits.contiguous(), spx.contiguous(), self.S, self.invT, measure, self.prob_sum[r],
+                                      self.class_sum[r], self.hist[r])
+
+    def add_uncertainty_lowres(self, row0, zq, size, spx, measure):
+        """As ``add_uncertainty`` for ``F.interpolate(zq, size, 'bilinear', align_corners=False)`` evaluated inside the scan: same
+        accumulators, bit for bit.  A refused geometry raises before anything is accumulated (or recorded here)."""
+        r, hw = self._rows_lowres(row0, zq.shape[0], size)
+        self.backend.uncertainty_pass_lowres(zq.contiguous(), (int(size[0]), int(size[1])), spx.contiguous(), self.S, self.invT, measure,
+                                             self.prob_sum[r], self.class_sum[r], self.hist[r])
+        self.hw = hw
+
+    def scores_single_pass(self, cls_w, ban_class=-1, want_hist=False, want_dominant=False):
         """Weighted region means from the single-pass accumulators (cls_w None -> unweighted)."""
         n = self.plan.n_local
         if n == 0:
             dev = self.backend.device
             score = torch.zeros((0, self.S), dtype=torch.float32, device=dev)
+            dom = torch.zeros((0, self.S), dtype=torch.int32, device=dev)
             h64 = torch.zeros((0, self.S, self.C), dtype=torch.int64, device=dev)
         else:
             score, dom, cnt, h64 = self.backend.finalize_weighted(self.class_sum[:n], self.hist[:n], cls_w, ban_class, want_hist)
         full = gather_rows(score, self.plan)                                      # exchange 2
+        if want_dominant:
+            return full, gather_rows(dom, self.plan)
         if want_hist:
             return full, gather_rows(h64, self.plan)
         return full

@@ -79,10 +79,48 @@ class RegionSelector(base.RegionSelector):
             for st in streams:
                 main.wait_stream(st)
 
+    @property
+    def uncertainty(self):
+        """The per-pixel measure (``--uncertainty``): 'bvsb', the reference's, runs the selectors' own kernels; another one routes
+        the scan through ``_scan_uncertainty``."""
+        return getattr(self.args, 'uncertainty', None) or 'bvsb'
+
+    def _scan_uncertainty(self, trainer, pool_set, rnd, C, strip=False):
+        """The pool scan for a measure other than BvSB (csrc/uncertainty.hip) into the single-pass accumulators of ``rnd``.  A model
+        that hands out its quarter-resolution logits is scanned from them, the final bilinear upsampling evaluated inside the scan; a
+        geometry the kernel refuses (before anything is launched) falls back to scanning ``ops.upsample_bilinear``'s tensor."""
+        from .. import _lib, ops
+        measure, backend = self.uncertainty, rnd.backend
+        low = (getattr(trainer.net, 'lowres_logits', False) and getattr(self.args, 'lowres_scan', True)
+               and hasattr(backend, 'uncertainty_pass_lowres'))
+        for row, preds, spx in self._iterate(trainer, pool_set, rnd, lowres=low):
+            if strip:
+                preds = preds[:, :-1].contiguous()              # (the upsampling is per channel: stripping first changes nothing)
+            if preds.shape[1] != C:
+                raise ValueError("scorer expects %d channels, got %d" % (C, preds.shape[1]))
+            if low:
+                try:
+                    rnd.add_uncertainty_lowres(row, preds, spx.shape[-2:], spx, measure)
+                    continue
+                except _lib.MulActSegHipError as e:
+                    if "out of range" not in str(e):
+                        raise
+                    low = False
+            if preds.shape[-2:] != spx.shape[-2:]:
+                preds = ops.upsample_bilinear(preds.contiguous(), spx.shape[-2:])
+            rnd.add_uncertainty(row, preds, spx, measure)
+
     def calculate_scores_tensor(self, trainer, pool_set):
         """[n_img, S] f32 on the device: normalised region means (``my_bvsb.py:50-84``)."""
         backend = self._backend(trainer)
         strip = 'predignore' in self.args.method            # my_bvsb.py:65-66: drop the "undefined" channel
+        if self.uncertainty != 'bvsb':
+            rnd = AcquisitionRound(len(pool_set.im_idx), self.num_class, self.num_superpixels, self.batch_size,
+                                   self.temperature, backend, single_pass=True)
+            self._scan_uncertainty(trainer, pool_set, rnd, self.num_class, strip)
+            scores = rnd.scores_single_pass(None, ban_class=-1)     # unit weights are exact (mas_region_finalize_weighted)
+            backend.minmax_normalize_(scores)
+            return scores
         rnd = AcquisitionRound(len(pool_set.im_idx), self.num_class, self.num_superpixels, self.batch_size,
                                self.temperature, backend)
         for row, preds, spx in self._iterate(trainer, pool_set, rnd):

@@ -17,6 +17,12 @@ class RegionSelector(my_bvsb.RegionSelector):
         C = self.num_class + self.extra_channels
         if self.extra_channels:
             assert 'predignore' in self.args.method          # my_bvsb_banignore.py:35
+        if self.uncertainty != 'bvsb':       # score and dominant class from the weighted finaliser (unit weights are exact)
+            rnd = AcquisitionRound(len(pool_set.im_idx), C, self.num_superpixels, self.batch_size, self.temperature, backend,
+                                   single_pass=True)
+            self._scan_uncertainty(trainer, pool_set, rnd, C)
+            self._round = rnd
+            return rnd.scores_single_pass(None, ban_class=-1, want_dominant=True)
         rnd = AcquisitionRound(len(pool_set.im_idx), C, self.num_superpixels, self.batch_size, self.temperature, backend)
         for row, preds, spx in self._iterate(trainer, pool_set, rnd):
             if preds.shape[1] != C:

@@ -28,6 +28,14 @@ class RegionSelector(my_bvsb.RegionSelector):
         n_img = len(pool_set.im_idx)
         C = self.num_class + self.extra_channels
         ban = C - 1 if self.ban_ignore else -1                                      # (:79-84)
+        if self.uncertainty != 'bvsb':
+            if getattr(self.args, 'two_pass_scoring', False):
+                raise ValueError("--uncertainty %s needs the single-pass round: the two-pass kernels know BvSB only" % self.uncertainty)
+            rnd = AcquisitionRound(n_img, C, self.num_superpixels, self.batch_size, self.args.ce_temp, backend, single_pass=True)
+            self._scan_uncertainty(trainer, pool_set, rnd, C)
+            cls_w = rnd.class_weights(self.args.cls_weight_coeff)
+            self._round, self.cls_weight = rnd, cls_w
+            return rnd.scores_single_pass(cls_w, ban_class=ban, want_hist=want_hist)
         if not getattr(self.args, 'two_pass_scoring', False):
             rnd = AcquisitionRound(n_img, C, self.num_superpixels, self.batch_size, self.args.ce_temp, backend,
                                    single_pass=True)

@@ -592,6 +592,81 @@ def single_pass_accum_lowres(zq, size, spx, S, invT, prob_sum=None, class_sum=No
     return prob_sum, class_sum, hist
 
 
+UNCERTAINTY = {'bvsb': 0, 'margin': 1, 'least_confidence': 2, 'entropy': 3}       # MAS_UNC_* of include/mulactseg_hip.h
+
+
+def _measure_code(measure):
+    try:
+        return UNCERTAINTY[measure]
+    except KeyError:
+        raise ValueError("unknown uncertainty measure %r (one of %s)" % (measure, ', '.join(UNCERTAINTY)))
+
+
+def _uncertainty_buffers(B, C, S, dev, prob_sum, class_sum, hist):
+    if prob_sum is None:
+        prob_sum = torch.zeros((B, C), dtype=torch.int64, device=dev)
+    if class_sum is None:
+        class_sum = torch.zeros((B, S, C), dtype=torch.int64, device=dev)
+    if hist is None:
+        hist = torch.zeros((B, S, C), dtype=torch.int32, device=dev)
+    return prob_sum, class_sum, hist
+
+
+def uncertainty_accum(z, spx, S, invT, measure, prob_sum=None, class_sum=None, hist=None):
+    """``single_pass_accum`` with the per-pixel value of ``measure`` (a key of ``UNCERTAINTY``; csrc/uncertainty.h) in place of the
+    BvSB margin: (prob_sum [B,C] i64, class_sum [B,S,C] i64, hist [B,S,C] i32), all accumulated into.  2 <= C <= 32."""
+    code = _measure_code(measure)
+    _need(z, "z", torch.float32)
+    _need(spx, "spx")
+    B, C, H, W = z.shape
+    if tuple(spx.shape) != (B, H, W):
+        raise ValueError("spx shape %s does not match logits %s" % (tuple(spx.shape), tuple(z.shape)))
+    prob_sum, class_sum, hist = _uncertainty_buffers(B, C, S, z.device, prob_sum, class_sum, hist)
+    with torch.cuda.device(z.device):
+        _lib.check(_lib.load().mas_uncertainty_accum(z.data_ptr(), spx.data_ptr(), _id_code(spx), B, C, H, W, S, invT, code,
+                                                     prob_sum.data_ptr(), class_sum.data_ptr(), hist.data_ptr(), _stream(z)),
+                   "mas_uncertainty_accum")
+    return prob_sum, class_sum, hist
+
+
+def uncertainty_accum_lowres(zq, size, spx, S, invT, measure, prob_sum=None, class_sum=None, hist=None):
+    """``uncertainty_accum`` of ``F.interpolate(zq, size, 'bilinear', align_corners=False)`` without materialising it: ``zq``
+    [B,C,h,w], ``spx`` [B,H,W]; same outputs, bit for bit.  A geometry outside the identity / an upsampling of at most x6 along the rows
+    is refused ("argument out of range") before anything is launched."""
+    code = _measure_code(measure)
+    _need(zq, "zq", torch.float32)
+    _need(spx, "spx")
+    B, C, h, w = zq.shape
+    H, W = int(size[0]), int(size[1])
+    if tuple(spx.shape) != (B, H, W):
+        raise ValueError("spx shape %s does not match logits %s at size %s" % (tuple(spx.shape), tuple(zq.shape), (H, W)))
+    prob_sum, class_sum, hist = _uncertainty_buffers(B, C, S, zq.device, prob_sum, class_sum, hist)
+    with torch.cuda.device(zq.device):
+        _lib.check(_lib.load().mas_uncertainty_accum_lowres(zq.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), B, C, H, W, S, invT, code,
+                                                            prob_sum.data_ptr(), class_sum.data_ptr(), hist.data_ptr(), _stream(zq)),
+                   "mas_uncertainty_accum_lowres")
+    return prob_sum, class_sum, hist
+
+
+def uncertainty_reference(z, spx, S, invT, measure, prob_sum=None, class_sum=None, hist=None):
+    """``uncertainty_accum`` on HOST tensors: the library's plain loop over the pixels through csrc/uncertainty.h
+    (``mas_uncertainty_reference``), the CPU-side statement of the arithmetic the kernel is checked against.  Needs no GPU."""
+    code = _measure_code(measure)
+    for t, name in ((z, "z"), (spx, "spx"), (prob_sum, "prob_sum"), (class_sum, "class_sum"), (hist, "hist")):
+        if t is not None and (t.is_cuda or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous host tensor" % name)
+    if z.dtype != torch.float32:
+        raise TypeError("z must be float32, got %s" % z.dtype)
+    B, C, H, W = z.shape
+    if tuple(spx.shape) != (B, H, W):
+        raise ValueError("spx shape %s does not match logits %s" % (tuple(spx.shape), tuple(z.shape)))
+    prob_sum, class_sum, hist = _uncertainty_buffers(B, C, S, z.device, prob_sum, class_sum, hist)
+    _lib.check(_lib.load().mas_uncertainty_reference(z.data_ptr(), spx.data_ptr(), _id_code(spx), B, C, H, W, S, invT, code,
+                                                     prob_sum.data_ptr(), class_sum.data_ptr(), hist.data_ptr()),
+               "mas_uncertainty_reference")
+    return prob_sum, class_sum, hist
+
+
 def region_finalize_weighted(class_sum, hist, w31, ban_class=-1, want_hist_i64=False):
     """Weighted mean per region from the single-pass accumulators.  ``w31``: int32 tensor [C] holding uint32 bits."""
     _need(class_sum, "class_sum", torch.int64)

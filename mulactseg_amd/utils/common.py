@@ -75,6 +75,8 @@ def get_parser():
     a('--loader', type=str, default='region_cityscapes')
     a("--active_method", default='my_random')
     a("--initial_active_method", default='my_random')
+    a("--uncertainty", default='bvsb', choices=['bvsb', 'margin', 'least_confidence', 'entropy'],
+      help="per-pixel measure of the my_bvsb* selectors: the reference's p2/p1, or 1-(p1-p2), 1-p1, entropy/ln C")
     # temperatures / loss weights
     a("--ce_temp", type=float, default=1.0)
     a("--multi_ce_temp", type=float, default=1.0)
@@ -242,6 +244,9 @@ def arg_assert(args):
     if 'deeplabv3pluswn_resnet50' in args.model and args.ce_temp == 1:
         print("Check CE temp: {}".format(args.ce_temp))
     assert args.ignore_size == 0 and args.mark_topk == -1            # deprecated options
+    if getattr(args, 'uncertainty', 'bvsb') != 'bvsb' and getattr(args, 'two_pass_scoring', False):
+        raise ValueError("--uncertainty %s needs the single-pass round: the two-pass kernels (two_pass_scoring) know BvSB only"
+                         % args.uncertainty)
     from ..ops import stage2_threshold_method       # NotImplementedError here; the reference raises it at the first picture
     stage2_threshold_method(getattr(args, 'cosprop_threshold_method', 'median'))            # (trainer/eval_save_cosplbl_prop.py:253)
 
