@@ -56,7 +56,8 @@ extern "C" {
  * step (mas_region_label_counts, mas_region_multi_hot, mas_region_dominant, mas_region_paint); 9 = mas_ms_ensemble.  mas_naive_plbl and
  * mas_spx_max_onehot came later under 9, then mas_lowres_iou_counts, then mas_render_labels and mas_render_lowres_pred, then mas_ms_naive_plbl, then mas_ms_iou_counts and
  * mas_ms_iou_lds_bytes, then mas_candidate_plbl and mas_stage2_assign_labels, then mas_uncertainty_accum,
- * mas_uncertainty_accum_lowres and mas_uncertainty_reference: new entry
+ * mas_uncertainty_accum_lowres and mas_uncertainty_reference, then mas_train_augment_u8, mas_photometric and
+ * mas_photometric_reference: new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -481,6 +482,32 @@ int mas_train_augment(const uint8_t* img, int H, int W, int th, int tw, const in
                       int gap_x, int crop_i, int crop_j, int flip, int out_h, int out_w, const float* mean, const float* std,
                       const uint8_t* fill, const void* map0, int map0_dtype, int64_t pad0, void* out_map0, int out0_u8,
                       const void* map1, int map1_dtype, int64_t pad1, void* out_map1, int out1_u8, float* out_img, void* stream);
+
+/* Photometric augmentation of ONE sample (dataloader/transform.py:139-153 of the reference: ExtColorJitter + ExtRandomGrayscale after
+ * crop and flip), for the samples that draw it; the arithmetic is csrc/photometric.h (Pillow's ImageEnhance / convert('HSV') /
+ * convert('L') on 8-bit RGB, bit for bit).  The chain: `order` int[4], a permutation of the ops 0 = brightness, 1 = contrast,
+ * 2 = saturation, 3 = hue; `factor` float[4] indexed by op (the hue entry is the hue shift in [-0.5, 0.5]); bit k of `present` says
+ * that op k is in the chain (an absent op's factor is ignored); order, factor, mean, std, fill are HOST pointers.  Factors below 0, a
+ * hue outside [-0.5, 0.5] and an order that is no permutation are MAS_ERR_RANGE; at most 2^24 pixels (MAS_ERR_SHAPE).
+ *
+ * mas_train_augment_u8: the geometry of mas_train_augment (same arguments, same maps), the crop written as u8 [out_h,out_w,3].  When
+ * contrast is present, the ops that precede it in `order` are applied per pixel (in registers, not to out_crop) and the L of the
+ * result is added to *lsum (device u32; the caller zeroes it; required then, ignored and may be NULL otherwise).
+ * mas_photometric: crop u8 [h,w,3] (4-byte aligned) -> the whole chain in order, then grayscale when `grey`, then to-tensor +
+ * normalise -> out_img f32 [3,h,w] (16-byte aligned); the contrast degenerate value is (int)(*lsum / (h w) + 0.5), formed on the
+ * device.  out_u8 (u8 [h,w,3], may be NULL) receives the 8-bit result before normalisation.
+ * mas_photometric_reference: the same header as a host loop over HOST memory, the contrast sum included (*lsum_out, when not NULL,
+ * receives it); out_u8 and out_img may each be NULL.  No device is touched. */
+int mas_train_augment_u8(const uint8_t* img, int H, int W, int th, int tw, const int32_t* hbounds, const int32_t* hk, int hks,
+                         const int32_t* vbounds, const int32_t* vk, int vks, const int32_t* xidx, const int32_t* yidx, int gap_y,
+                         int gap_x, int crop_i, int crop_j, int flip, int out_h, int out_w, const uint8_t* fill, const void* map0,
+                         int map0_dtype, int64_t pad0, void* out_map0, int out0_u8, const void* map1, int map1_dtype, int64_t pad1,
+                         void* out_map1, int out1_u8, const int32_t* order, const float* factor, int present, uint8_t* out_crop,
+                         uint32_t* lsum, void* stream);
+int mas_photometric(const uint8_t* crop, int h, int w, const int32_t* order, const float* factor, int present, int grey,
+                    const float* mean, const float* std, const uint32_t* lsum, float* out_img, uint8_t* out_u8, void* stream);
+int mas_photometric_reference(const uint8_t* crop, int h, int w, const int32_t* order, const float* factor, int present, int grey,
+                              const float* mean, const float* std, uint8_t* out_u8, float* out_img, uint32_t* lsum_out);
 
 /* K8 (part): F.interpolate(mode='bilinear', align_corners=False) of x [NC,Hi,Wi] -> y [NC,Ho,Wo]
  * (models/segmentation/utils.py:25, deeplabv3.py:116) and its backward as a deterministic gather (no atomics).

@@ -24,6 +24,7 @@ SK_DMA, SK_NOSPLIT = 1, 2
 LOWRES_GENERIC = 1
 UNC_BVSB, UNC_MARGIN, UNC_LEAST_CONFIDENCE, UNC_ENTROPY = 0, 1, 2, 3
 STAGE2_THR_MEDIAN, STAGE2_THR_MIN = 0, 1
+PM_BRIGHTNESS, PM_CONTRAST, PM_SATURATION, PM_HUE = 0, 1, 2, 3
 ABI_VERSION = 9        # MAS_ABI_VERSION of include/mulactseg_hip.h this table was written against (load() refuses any other library)
 
 _c = ctypes
@@ -77,6 +78,10 @@ SIGNATURES = {
     "mas_aspp_dw3_bwd_w": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mas_train_augment": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp,
                                _vp, _i, _i64, _vp, _i, _vp, _i, _i64, _vp, _i, _vp, _vp]),
+    "mas_train_augment_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp,
+                                  _vp, _i, _i64, _vp, _i, _vp, _i, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "mas_photometric": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mas_photometric_reference": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mas_upsample_bilinear_fwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "mas_upsample_bilinear_bwd": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "mas_ms_ensemble": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

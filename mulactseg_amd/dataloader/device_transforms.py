@@ -121,7 +121,9 @@ class DeviceTrainAugment:
         self.keep_u8 = keep_u8
         self._ring = _PinnedRing()
 
-    def __call__(self, img, maps=(), params=None):
+    def _prepare(self, img, maps, params):
+        """Checks, draws (unless ``params``), coefficient tables and map outputs of one sample -> (params, the geometry arguments
+        up to ``out_w`` of the augmentation entries, the map arguments, the map outputs, the table tensor to keep alive)."""
         if not (img.is_cuda and img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.is_contiguous()):
             raise ValueError("picture must be a contiguous uint8 [H,W,3] tensor on the GPU")
         maps = list(maps)
@@ -131,7 +133,7 @@ class DeviceTrainAugment:
         for m in maps:
             if not (m.is_cuda and tuple(m.shape) == (H, W) and m.dtype in _MAP_CODES and m.is_contiguous()):
                 raise ValueError("maps must be contiguous [H,W] integer tensors on the picture's device")
-        p = params if params is not None else draw_params(self.rng, H, W, self.size, self.scale_range)
+        p = params if params is not None else self._draw(H, W)
         th, tw = p['th'], p['tw']
         hb, hk = bilinear_tables(W, tw)
         vb, vk = bilinear_tables(H, th)
@@ -141,7 +143,6 @@ class DeviceTrainAugment:
         tab = self._ring.upload(np.concatenate(parts).astype(np.int32, copy=False), img.device)   # one small pinned H2D copy
         ptr = [tab.data_ptr() + 4 * int(o) for o in offs[:-1]]
         ch, cw = self.size
-        out = torch.empty((3, ch, cw), dtype=torch.float32, device=img.device)
         outs, margs = [], []
         for k in range(2):
             if k < len(maps):
@@ -151,15 +152,152 @@ class DeviceTrainAugment:
                 margs += [maps[k].data_ptr(), _MAP_CODES[maps[k].dtype], int(self.pad_values[k]), o.data_ptr(), int(u8)]
             else:
                 margs += [None, 0, 0, None, 0]
+        geom = [img.data_ptr(), H, W, th, tw, ptr[0], ptr[1], hk.shape[1], ptr[2], ptr[3], vk.shape[1], ptr[4], ptr[5],
+                p['gap_y'], p['gap_x'], p['i'], p['j'], int(p['flip']), ch, cw]
+        return p, geom, margs, outs, tab
+
+    def _draw(self, H, W):
+        return draw_params(self.rng, H, W, self.size, self.scale_range)
+
+    def __call__(self, img, maps=(), params=None):
+        p, geom, margs, outs, tab = self._prepare(img, maps, params)
+        ch, cw = self.size
+        out = torch.empty((3, ch, cw), dtype=torch.float32, device=img.device)
         lib = _lib.load()
         with torch.cuda.device(img.device):
             st = torch.cuda.current_stream(img.device).cuda_stream
-            _lib.check(lib.mas_train_augment(img.data_ptr(), H, W, th, tw, ptr[0], ptr[1], hk.shape[1], ptr[2], ptr[3], vk.shape[1],
-                                             ptr[4], ptr[5], p['gap_y'], p['gap_x'], p['i'], p['j'], int(p['flip']), ch, cw,
-                                             self.mean.ctypes.data, self.std.ctypes.data, self.fill.ctypes.data, *margs,
+            _lib.check(lib.mas_train_augment(*geom, self.mean.ctypes.data, self.std.ctypes.data, self.fill.ctypes.data, *margs,
                                              out.data_ptr(), st), "mas_train_augment")
         tab.record_stream(torch.cuda.current_stream(img.device))
         return out, outs
+
+
+def _jitter_range(value, center=1.0, clip_first_on_zero=True):
+    """torchvision 0.12 ``ColorJitter._check_input`` for a number: ``[center - v, center + v]`` (the first clipped at 0);
+    ``None`` when the range collapses to its centre (nothing is drawn then)."""
+    if value < 0:
+        raise ValueError("a jitter strength must be non-negative")
+    lo, hi = center - float(value), center + float(value)
+    if clip_first_on_zero:
+        lo = max(lo, 0.0)
+    return None if lo == hi == center else (lo, hi)
+
+
+def draw_photometric(gen, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.1, p_jitter=0.2, p_gray=0.2):
+    """The photometric draws of ``ExtColorJitter(b, c, s, h, p)`` + ``ExtRandomGrayscale(p)`` (reference ``ext_transforms.py:48-88``)
+    in the order torchvision 0.12.0 makes them, on torch's CPU generator ``gen`` (``None``: the global one): ``rand(1)`` -- jitter
+    unless ``p < u``; then ``randperm(4)`` and one ``uniform_`` each for brightness, contrast, saturation, hue (a component whose
+    range collapses draws nothing); then ``rand(1) < p_gray``, always drawn.
+    -> ``dict(order=[4 ints] or None, factors=[b, c, s, h] with None for an absent op, grey=bool)``; ``order is None``: no jitter."""
+    ranges = [_jitter_range(brightness), _jitter_range(contrast), _jitter_range(saturation),
+              _jitter_range(hue, center=0.0, clip_first_on_zero=False)]
+    if not 0 <= hue <= 0.5:
+        raise ValueError("hue must lie in [0, 0.5]")
+    order, factors = None, [None] * 4
+    if not bool(p_jitter < torch.rand(1, generator=gen)):
+        order = [int(v) for v in torch.randperm(4, generator=gen)]
+        factors = [None if r is None else float(torch.empty(1).uniform_(r[0], r[1], generator=gen)) for r in ranges]
+    grey = bool(torch.rand(1, generator=gen) < p_gray)
+    return dict(order=order, factors=factors, grey=grey)
+
+
+def _chain_args(photometric):
+    """-> (order int32[4], factor float32[4], present bits, grey) of the C entries."""
+    order = photometric.get('order')
+    factors = photometric.get('factors') or [None] * 4
+    present = 0
+    if order is not None:
+        for k, f in enumerate(factors):
+            present |= (f is not None) << k
+    o = np.asarray(order if order is not None else range(4), dtype=np.int32)
+    f = np.asarray([0.0 if v is None else v for v in factors], dtype=np.float32)
+    return o, f, int(present), int(bool(photometric.get('grey')))
+
+
+def photometric_reference(crop, photometric, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    """``mas_photometric_reference``: the arithmetic of ``csrc/photometric.h`` as a host loop (no GPU) on a uint8 ``[h,w,3]`` numpy
+    crop -> (uint8 [h,w,3], float32 [3,h,w], the contrast L sum -- 0 without contrast)."""
+    crop = np.ascontiguousarray(crop, dtype=np.uint8)
+    h, w = crop.shape[:2]
+    o, f, present, grey = _chain_args(photometric)
+    mean, std = np.asarray(mean, dtype=np.float32), np.asarray(std, dtype=np.float32)
+    u8 = np.empty((h, w, 3), dtype=np.uint8)
+    f32 = np.empty((3, h, w), dtype=np.float32)
+    lsum = np.zeros(1, dtype=np.uint32)
+    _lib.check(_lib.load().mas_photometric_reference(crop.ctypes.data, h, w, o.ctypes.data, f.ctypes.data, present, grey, mean.ctypes.data,
+                                                     std.ctypes.data, u8.ctypes.data, f32.ctypes.data, lsum.ctypes.data),
+               "mas_photometric_reference")
+    return u8, f32, int(lsum[0])
+
+
+def photometric(crop, photometric, lsum=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), return_u8=False):
+    """``mas_photometric`` (pass 2 of the jittered path) on a uint8 ``[h,w,3]`` crop on the GPU; ``lsum``: the one-element device
+    accumulator pass 1 filled (needed when contrast is in the chain) -> float32 ``[3,h,w]`` (and the uint8 result when asked)."""
+    if not (crop.is_cuda and crop.dtype == torch.uint8 and crop.dim() == 3 and crop.shape[2] == 3 and crop.is_contiguous()):
+        raise ValueError("crop must be a contiguous uint8 [h,w,3] tensor on the GPU")
+    h, w = int(crop.shape[0]), int(crop.shape[1])
+    o, f, present, grey = _chain_args(photometric)
+    mean, std = np.asarray(mean, dtype=np.float32), np.asarray(std, dtype=np.float32)
+    out = torch.empty((3, h, w), dtype=torch.float32, device=crop.device)
+    u8 = torch.empty((h, w, 3), dtype=torch.uint8, device=crop.device) if return_u8 else None
+    with torch.cuda.device(crop.device):
+        st = torch.cuda.current_stream(crop.device).cuda_stream
+        _lib.check(_lib.load().mas_photometric(crop.data_ptr(), h, w, o.ctypes.data, f.ctypes.data, present, grey, mean.ctypes.data,
+                                               std.ctypes.data, None if lsum is None else lsum.data_ptr(), out.data_ptr(),
+                                               None if u8 is None else u8.data_ptr(), st), "mas_photometric")
+    return (out, u8) if return_u8 else out
+
+
+class DeviceTrainAugmentStrong(DeviceTrainAugment):
+    """``DeviceTrainAugment`` followed by ``ExtColorJitter(brightness, contrast, saturation, hue, p=p_jitter)`` and
+    ``ExtRandomGrayscale(p=p_gray)`` (reference ``transform.py:139-153``, the ``_strongv1`` names), bit-identical to torchvision
+    0.12 on the installed Pillow (``csrc/photometric.h``).  The geometry draws stay on ``rng`` (Python's ``random``); the photometric
+    draws follow them on ``torch_generator`` (``None``: torch's global CPU generator, as in the reference).  A sample that draws
+    neither op takes the parent's single launch; otherwise ``mas_train_augment_u8`` writes the u8 crop, the maps and (for contrast)
+    the L sum, and ``mas_photometric`` turns the crop into the normalised picture -- nothing comes back to the host in between.
+    ``params`` may carry the photometric draw under ``'photometric'`` (``draw_photometric``'s dictionary)."""
+
+    def __init__(self, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.1, p_jitter=0.2, p_gray=0.2, torch_generator=None, **kw):
+        super().__init__(**kw)
+        self.jitter = dict(brightness=brightness, contrast=contrast, saturation=saturation, hue=hue, p_jitter=p_jitter, p_gray=p_gray)
+        draw_photometric(torch.Generator().manual_seed(0), **self.jitter)          # refuse bad strengths here, not at the first sample
+        self.torch_generator = torch_generator
+
+    def _draw(self, H, W):
+        p = super()._draw(H, W)
+        p['photometric'] = draw_photometric(self.torch_generator, **self.jitter)
+        return p
+
+    def _with_photometric(self, params):
+        if params is not None and 'photometric' not in params:
+            params = dict(params, photometric=draw_photometric(self.torch_generator, **self.jitter))
+        return params
+
+    def augment_u8(self, img, maps=(), params=None):
+        """Pass 1 alone (``mas_train_augment_u8``) -> (crop uint8 [ch,cw,3], [maps], the one-element L accumulator -- ``None``
+        without contrast in the chain)."""
+        p, geom, margs, outs, tab = self._prepare(img, maps, self._with_photometric(params))
+        o, f, present, _ = _chain_args(p['photometric'])
+        ch, cw = self.size
+        crop = torch.empty((ch, cw, 3), dtype=torch.uint8, device=img.device)
+        lsum = torch.zeros(1, dtype=torch.int32, device=img.device) if (present >> _lib.PM_CONTRAST) & 1 else None
+        with torch.cuda.device(img.device):
+            st = torch.cuda.current_stream(img.device).cuda_stream
+            _lib.check(_lib.load().mas_train_augment_u8(*geom, self.fill.ctypes.data, *margs, o.ctypes.data, f.ctypes.data, present,
+                                                        crop.data_ptr(), None if lsum is None else lsum.data_ptr(), st),
+                       "mas_train_augment_u8")
+        tab.record_stream(torch.cuda.current_stream(img.device))
+        return crop, outs, lsum
+
+    def __call__(self, img, maps=(), params=None):
+        params = self._with_photometric(params)
+        if params is None:
+            params = self._draw(int(img.shape[0]), int(img.shape[1])) if img.dim() == 3 else None
+        ph = params['photometric'] if params is not None else None
+        if ph is None or not (_chain_args(ph)[2] or ph.get('grey')):          # the plain sample: today's single launch
+            return super().__call__(img, maps, params=params)
+        crop, outs, lsum = self.augment_u8(img, maps, params)
+        return photometric(crop, ph, lsum, self.mean, self.std), outs          # (crop and sum live on the stream both passes use)
 
 
 class DeviceMultiScaleFlip(DeviceTrainAugment):

@@ -5,11 +5,21 @@
 called as ``transform(picture u8 [H,W,3] cuda, [maps]) -> (image f32 [3,h,w], [maps])``; ``transform.n_maps`` says how many maps
 it pads (``ExtRandomCrop.pad_values``; the reference asserts the same count, ``ext_transforms.py:489``).
 
+The suffix ``_strongv1`` adds the reference's photometric stage after crop and flip -- ``ExtColorJitter(0.4, 0.4, 0.4, 0.1, p=0.2)``
+then ``ExtRandomGrayscale(p=0.2)`` (``transform.py:139-153``) -- to the crops above: ``DeviceTrainAugmentStrong``,
+``csrc/photometric.hip``, bit-identical to torchvision 0.12 on the installed Pillow (12.2.0 is what the tests pin; the reference
+pins 9.2.0).  The geometry draws stay on Python's ``random``, the photometric draws come from torch's global CPU generator, as in
+the reference.  ``rescale_769_multi_notrg_ignore_strongv1`` is the reference's own name; the other ``_strongv1`` names apply the
+same stage to the other built crops.
+
 Not offered (outside the production configurations): the unpadded 512x1024 crops (``orig_*``, ``rescale``), ``load_smaller_spx``
-(a third map), the colour-jitter variant.  ``eval_spx_identity`` (VOC) keeps the picture and its two maps at their own size;
+(a third map).  ``eval_spx_identity`` (VOC) keeps the picture and its two maps at their own size;
 ``eval_spx_identity_ms`` (VOC) returns a LIST of ten pictures (five scales, then the same
 flipped) and takes no map (``n_maps == 0``)."""
-from .device_transforms import DeviceIdentity, DeviceMultiScaleFlip, DeviceResize, DeviceResizeFlip, DeviceResizeThreeMaps, DeviceTrainAugment
+from .device_transforms import (DeviceIdentity, DeviceMultiScaleFlip, DeviceResize, DeviceResizeFlip, DeviceResizeThreeMaps, DeviceTrainAugment,
+                                DeviceTrainAugmentStrong)
+
+STRONG_V1 = dict(brightness=0.4, contrast=0.4, saturation=0.4, hue=0.1, p_jitter=0.2, p_gray=0.2)
 
 
 def _with_maps(t, n):
@@ -23,7 +33,10 @@ def _no_small(args, name):
 
 
 def get_train_transform(args, transform):
-    """Cityscapes: 768x768 crops of a U(0.5, 2) rescale, padded with (124, 116, 104) / the per-map pad values."""
+    """Cityscapes: 768x768 crops of a U(0.5, 2) rescale, padded with (124, 116, 104) / the per-map pad values.  ``*_strongv1``: the
+    same crop followed by colour jitter and grayscale.  ``rescale_769_multi_notrg_ignore_strongv1`` is the reference's name; there it
+    ASSERTS ``--load_smaller_spx`` and pads a third map (the smaller superpixels), which is not built: here the name takes the two
+    maps [label padded with 0, superpixel] and refuses ``--load_smaller_spx`` like every other name."""
     if transform is None:
         return None
     crop = dict(size=(768, 768), scale_range=(0.5, 2.0))
@@ -40,6 +53,23 @@ def get_train_transform(args, transform):
     if transform == 'rescale_769_multi_notrg_ignore':               # [label padded with 0, superpixel]
         _no_small(args, transform)
         return _with_maps(DeviceTrainAugment(pad_values=[0, args.nseg], **crop), 2)
+    strong = dict(crop, **STRONG_V1)                                # + ExtColorJitter(0.4, 0.4, 0.4, 0.1, p=0.2), ExtRandomGrayscale(p=0.2)
+    if transform == 'rescale_769_nospx_strongv1':
+        return _with_maps(DeviceTrainAugmentStrong(pad_values=[args.ignore_idx], **strong), 1)
+    if transform == 'rescale_769_strongv1':
+        return _with_maps(DeviceTrainAugmentStrong(pad_values=[args.ignore_idx, args.nseg], **strong), 2)
+    if transform == 'rescale_769_multi_strongv1':
+        _no_small(args, transform)
+        return _with_maps(DeviceTrainAugmentStrong(pad_values=[args.ignore_idx, args.nseg], **strong), 2)
+    if transform == 'rescale_769_multi_notrg_strongv1':
+        _no_small(args, transform)
+        return _with_maps(DeviceTrainAugmentStrong(pad_values=[args.nseg], **strong), 1)
+    if transform == 'rescale_769_multi_notrg_ignore_strongv1':
+        # The reference's name (transform.py:139-153).  The reference ASSERTS --load_smaller_spx there and pads a third map
+        # (the smaller superpixels); that map is not built, so the name is offered with the two maps [label padded with 0,
+        # superpixel] of 'rescale_769_multi_notrg_ignore' and --load_smaller_spx is refused as for every other name.
+        _no_small(args, transform)
+        return _with_maps(DeviceTrainAugmentStrong(pad_values=[0, args.nseg], **strong), 2)
     if transform == 'eval_spx':                                     # ExtResize((1024, 2048)), two maps
         return _with_maps(DeviceResize((1024, 2048), pad_values=[args.ignore_idx, args.nseg]), 2)
     if transform == 'eval_dom_gt_spx':                              # ExtResize((1024, 2048)), three maps: dominant target, label, ids
@@ -61,6 +91,14 @@ def get_train_transform_voc(args, transform):
     if transform == 'rescale_513_multi_notrg':                      # [superpixel]
         _no_small(args, transform)
         return _with_maps(DeviceTrainAugment(pad_values=[args.nseg], **crop), 1)
+    strong = dict(crop, **STRONG_V1)                                # the photometric stage of the Cityscapes '_strongv1' names
+    if transform == 'rescale_513_notrg_strongv1':
+        return _with_maps(DeviceTrainAugmentStrong(pad_values=[args.ignore_idx], **strong), 1)
+    if transform == 'rescale_513_strongv1':
+        return _with_maps(DeviceTrainAugmentStrong(pad_values=[args.ignore_idx, args.nseg], **strong), 2)
+    if transform == 'rescale_513_multi_notrg_strongv1':
+        _no_small(args, transform)
+        return _with_maps(DeviceTrainAugmentStrong(pad_values=[args.nseg], **strong), 1)
     if transform == 'eval_spx':
         return _with_maps(DeviceResize(513, center_crop=513, pad_values=[args.ignore_idx, args.nseg]), 2)
     if transform == 'eval_spx_identity':                            # ToTensor + Normalize at the picture's own size, [label, superpixel]
