@@ -57,7 +57,8 @@ extern "C" {
  * mas_spx_max_onehot came later under 9, then mas_lowres_iou_counts, then mas_render_labels and mas_render_lowres_pred, then mas_ms_naive_plbl, then mas_ms_iou_counts and
  * mas_ms_iou_lds_bytes, then mas_candidate_plbl and mas_stage2_assign_labels, then mas_uncertainty_accum,
  * mas_uncertainty_accum_lowres and mas_uncertainty_reference, then mas_train_augment_u8, mas_photometric and
- * mas_photometric_reference: new entry
+ * mas_photometric_reference, then mas_partial_loss_reference and the MAS_LOSS_RC / MAS_LOSS_TOPONE flag bits (a library built before
+ * them treats the bits as unset): new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -115,6 +116,12 @@ int mas_region_finalize(const uint64_t* score_sum, const uint32_t* hist, int64_t
 #define MAS_LOSS_DECOMP 8           /* separate one-hot (ce) / multi-hot (mc) sums and normalisers
                                        (OnehotCEMultihotChoice, ..._lossdecomp.py:58-72); otherwise one
                                        merged sum (MultiChoiceCE_, active_joint_multi_predignore.py:59-61) */
+/* The term of a MULTI-HOT pixel inside the CE sums (csrc/partial_label.h is the arithmetic; one-hot pixels are the same in all three):
+ * neither bit = the merged positive -log sum_{c in Y} p_c.  Valid only with MAS_LOSS_CE; both bits at once, or either with
+ * MAS_LOSS_TCE, is MAS_ERR_RANGE before anything is launched.  Without MAS_LOSS_DECOMP the term goes into the merged sum
+ * (RCMultiChoiceCE, utils/loss.py:653-707).  The group flags combine freely. */
+#define MAS_LOSS_RC 32              /* risk-consistent weighting: sum_{c in Y} w_c * -log p_c, w_c = p_c / sum_Y p (detached) */
+#define MAS_LOSS_TOPONE 64          /* top-1 candidate: -log max_{c in Y} p_c (trainer/active_joint_multi_lossdecomp_topone.py) */
 
 /* layout of the caller-zeroed accumulator `acc` (8 x uint64) */
 #define MAS_ACC_SUM_CE 0     /* fixed point, 32 fractional bits */
@@ -208,6 +215,15 @@ int mas_partial_loss_fwd_fused(const float* z, int h, int w, const void* spx, in
 int mas_partial_loss_bwd_fused(const float* z, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits,
                                const void* work, const float* grad, const float* weights, int N, int C, int H, int W, int S, float invT,
                                int flags, float* dz, int64_t* dzq_fix, void* stream);
+
+/* The CPU-side statement of csrc/partial_label.h: every pointer is a HOST pointer, no device is touched.  A plain loop over the selected
+ * pixels for the CE-family flags (MAS_LOSS_CE, optionally with MAS_LOSS_DECOMP and one of MAS_LOSS_RC / MAS_LOSS_TOPONE; any other bit
+ * is MAS_ERR_RANGE).  Adds into acc[0..4] (caller-zeroed) what mas_partial_loss_fwd adds; losses [3] (may be NULL) = mas_loss_values of
+ * acc; dz [N,C,H,W] (may be NULL; needs grad_out [3]) = what mas_loss_scales + mas_partial_loss_bwd write.  The kernels are tested
+ * against it bit for bit. */
+int mas_partial_loss_reference(const float* z, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits, int N, int C,
+                               int H, int W, int S, float invT, int flags, const float* grad_out /* [3] or NULL */,
+                               uint64_t* acc /* [8] += */, float* losses /* [3] or NULL */, float* dz /* or NULL */);
 
 /* =============================================================================================
  * K4  ordering of the region scores and the budgeted selection walk

@@ -16,6 +16,7 @@ MAX_CLASSES = 32
 LABELS_BAD_VALUE = 1
 SCORE_FRAC, PROB_FRAC, LOSS_FRAC = 40, 23, 32
 LOSS_CE, LOSS_GROUP, LOSS_GROUP_ONLY_MULTI, LOSS_DECOMP, LOSS_TCE = 1, 2, 4, 8, 16
+LOSS_RC, LOSS_TOPONE = 32, 64       # the multi-hot pixel term of the CE sums (csrc/partial_label.h); neither = the merged positive
 ACC_WORDS = 8
 GRAD_FRAC = 44
 MS_MAX_SOURCES = 16
@@ -159,6 +160,7 @@ SIGNATURES = {
     "mas_fix_to_float": (_i, [_vp, _i64, _i, _vp, _vp]),
     "mas_partial_loss_work_bytes": (_c.c_size_t, [_i, _i, _i, _i]),
     "mas_partial_loss_fwd_fused": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _c.c_size_t, _vp, _vp]),
+    "mas_partial_loss_reference": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
     "mas_adamw_job_bytes": (_c.c_size_t, []),
     "mas_adamw_max_groups": (_i, []),
     "mas_adamw_job": (_c.c_uint, [_vp, _vp, _vp, _vp, _vp, _c.c_longlong, _i, _c.c_uint]),

@@ -10,11 +10,16 @@
 //   k_loss_scales        upstream gradients / (1 + n) -> per-loss scale factors (no host sync).
 //   k_partial_loss_bwd   one pass writing dz[N,C,H,W] completely (zeros off-mask), softmax recomputed,
 //                        group-loss gradient gathered from the arg-pixel table (no atomics).
+//   PLX instantiations of both scans: the multi-hot pixel term is the risk-consistent (MAS_LOSS_RC) or the top-1 candidate
+//                        (MAS_LOSS_TOPONE) formula of partial_label.h instead of the merged positive; chosen at launch, so the
+//                        merged-positive kernels carry nothing of it.
+//   mas_partial_loss_reference   the CE-family sums and dz on HOST pointers, a plain loop through partial_label.h.
 //
 // Reference semantics: trainer/active_joint_multi_predignore_lossdecomp.py:21-72 (OnehotCEMultihotChoice),
 // trainer/active_joint_multi_predignore_mclossablation2.py:22-79 (GroupMultiLabelCE_onlymulti),
 // trainer/active_joint_multi_predignore.py:21-128, utils/loss.py:91-141,543-588 (base classes).
 #include "common.h"
+#include "partial_label.h"
 
 namespace {
 
@@ -166,7 +171,7 @@ __device__ __forceinline__ void tile_compact(const unsigned char* __restrict__ m
     }
 }
 
-template <int CT, bool EXACT, typename IdT, bool VEC, bool LOWRES>
+template <int CT, bool EXACT, typename IdT, bool VEC, bool LOWRES, bool PLX>
 __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __restrict__ z, const IdT* __restrict__ spx,
                                                                 const unsigned char* __restrict__ mask,
                                                                 const unsigned* __restrict__ bits, int C, int H, int W, int S,
@@ -183,6 +188,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
     const bool do_group = flags & MAS_LOSS_GROUP;
     const bool only_multi = flags & MAS_LOSS_GROUP_ONLY_MULTI;
     const bool tce = flags & MAS_LOSS_TCE;          // `spx` holds class labels, the target of a pixel is its label, no epsilon
+    const int pl_mode = PLX ? mas_pl_mode(flags) : MAS_PL_CHOICE;      // (PLX: rc or topone, never combined with tce)
     if (threadIdx.x == 0) *qcount = 0;
     if (do_group) {
         for (int i = threadIdx.x; i < kSlots; i += kThreads) t_keys[i] = -1;
@@ -226,7 +232,10 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
 #pragma unroll
             for (int c = 0; c < CT; ++c) v[c] = v[c] * rinv;
         }
-        if (do_ce) {
+        if (PLX && do_ce && nb > 1) {
+            sum_mc += mas_fix(mas_pl_loss(v, CT, EXACT ? CT : C, Y, pl_mode), MAS_LOSS_FRAC);
+            n_mc += 1;
+        } else if (do_ce) {
             float pos = 0.0f;
 #pragma unroll
             for (int c = 0; c < CT; ++c)
@@ -278,7 +287,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
 // acc[ACC_DONE]: workgroups of k_group_finalize that have added their sums (the fused entry point: the LAST one turns the sums into
 // the loss values -- no k_loss_values launch)
 constexpr int ACC_DONE = 7;
-__device__ __forceinline__ void loss_values_of(const mas_u64* acc, int flags, const float* w, float* out);
+__host__ __device__ __forceinline__ void loss_values_of(const mas_u64* acc, int flags, const float* w, float* out);
 
 __global__ __launch_bounds__(kThreads) void k_group_finalize(const mas_u64* __restrict__ gmax, long long n_entries,
                                                               mas_u64* __restrict__ acc, int flags, const float* __restrict__ w,
@@ -341,7 +350,7 @@ __global__ __launch_bounds__(kThreads) void k_loss_prep(mas_u64* __restrict__ ze
 
 // loss = (sum * 2^-32) / (1 + n) in f64, rounded once to f32; MAS_LOSS_TCE: the plain mean, / n (0 / 0 = NaN as torch's
 // CrossEntropyLoss over no valid pixel)
-__device__ __forceinline__ float loss_value(mas_u64 sum, mas_u64 n, int one = 1) {
+__host__ __device__ __forceinline__ float loss_value(mas_u64 sum, mas_u64 n, int one = 1) {
     union { double d; mas_u64 u; } s;
     s.u = (mas_u64)(1023 - MAS_LOSS_FRAC) << 52;
     return (float)(((double)sum * s.d) / (double)(n + one));
@@ -350,7 +359,7 @@ __device__ __forceinline__ float loss_value(mas_u64 sum, mas_u64 n, int one = 1)
 // losses[0..2] = (ce, mc, group); with weights also losses[3] = (w_ce * ce + w_mc * mc) + w_group * group, every product and sum
 // rounded once in f32 -- the operation order of `coeff * ce_loss + coeff_mc * mc_loss + coeff_gm * group_loss`
 // (trainer/active_joint_multi_predignore_lossdecomp.py:104), so the value equals the torch expression bit for bit.
-__device__ __forceinline__ void loss_values_of(const mas_u64* acc, int flags, const float* w, float* out) {
+__host__ __device__ __forceinline__ void loss_values_of(const mas_u64* acc, int flags, const float* w, float* out) {
     if (flags & MAS_LOSS_TCE) {
         out[0] = loss_value(acc[ACC_SUM_CE], acc[ACC_N_CE], 0);
         out[1] = 0.0f;
@@ -385,7 +394,7 @@ __global__ void k_loss_values_weighted(const mas_u64* __restrict__ acc, int flag
 
 // scale_k = upstream_k / (1 + n_k) (f32 division, correctly rounded); with weights: grad[0] is dL/dtotal and
 // scale_k = (dL/dtotal * w_k) / (1 + n_k) -- the chain rule through the weighted sum, in the order autograd applies it
-__device__ __forceinline__ void loss_scales_of(const mas_u64* acc, const float* grad, const float* w, int flags, float* scale) {
+__host__ __device__ __forceinline__ void loss_scales_of(const mas_u64* acc, const float* grad, const float* w, int flags, float* scale) {
     if (flags & MAS_LOSS_TCE) {
         scale[0] = (w ? grad[0] * w[0] : grad[0]) / (float)acc[ACC_N_CE];
         scale[1] = 0.0f;
@@ -420,7 +429,7 @@ __global__ void k_loss_scales(const mas_u64* __restrict__ acc, const float* __re
 // selected pixel adds (gradient of its class-c logit) * (bilinear weight) into the four quarter-resolution elements its
 // logits were interpolated from -- integer atomics, so the sums do not depend on the order; nothing is written at full
 // resolution.
-template <int CT, bool EXACT, typename IdT, bool VEC, bool LOWRES>
+template <int CT, bool EXACT, typename IdT, bool VEC, bool LOWRES, bool PLX>
 __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __restrict__ z, const IdT* __restrict__ spx,
                                                                 const unsigned char* __restrict__ mask,
                                                                 const unsigned* __restrict__ bits,
@@ -439,6 +448,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
     const bool do_ce = flags & MAS_LOSS_CE;
     const bool do_group = flags & MAS_LOSS_GROUP;
     const bool only_multi = flags & MAS_LOSS_GROUP_ONLY_MULTI;
+    const int pl_mode = PLX ? mas_pl_mode(flags) : MAS_PL_CHOICE;
     if (threadIdx.x == 0) qcount[0] = 0;
     __syncthreads();
     int bid = blockIdx.x;
@@ -498,7 +508,12 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
             for (int c = 0; c < CT; ++c) v[c] = v[c] * rinv;
         }
         float coef = 0.0f, pos = 0.0f;
-        if (do_ce) {
+        // PLX: the multi-hot pixel's CE coefficients come from partial_label.h (rc / topone); one-hot pixels keep the arithmetic below
+        const bool plx = PLX && do_ce && nb > 1;
+        mas_pl_grad_ctx gk = {};
+        if (plx) {
+            gk = mas_pl_grad_prepare(v, CT, EXACT ? CT : C, Y, pl_mode, a_mc);
+        } else if (do_ce) {
 #pragma unroll
             for (int c = 0; c < CT; ++c)
                 if (EXACT || c < C) pos = ((Y >> c) & 1u) ? (pos + v[c]) : pos;
@@ -530,6 +545,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
                 const float p = v[c];
                 const float yj = ((Y >> c) & 1u) ? 1.0f : 0.0f;
                 float d = coef * (p * (pos - yj));
+                if (plx) d = mas_pl_grad(gk, pl_mode, p, (int)((Y >> c) & 1u), c);
                 if (A) {
                     if ((A >> c) & 1u) d = d + t[c] * p;
                     d = d - p * u;
@@ -572,7 +588,7 @@ struct LossArgs {
     const float* grad = nullptr; const float* gw = nullptr;     // backward with scale == NULL: upstream gradient(s) and optional weights
 };
 
-template <int CT, bool EXACT, typename IdT>
+template <int CT, bool EXACT, typename IdT, bool PLX>
 int launch_loss(const LossArgs& a, bool backward, hipStream_t st) {
     const int tiles_x = (a.W + kTileW - 1) / kTileW;
     const int tiles_y = (a.H + kTileH - 1) / kTileH;
@@ -586,10 +602,10 @@ int launch_loss(const LossArgs& a, bool backward, hipStream_t st) {
 #define MAS_LAUNCH_LOSS(VECV, LOWV)                                                                                                     \
     do {                                                                                                                                \
         if (!backward)                                                                                                                  \
-            hipLaunchKernelGGL((k_partial_loss_fwd<CT, EXACT, IdT, VECV, LOWV>), grid, block, fwd_smem_bytes(a.C), st, a.z, ids, a.mask, \
+            hipLaunchKernelGGL((k_partial_loss_fwd<CT, EXACT, IdT, VECV, LOWV, PLX>), grid, block, fwd_smem_bytes(a.C), st, a.z, ids, a.mask, \
                                a.bits, a.C, a.H, a.W, a.S, a.invT, a.flags, tiles_x, tiles_y, a.gmax, a.acc, lr);                        \
         else                                                                                                                            \
-            hipLaunchKernelGGL((k_partial_loss_bwd<CT, EXACT, IdT, VECV, LOWV>), grid, block, 0, st, a.z, ids, a.mask, a.bits, a.gmax,   \
+            hipLaunchKernelGGL((k_partial_loss_bwd<CT, EXACT, IdT, VECV, LOWV, PLX>), grid, block, 0, st, a.z, ids, a.mask, a.bits, a.gmax, \
                                a.scale, a.C, a.H, a.W, a.S, a.invT, a.flags, tiles_x, tiles_y, a.dz, lr, a.acc, a.grad, a.gw);           \
     } while (0)
     if (low) { if (vec) MAS_LAUNCH_LOSS(true, true); else MAS_LAUNCH_LOSS(false, true); }
@@ -600,15 +616,27 @@ int launch_loss(const LossArgs& a, bool backward, hipStream_t st) {
 
 template <int CT, bool EXACT>
 int dispatch_loss_ids(const LossArgs& a, int spx_dtype, bool backward, hipStream_t st) {
+    // the rc / topone multi-hot term is compiled into instantiations of its own (PLX): the merged-positive kernels stay as they were
+    const bool plx = (a.flags & (MAS_LOSS_RC | MAS_LOSS_TOPONE)) != 0;
+#define MAS_LOSS_BY_MODE(IDT) (plx ? launch_loss<CT, EXACT, IDT, true>(a, backward, st) : launch_loss<CT, EXACT, IDT, false>(a, backward, st))
     switch (spx_dtype) {
-        case MAS_ID_I64: return launch_loss<CT, EXACT, long long>(a, backward, st);
-        case MAS_ID_I32: return launch_loss<CT, EXACT, int>(a, backward, st);
-        case MAS_ID_U16: return launch_loss<CT, EXACT, unsigned short>(a, backward, st);
+        case MAS_ID_I64: return MAS_LOSS_BY_MODE(long long);
+        case MAS_ID_I32: return MAS_LOSS_BY_MODE(int);
+        case MAS_ID_U16: return MAS_LOSS_BY_MODE(unsigned short);
         default: return MAS_ERR_DTYPE;
     }
+#undef MAS_LOSS_BY_MODE
+}
+
+// MAS_LOSS_RC / MAS_LOSS_TOPONE name the multi-hot term of the CE sums: one of them at most, with MAS_LOSS_CE, never with MAS_LOSS_TCE
+inline bool loss_flags_ok(int flags) {
+    const int m = flags & (MAS_LOSS_RC | MAS_LOSS_TOPONE);
+    if (!m) return true;
+    return m != (MAS_LOSS_RC | MAS_LOSS_TOPONE) && (flags & MAS_LOSS_CE) && !(flags & MAS_LOSS_TCE);
 }
 
 int dispatch_loss(const LossArgs& a, int spx_dtype, bool backward, hipStream_t st) {
+    if (!loss_flags_ok(a.flags)) return MAS_ERR_RANGE;
     if (a.N <= 0 || a.H <= 0 || a.W <= 0 || a.S <= 0 || (long long)a.H * a.W > 0x7fffffffLL / 2) return MAS_ERR_SHAPE;
     if (a.C < 2 || a.C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
     switch (a.C) {
@@ -763,6 +791,7 @@ extern "C" int mas_partial_loss_fwd_fused(const float* z, int h, int w, const vo
                                           int W, int S, float invT, int flags, const float* weights, void* work, size_t work_bytes,
                                           float* losses, void* stream) {
     if (!z || !spx || !mask || !work || (!targets && !bits)) return MAS_ERR_NULL;
+    if (!loss_flags_ok(flags)) return MAS_ERR_RANGE;
     if (N <= 0 || S <= 0 || H <= 0 || W <= 0) return MAS_ERR_SHAPE;
     if (C < 2 || C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
     if ((h > 0) != (w > 0) || h > H || w > W) return MAS_ERR_SHAPE;
@@ -800,6 +829,7 @@ extern "C" int mas_partial_loss_bwd_fused(const float* z, int h, int w, const vo
                                           const void* work, const float* grad, const float* weights, int N, int C, int H, int W, int S,
                                           float invT, int flags, float* dz, int64_t* dzq_fix, void* stream) {
     if (!z || !spx || !mask || !work || !grad || !dz) return MAS_ERR_NULL;
+    if (!loss_flags_ok(flags)) return MAS_ERR_RANGE;
     if (N <= 0 || S <= 0 || H <= 0 || W <= 0) return MAS_ERR_SHAPE;
     if (C < 2 || C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
     const bool low = h > 0;
@@ -823,6 +853,69 @@ extern "C" int mas_partial_loss_bwd_fused(const float* z, int h, int w, const vo
         hipLaunchKernelGGL(k_fix_to_float, dim3((unsigned)((nq + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
                            reinterpret_cast<const long long*>(dzq_fix), (long long)nq, MAS_GRAD_FRAC, dz);
         return mas_launch_status();
+    }
+    return 0;
+}
+
+// ---- the CPU-side statement of the spec: host pointers, a plain loop over the pixels through partial_label.h.  No device is touched.
+// CE-family flags only (MAS_LOSS_CE with MAS_LOSS_DECOMP / MAS_LOSS_RC / MAS_LOSS_TOPONE); softmax in the operation order of
+// mas_softmax_regs (common.h).  acc[0..4] are added to; losses (optional) = mas_loss_values(acc); dz (optional, with grad_out) = what
+// mas_loss_scales + mas_partial_loss_bwd write.
+extern "C" int mas_partial_loss_reference(const float* z, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits, int N,
+                                          int C, int H, int W, int S, float invT, int flags, const float* grad_out, uint64_t* acc,
+                                          float* losses, float* dz) {
+    if (!z || !spx || !mask || !bits || !acc || (dz && !grad_out)) return MAS_ERR_NULL;
+    if (N <= 0 || H <= 0 || W <= 0 || S <= 0 || (long long)H * W > 0x7fffffffLL / 2) return MAS_ERR_SHAPE;
+    if (C < 2 || C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
+    if (spx_dtype != MAS_ID_I64 && spx_dtype != MAS_ID_I32 && spx_dtype != MAS_ID_U16) return MAS_ERR_DTYPE;
+    if (!(flags & MAS_LOSS_CE) || (flags & ~(MAS_LOSS_CE | MAS_LOSS_DECOMP | MAS_LOSS_RC | MAS_LOSS_TOPONE)) || !loss_flags_ok(flags))
+        return MAS_ERR_RANGE;
+    const int mode = mas_pl_mode(flags);
+    const size_t HW = (size_t)H * W;
+    mas_u64* a64 = reinterpret_cast<mas_u64*>(acc);
+    for (int pass = 0; pass < (dz ? 2 : 1); ++pass) {
+        float sc3[3] = {0.f, 0.f, 0.f};
+        if (pass == 1) {
+            loss_scales_of(a64, grad_out, nullptr, flags, sc3);
+            for (size_t i = 0; i < (size_t)N * C * HW; ++i) dz[i] = 0.0f;
+        }
+        const float a_ce = sc3[0] * invT, a_mc = sc3[1] * invT;
+        for (int n = 0; n < N; ++n) {
+            for (size_t i = 0; i < HW; ++i) {
+                const size_t g = (size_t)n * HW + i;
+                if (!mask[g]) continue;
+                long long id;
+                if (spx_dtype == MAS_ID_I64) id = static_cast<const long long*>(spx)[g];
+                else if (spx_dtype == MAS_ID_I32) id = static_cast<const int*>(spx)[g];
+                else id = static_cast<const unsigned short*>(spx)[g];
+                if (id < 0 || id >= S) continue;
+                const uint32_t Y = bits[(size_t)n * S + (size_t)id];
+                const int nb = mas_pl_popcount(Y);
+                if (nb == 0) { if (pass == 0) a64[ACC_N_EMPTY] += 1; continue; }
+                float p[MAS_MAX_CLASSES];
+                const float* zp = z + (size_t)n * C * HW + i;
+                float m = zp[0];
+                for (int c = 1; c < C; ++c) m = (zp[c * HW] > m) ? zp[c * HW] : m;
+                const float negM = -(m * invT);
+                float sum = 0.0f;
+                for (int c = 0; c < C; ++c) {
+                    p[c] = mas_expf_np(mas_fmaf(zp[c * HW], invT, negM));
+                    sum = (c == 0) ? p[c] : (sum + p[c]);
+                }
+                const float rinv = 1.0f / sum;
+                for (int c = 0; c < C; ++c) p[c] = p[c] * rinv;
+                const int pm = nb == 1 ? MAS_PL_CHOICE : mode;
+                if (pass == 0) {
+                    const mas_u64 q = mas_fix(mas_pl_loss(p, C, C, Y, pm), MAS_LOSS_FRAC);
+                    if (nb == 1) { a64[ACC_SUM_CE] += q; a64[ACC_N_CE] += 1; } else { a64[ACC_SUM_MC] += q; a64[ACC_N_MC] += 1; }
+                } else {
+                    const mas_pl_grad_ctx gk = mas_pl_grad_prepare(p, C, C, Y, pm, nb == 1 ? a_ce : a_mc);
+                    for (int c = 0; c < C; ++c)
+                        dz[((size_t)n * C + c) * HW + i] = mas_pl_grad(gk, pm, p[c], (int)((Y >> c) & 1u), c);
+                }
+            }
+        }
+        if (pass == 0 && losses) loss_values_of(a64, flags, nullptr, losses);
     }
     return 0;
 }

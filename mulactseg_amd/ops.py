@@ -238,6 +238,41 @@ def partial_loss_bwd_lowres(zq, size, spx, mask, bits, gmax, acc, grad_out, invT
     return _partial_loss_bwd(zq, size, spx, mask, bits, gmax, acc, grad_out, invT, flags, want_fix, weights)
 
 
+# `flags` of the partial-label entry points (MAS_LOSS_* of include/mulactseg_hip.h); LOSS_RC / LOSS_TOPONE: csrc/partial_label.h
+LOSS_CE, LOSS_GROUP, LOSS_GROUP_ONLY_MULTI, LOSS_DECOMP, LOSS_TCE = (_lib.LOSS_CE, _lib.LOSS_GROUP, _lib.LOSS_GROUP_ONLY_MULTI,
+                                                                    _lib.LOSS_DECOMP, _lib.LOSS_TCE)
+LOSS_RC, LOSS_TOPONE = _lib.LOSS_RC, _lib.LOSS_TOPONE
+
+
+def partial_loss_reference(z, spx, mask, bits, invT, flags, grad_out=None):
+    """The CE-family sums and the full-resolution gradient on HOST tensors: the library's plain loop over the selected pixels through
+    csrc/partial_label.h (``mas_partial_loss_reference``), the CPU-side statement of the arithmetic the scans are checked against.
+    ``flags``: LOSS_CE, optionally with LOSS_DECOMP and one of LOSS_RC / LOSS_TOPONE.  Returns (losses f32[3], acc i64[8]) and, with
+    ``grad_out`` (f32[3], the upstream gradients of (ce, mc, group)), dz [N,C,H,W] as a third value.  Needs no GPU."""
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    for t, name, dt in ((z, "z", torch.float32), (spx, "spx", None), (mask, "mask", torch.uint8), (bits, "bits", torch.int32),
+                        (grad_out, "grad_out", torch.float32)):
+        if t is None:
+            continue
+        if t.is_cuda or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous host tensor" % name)
+        if dt is not None and t.dtype != dt:
+            raise TypeError("%s must be %s, got %s" % (name, dt, t.dtype))
+    N, C, H, W = z.shape
+    S = bits.shape[1]
+    if tuple(spx.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W) or bits.shape[0] != N:
+        raise ValueError("shape mismatch between inputs %s, superpixels %s, spmasks %s, targets %s"
+                         % (tuple(z.shape), tuple(spx.shape), tuple(mask.shape), tuple(bits.shape)))
+    acc = torch.zeros(_lib.ACC_WORDS, dtype=torch.int64)
+    losses = torch.zeros(3, dtype=torch.float32)
+    dz = torch.empty_like(z) if grad_out is not None else None
+    _lib.check(_lib.load().mas_partial_loss_reference(z.data_ptr(), spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), N, C, H, W,
+                                                      S, invT, flags, _opt(grad_out), acc.data_ptr(), losses.data_ptr(), _opt(dz)),
+               "mas_partial_loss_reference")
+    return (losses, acc) if dz is None else (losses, acc, dz)
+
+
 class LossState:
     """What a fused forward leaves for its backward: the work buffer (accumulators | arg-pixel table | target bit masks) and views."""
     __slots__ = ("work", "acc", "gmax", "bits", "N", "S", "C", "flags")

@@ -9,9 +9,13 @@ re-compute the softmax; by default (``args.lowres_loss``, True) the scans take t
 evaluate the final x4 bilinear upsampling (``models/segmentation/utils.py:25``) per selected pixel.  Under data parallelism the normalisers ``1 + n`` are global over the batch
 (SURVEY.md section 5.8): the fixed-point sums and counts are all-reduced before the division so that
 N GPUs x batch 4 optimise exactly the single-GPU objective of batch 4N.
+
+``--partial_loss rc|topone`` swaps the term of the multi-hot pixels (``mc``) for the risk-consistent weighting or the top-1 candidate
+(``csrc/partial_label.h``); ``ce`` and ``group`` stay, and so do the scans.
 """
 
-from ..utils.loss import FusedPartialLabelLoss, GroupMultiLabelCE_onlymulti, OnehotCEMultihotChoice
+from ..utils.loss import (FusedPartialLabelLoss, GroupMultiLabelCE_onlymulti, OnehotCEMultihotChoice, OnehotCEMultihotRC,
+                          OnehotCEMultihotTopone)
 from . import active_joint_multi_predignore
 
 
@@ -20,11 +24,13 @@ class ActiveTrainer(active_joint_multi_predignore.ActiveTrainer):
         a = self.args
         # the reference's two modules stay available under their names (drop-in surface) ...
         self.group_multi_loss = GroupMultiLabelCE_onlymulti(args=a, num_class=self.num_classes, num_superpixel=a.nseg, temperature=a.group_ce_temp)
-        self.multi_pos_loss = OnehotCEMultihotChoice(num_class=self.num_classes, temperature=a.multi_ce_temp)
+        multi_hot = getattr(a, 'partial_loss', 'choice')
+        decomp = {'choice': OnehotCEMultihotChoice, 'rc': OnehotCEMultihotRC, 'topone': OnehotCEMultihotTopone}[multi_hot]
+        self.multi_pos_loss = decomp(num_class=self.num_classes, temperature=a.multi_ce_temp)
         # ... and train_impl uses the fused scan when both temperatures agree (they do in every script)
         self.fused_loss = None
         if a.group_ce_temp == a.multi_ce_temp:
-            self.fused_loss = FusedPartialLabelLoss(a.nseg, a.group_ce_temp, a.multi_ce_temp, only_multi=True, decomp=True)
+            self.fused_loss = FusedPartialLabelLoss(a.nseg, a.group_ce_temp, a.multi_ce_temp, only_multi=True, decomp=True, multi_hot=multi_hot)
 
     def losses(self, preds, labels, superpixels, spmasks):
         if self.fused_loss is not None:

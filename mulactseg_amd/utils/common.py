@@ -85,6 +85,9 @@ def get_parser():
     a("--coeff_mc", type=float, default=1.0)
     a("--coeff_gm", type=float, default=1.0)
     a("--loss_type", type=str, default='cross_entropy')
+    a("--partial_loss", default='choice', choices=['choice', 'rc', 'topone'],
+      help="term of a multi-hot pixel in the lossdecomp trainers: the reference's -log sum_Y p, the risk-consistent weighting, "
+           "or -log max_Y p")
     # active learning
     a("--seed", type=int, default=0)
     a("--start_over", action='store_true', default=False)
@@ -229,6 +232,10 @@ def preprocess(args):
         assert 'ignore' in args.loader
 
 
+# the trainers whose multi-hot term --partial_loss swaps (the group term stays)
+PARTIAL_LOSS_METHODS = ('active_joint_multi_predignore_lossdecomp', 'active_joint_multi_lossdecomp')
+
+
 def arg_assert(args):
     """Consistency of the flags -- ``utils/common.py:205-231``."""
     assert args.init_checkpoint is not None
@@ -247,6 +254,9 @@ def arg_assert(args):
     if getattr(args, 'uncertainty', 'bvsb') != 'bvsb' and getattr(args, 'two_pass_scoring', False):
         raise ValueError("--uncertainty %s needs the single-pass round: the two-pass kernels (two_pass_scoring) know BvSB only"
                          % args.uncertainty)
+    if getattr(args, 'partial_loss', 'choice') != 'choice' and args.method not in PARTIAL_LOSS_METHODS:
+        raise NotImplementedError("--partial_loss %s is honoured by --method %s only (got %s)"
+                                  % (args.partial_loss, ' / '.join(PARTIAL_LOSS_METHODS), args.method))
     from ..ops import stage2_threshold_method       # NotImplementedError here; the reference raises it at the first picture
     stage2_threshold_method(getattr(args, 'cosprop_threshold_method', 'median'))            # (trainer/eval_save_cosplbl_prop.py:253)
 

@@ -15,8 +15,15 @@ class here                     reference definition
 ``GroupMultiLabelCE_``         ``trainer/active_joint_multi_predignore.py:74-128``
 ``OnehotCEMultihotChoice``     ``trainer/active_joint_multi_predignore_lossdecomp.py:16-72``
 ``GroupMultiLabelCE_onlymulti````trainer/active_joint_multi_predignore_mclossablation2.py:17-79``
+``RCMultiChoiceCE``            ``utils/loss.py:653-707`` (risk-consistent weighting; drops the last target column)
+``OnehotCEMultihotTopone``     ``trainer/active_joint_multi_lossdecomp_topone.py:14-71``
+``OnehotCEMultihotRC``         ``trainer/active_joint_multi_lossdecomp_rc.py:14-76`` -- the reference's version raises at
+                               ``:54`` (``:53`` already reduced the class axis); the class here computes what
+                               ``RCMultiChoiceCE`` defines, restricted to multi-hot pixels
 ``FusedPartialLabelLoss``      (new) the three production losses from ONE forward scan and ONE
-                               backward scan -- what ``train_impl`` of the production trainer uses
+                               backward scan -- what ``train_impl`` of the production trainer uses;
+                               ``multi_hot='choice'|'rc'|'topone'`` names the multi-hot pixel term
+                               (``csrc/partial_label.h``), ``group=False`` leaves the group term out
 =============================  =================================================================
 
 Inputs must be ROCm tensors; there is no CPU path (``_lib.MulActSegHipError`` otherwise).
@@ -214,6 +221,28 @@ class OnehotCEMultihotChoice(MultiChoiceCE):
         return ce, mc
 
 
+class RCMultiChoiceCE(MultiChoiceCE):
+    """Risk-consistent weighting, one merged sum: every candidate's own CE weighted by the detached in-set confidence
+    ``p_c / sum_Y p`` -- reference ``utils/loss.py:653-707`` (last target column dropped)."""
+    _flags = _lib.LOSS_CE | _lib.LOSS_RC
+
+
+class OnehotCEMultihotRC(OnehotCEMultihotChoice):
+    """(ce over one-hot superpixels, risk-consistent mc over multi-hot superpixels) -- the loss
+    ``trainer/active_joint_multi_lossdecomp_rc.py:14-76`` means: as written it raises at ``:54`` (a second reduction over the class
+    axis ``:53`` already removed); this is ``RCMultiChoiceCE``'s term restricted to multi-hot pixels, all target columns used."""
+    _flags = _lib.LOSS_CE | _lib.LOSS_DECOMP | _lib.LOSS_RC
+
+
+class OnehotCEMultihotTopone(OnehotCEMultihotChoice):
+    """(ce over one-hot superpixels, ``-log max_Y p`` over multi-hot superpixels) --
+    ``trainer/active_joint_multi_lossdecomp_topone.py:14-71``.  On a tie the gradient goes to the lowest class index."""
+    _flags = _lib.LOSS_CE | _lib.LOSS_DECOMP | _lib.LOSS_TOPONE
+
+
+MULTI_HOT_FLAGS = {'choice': 0, 'rc': _lib.LOSS_RC, 'topone': _lib.LOSS_TOPONE}
+
+
 class GroupMultiLabelCE(nn.Module):
     """Group / MIL loss: -log of the per-superpixel class-wise max probability --
     reference ``utils/loss.py:81-141`` (last target column dropped)."""
@@ -269,11 +298,18 @@ class FusedPartialLabelLoss(nn.Module):
     """The production stage-1 objective from one forward scan and one backward scan:
     returns (group_loss, ce_loss, mc_loss) exactly as
     ``GroupMultiLabelCE_onlymulti`` + ``OnehotCEMultihotChoice`` would
-    (``trainer/active_joint_multi_predignore_lossdecomp.py:102-103``), reading the logits once."""
+    (``trainer/active_joint_multi_predignore_lossdecomp.py:102-103``), reading the logits once.
+
+    ``multi_hot``: the term of a multi-hot pixel -- 'choice' (the reference's merged positive), 'rc' (risk-consistent weighting) or
+    'topone' (top-1 candidate); the same scans with another per-pixel formula.  ``group=False``: no group term -- no
+    ``[N,S,C]`` table is allocated and the group value is 0 (the objective of ``trainer/active_joint_multi_lossdecomp_rc.py``)."""
 
     def __init__(self, num_superpixel, group_temperature=1.0, multi_temperature=1.0, only_multi=True, decomp=True,
-                 sync_normalisers=True):
+                 sync_normalisers=True, multi_hot='choice', group=True):
         super().__init__()
+        if multi_hot not in MULTI_HOT_FLAGS:
+            raise ValueError("multi_hot must be one of %s, got %r" % (', '.join(MULTI_HOT_FLAGS), multi_hot))
+        self.multi_hot = multi_hot
         # under torch.distributed: all-reduce (sum, n) before the division so that the objective equals the
         # single-GPU objective over the global batch; multiply the loss by world_size before backward()
         # when gradients are then AVERAGED over ranks (DistributedDataParallel does).
@@ -283,8 +319,8 @@ class FusedPartialLabelLoss(nn.Module):
                              "(both 0.1 in the reference scripts)")
         self.num_superpixel = num_superpixel
         self.temp = multi_temperature
-        self.flags = _lib.LOSS_CE | _lib.LOSS_GROUP | (_lib.LOSS_GROUP_ONLY_MULTI if only_multi else 0) \
-            | (_lib.LOSS_DECOMP if decomp else 0)
+        self.flags = _lib.LOSS_CE | ((_lib.LOSS_GROUP | (_lib.LOSS_GROUP_ONLY_MULTI if only_multi else 0)) if group else 0) \
+            | (_lib.LOSS_DECOMP if decomp else 0) | MULTI_HOT_FLAGS[multi_hot]
 
     def forward(self, inputs, targets, superpixels, spmasks):
         ce, mc, group, self.last_acc = _run(inputs, targets, superpixels, spmasks, self.temp, self.flags, False,
