@@ -58,7 +58,8 @@ extern "C" {
  * mas_ms_iou_lds_bytes, then mas_candidate_plbl and mas_stage2_assign_labels, then mas_uncertainty_accum,
  * mas_uncertainty_accum_lowres and mas_uncertainty_reference, then mas_train_augment_u8, mas_photometric and
  * mas_photometric_reference, then mas_partial_loss_reference and the MAS_LOSS_RC / MAS_LOSS_TOPONE flag bits (a library built before
- * them treats the bits as unset): new entry
+ * them treats the bits as unset), then mas_online_plbl_labels, mas_label_ce_fwd_lowres / _bwd_lowres / _value and
+ * mas_online_plbl_reference: new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -224,6 +225,57 @@ int mas_partial_loss_bwd_fused(const float* z, int h, int w, const void* spx, in
 int mas_partial_loss_reference(const float* z, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits, int N, int C,
                                int H, int W, int S, float invT, int flags, const float* grad_out /* [3] or NULL */,
                                uint64_t* acc /* [8] += */, float* losses /* [3] or NULL */, float* dz /* or NULL */);
+
+/* ---------------------------------------------------------------------------------------------
+ * Online local-prototype pseudo labels (trainer/active_onlineplbl_multi_predignore.py:25-141, active_onlinewplbl_...:20-148,
+ * active_onlinewplblonly_...:20-137).  Per-pixel arithmetic: csrc/online_plbl.h.
+ *
+ * mas_online_plbl_labels: the reference's generate_plbl for the whole batch, one call, no host round trip.  zq_p [N,C,h,w] are the
+ * quarter-resolution logits of the eval-mode forward, featq [N,Ch,h,w] its L2-normalised point features; both are interpolated per
+ * pixel to (H, W) in registers (the tap of csrc/upsample_tap.h), neither full-resolution tensor exists.  A pixel is valid when its
+ * mask byte is set, its id lies in [0, S) and bits[n, id] has more than one bit.  The prototype of (n, s, c), c in bits[n, s], is
+ * the valid pixel of s with the largest softmax(up(zq_p) * invT)[c], ties to the lowest pixel index: the table of
+ * mas_partial_loss_fwd_lowres with MAS_LOSS_GROUP | MAS_LOSS_GROUP_ONLY_MULTI, which this call runs.  A valid pixel takes the class
+ * whose prototype feature has the largest inner product (a sequential fma chain over the channels) with its own feature, candidates
+ * walked in ascending class order, replaced on strict '>'.  labels u8 [N,H,W] (255 = none), weight f32 [N,H,W] (0 = none) =
+ * softmax(up(zq_p) * invT)[label]; with MAS_OPL_WEIGHT_WO_PROTO a prototype pixel's weight is 1.0.
+ * 1 <= Ch <= MAS_OPL_MAX_FEAT (MAS_ERR_RANGE), 2 <= C <= MAS_MAX_CLASSES; `work`: mas_online_plbl_work_bytes(N, S, C) bytes, 8-byte
+ * aligned, not initialised by the caller (u64 acc[8] | the table u64 [N,S,C]).  Every check happens before the first launch. */
+#define MAS_OPL_WEIGHT_WO_PROTO 1
+#define MAS_OPL_MAX_FEAT 2048
+size_t mas_online_plbl_work_bytes(int N, int S, int C);
+int mas_online_plbl_labels(const float* zq_p, const float* featq, int Ch, int h, int w, const void* spx, int spx_dtype,
+                           const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, float invT, int flags,
+                           void* work, size_t work_bytes, uint8_t* labels, float* weight, void* stream);
+
+/* Cross entropy of the training-mode quarter-resolution logits zq [N,C,h,w], upsampled in-kernel, against a per-pixel label map with
+ * per-pixel weights.  Per pixel with labels != 255 (a label >= C counts as 255): ce = -log softmax(up(zq) * invT)[label],
+ * term = wgt * ce with wgt by `mode` (the low two bits of flags): MAS_LCE_UNWEIGHTED 1 (LocalProtoCE), MAS_LCE_WEIGHTED weight[pixel],
+ * MAS_LCE_THRESHOLD (th < weight[pixel]) ? 1 : 0.  acc[0] += floor(term * 2^MAS_LOSS_FRAC_BITS), acc[1] += 1 for every labelled pixel
+ * (UNWEIGHTED) or every pixel whose f32 term is non-zero (the other modes: masked_select(loss, loss != 0).mean()).  The forward call
+ * zeroes acc first; loss (may be NULL: a data-parallel caller all-reduces acc and calls mas_label_ce_value) = acc[0] / acc[1], and
+ * for acc[1] == 0: 0, or NaN with MAS_LCE_EMPTY_NAN.  Backward: d zq from (grad[0] / acc[1]) * invT * wgt * (softmax - onehot) of the
+ * pixels that were counted, added through the four taps into dzq_fix [N,C,h,w] (zeroed by the call; MAS_GRAD_FRAC_BITS, integer
+ * atomics) and, with dzq != NULL, converted by mas_fix_to_float.  weight may be NULL for MAS_LCE_UNWEIGHTED. */
+#define MAS_LCE_UNWEIGHTED 0
+#define MAS_LCE_WEIGHTED 1
+#define MAS_LCE_THRESHOLD 2
+#define MAS_LCE_EMPTY_NAN 4
+int mas_label_ce_fwd_lowres(const float* zq, int h, int w, const uint8_t* labels, const float* weight, int N, int C, int H, int W,
+                            float invT, int flags, float th, uint64_t* acc /* [2] */, float* loss /* [1] or NULL */, void* stream);
+int mas_label_ce_value(const uint64_t* acc, int flags, float* loss, void* stream);
+int mas_label_ce_bwd_lowres(const float* zq, int h, int w, const uint8_t* labels, const float* weight, const uint64_t* acc,
+                            const float* grad /* [1] */, int N, int C, int H, int W, float invT, int flags, float th,
+                            int64_t* dzq_fix /* [N,C,h,w] */, float* dzq /* [N,C,h,w] or NULL */, void* stream);
+
+/* The CPU-side statement of csrc/online_plbl.h: every pointer is a HOST pointer, no device is touched.  A plain loop that writes what
+ * mas_online_plbl_labels writes (labels, weight; gmax [N,S,C] may be NULL), and, with zq != NULL, what mas_label_ce_fwd_lowres and
+ * mas_label_ce_bwd_lowres write for those labels (acc [2], loss [1], dzq_fix [N,C,h,w] for grad [1]; each of the three may be NULL).
+ * The kernels are tested against it bit for bit. */
+int mas_online_plbl_reference(const float* zq_p, const float* featq, int Ch, int h, int w, const void* spx, int spx_dtype,
+                              const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, float invT, int flags,
+                              uint64_t* gmax, uint8_t* labels, float* weight, const float* zq, float invT_ce, int ce_flags, float th,
+                              const float* grad, uint64_t* acc, float* loss, int64_t* dzq_fix);
 
 /* =============================================================================================
  * K4  ordering of the region scores and the budgeted selection walk

@@ -25,6 +25,8 @@ SK_DMA, SK_NOSPLIT = 1, 2
 LOWRES_GENERIC = 1
 UNC_BVSB, UNC_MARGIN, UNC_LEAST_CONFIDENCE, UNC_ENTROPY = 0, 1, 2, 3
 STAGE2_THR_MEDIAN, STAGE2_THR_MIN = 0, 1
+OPL_WEIGHT_WO_PROTO = 1                 # mas_online_plbl_labels: a prototype pixel's weight is 1.0 (--weight_wo_proto)
+LCE_UNWEIGHTED, LCE_WEIGHTED, LCE_THRESHOLD, LCE_EMPTY_NAN = 0, 1, 2, 4     # mas_label_ce_*: the weight mode, and NaN for an empty mean
 PM_BRIGHTNESS, PM_CONTRAST, PM_SATURATION, PM_HUE = 0, 1, 2, 3
 ABI_VERSION = 9        # MAS_ABI_VERSION of include/mulactseg_hip.h this table was written against (load() refuses any other library)
 
@@ -166,6 +168,13 @@ SIGNATURES = {
     "mas_adamw_job": (_c.c_uint, [_vp, _vp, _vp, _vp, _vp, _c.c_longlong, _i, _c.c_uint]),
     "mas_adamw_multi": (_i, [_vp, _i, _c.c_uint, _vp, _i, _d, _d, _d, _d, _vp, _vp, _vp]),
     "mas_partial_loss_bwd_fused": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "mas_online_plbl_work_bytes": (_c.c_size_t, [_i, _i, _i]),
+    "mas_online_plbl_labels": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _c.c_size_t, _vp, _vp, _vp]),
+    "mas_label_ce_fwd_lowres": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp]),
+    "mas_label_ce_value": (_i, [_vp, _i, _vp, _vp]),
+    "mas_label_ce_bwd_lowres": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp]),
+    "mas_online_plbl_reference": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _f, _i, _f,
+                                       _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

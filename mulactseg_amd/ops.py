@@ -348,6 +348,185 @@ def partial_loss_bwd_fused(z, size, spx, mask, state, grad, invT, weights=None, 
 
 
 # ------------------------------------------------------------------------------------------------
+# online local-prototype pseudo labels and the cross entropy on them (csrc/online_plbl.hip)
+# ------------------------------------------------------------------------------------------------
+LCE_UNWEIGHTED, LCE_WEIGHTED, LCE_THRESHOLD, LCE_EMPTY_NAN = _lib.LCE_UNWEIGHTED, _lib.LCE_WEIGHTED, _lib.LCE_THRESHOLD, _lib.LCE_EMPTY_NAN
+
+
+def _plbl_bits(targets, bits):
+    if (targets is None) == (bits is None):
+        raise ValueError("give either targets (u8 [N,S,cols]) or bits (int32 [N,S])")
+    if bits is None:
+        bits = target_bits(targets.contiguous() if targets.dtype == torch.uint8 else targets.to(torch.uint8).contiguous())
+    return bits
+
+
+def _plbl_shapes(zq_p, featq, size, spx, mask, bits):
+    N, C, h, w = zq_p.shape
+    H, W = int(size[0]), int(size[1])
+    if featq.dim() != 4 or featq.shape[0] != N or tuple(featq.shape[2:]) != (h, w):
+        raise ValueError("features %s do not match the logits %s" % (tuple(featq.shape), tuple(zq_p.shape)))
+    if tuple(spx.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W) or bits.dim() != 2 or bits.shape[0] != N:
+        raise ValueError("shape mismatch between logits %s at size %s, superpixels %s, spmasks %s, targets %s"
+                         % (tuple(zq_p.shape), (H, W), tuple(spx.shape), tuple(mask.shape), tuple(bits.shape)))
+    return N, C, h, w, H, W, featq.shape[1], bits.shape[1]
+
+
+def online_pseudo_labels(zq_p, featq, size, spx, mask, targets=None, bits=None, invT=1.0, weight_wo_proto=False):
+    """The reference's ``generate_plbl`` (``trainer/active_onlinewplbl_multi_predignore.py:20-125``) for the whole batch in ONE library
+    call and without a host round trip: ``zq_p`` [N,C,h,w] quarter-resolution logits of the eval-mode forward, ``featq`` [N,Ch,h,w]
+    its L2-normalised point features, both interpolated to ``size`` = (H, W) per pixel inside the kernel; ``spx`` / ``mask`` [N,H,W];
+    ``targets`` u8 [N,S,cols] or ready ``bits`` int32 [N,S].  Returns (labels u8 [N,H,W], 255 = none; weight f32 [N,H,W], 0 = none)."""
+    _need(zq_p, "inputs_plbl", torch.float32)
+    _need(featq, "feats_plbl", torch.float32)
+    _need(spx, "superpixels")
+    mask = _mask_u8(mask)
+    bits = _need(_plbl_bits(targets, bits), "bits", torch.int32)
+    N, C, h, w, H, W, Ch, S = _plbl_shapes(zq_p, featq, size, spx, mask, bits)
+    dev = zq_p.device
+    lib = _lib.load()
+    nbytes = int(lib.mas_online_plbl_work_bytes(N, S, C))
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)           # (zeroed inside the call)
+    labels = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    weight = torch.empty((N, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mas_online_plbl_labels(zq_p.data_ptr(), featq.data_ptr(), Ch, h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(),
+                                              bits.data_ptr(), N, C, H, W, S, invT, _lib.OPL_WEIGHT_WO_PROTO if weight_wo_proto else 0,
+                                              work.data_ptr(), work.numel() * 8, labels.data_ptr(), weight.data_ptr(), _stream(zq_p)),
+                   "mas_online_plbl_labels")
+    return labels, weight
+
+
+def _label_ce_check(zq, size, labels, weight, flags):
+    N, C, h, w = zq.shape
+    H, W = int(size[0]), int(size[1])
+    if tuple(labels.shape) != (N, H, W) or (weight is not None and tuple(weight.shape) != (N, H, W)):
+        raise ValueError("labels %s / weight %s do not match logits %s at size %s"
+                         % (tuple(labels.shape), None if weight is None else tuple(weight.shape), tuple(zq.shape), (H, W)))
+    if weight is None and (flags & 3) != _lib.LCE_UNWEIGHTED:
+        raise ValueError("the weighted and threshold modes need a weight map")
+    return N, C, h, w, H, W
+
+
+def label_ce_fwd_lowres(zq, size, labels, weight, invT, flags, th=0.0, reduce_acc=None):
+    """Forward half of ``label_ce_lowres``: (loss f32 [1], acc i64 [2] = fixed-point sum and count).  ``reduce_acc(acc)`` (data
+    parallel) runs between the scan and the division, so the mean is over the global batch."""
+    _need(zq, "inputs", torch.float32)
+    _need(labels, "labels", torch.uint8)
+    if weight is not None:
+        _need(weight, "weight", torch.float32)
+    N, C, h, w, H, W = _label_ce_check(zq, size, labels, weight, flags)
+    acc = torch.empty(2, dtype=torch.int64, device=zq.device)                     # (zeroed inside the call)
+    loss = torch.empty(1, dtype=torch.float32, device=zq.device)
+    lib = _lib.load()
+    with torch.cuda.device(zq.device):
+        st = _stream(zq)
+        _lib.check(lib.mas_label_ce_fwd_lowres(zq.data_ptr(), h, w, labels.data_ptr(), _opt(weight), N, C, H, W, invT, flags, float(th),
+                                               acc.data_ptr(), None if reduce_acc is not None else loss.data_ptr(), st),
+                   "mas_label_ce_fwd_lowres")
+        if reduce_acc is not None:
+            reduce_acc(acc)
+            _lib.check(lib.mas_label_ce_value(acc.data_ptr(), flags, loss.data_ptr(), st), "mas_label_ce_value")
+    return loss, acc
+
+
+def label_ce_bwd_lowres(zq, size, labels, weight, acc, grad, invT, flags, th=0.0, want_fix=False):
+    """Backward half: dzq [N,C,h,w] f32 for the upstream gradient ``grad`` f32 [1] (and the int64 sums it was rounded from)."""
+    _need(grad, "grad", torch.float32)
+    N, C, h, w, H, W = _label_ce_check(zq, size, labels, weight, flags)
+    fix = torch.empty((N, C, h, w), dtype=torch.int64, device=zq.device)          # (zeroed inside the call)
+    dzq = torch.empty_like(zq)
+    with torch.cuda.device(zq.device):
+        _lib.check(_lib.load().mas_label_ce_bwd_lowres(zq.data_ptr(), h, w, labels.data_ptr(), _opt(weight), acc.data_ptr(), grad.data_ptr(),
+                                                       N, C, H, W, invT, flags, float(th), fix.data_ptr(), dzq.data_ptr(), _stream(zq)),
+                   "mas_label_ce_bwd_lowres")
+    return (dzq, fix) if want_fix else dzq
+
+
+class _LabelCELowRes(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, zq, size, labels, weight, invT, flags, th, reduce_acc):
+        zq = zq.contiguous()
+        loss, acc = label_ce_fwd_lowres(zq, size, labels, weight, invT, flags, th, reduce_acc)
+        ctx.save_for_backward(zq, labels, acc, weight if weight is not None else acc)
+        ctx.has_w, ctx.size, ctx.invT, ctx.flags, ctx.th = weight is not None, size, invT, flags, th
+        ctx.mark_non_differentiable(acc)
+        return loss[0], acc
+
+    @staticmethod
+    def backward(ctx, g, _g_acc):
+        zq, labels, acc, weight = ctx.saved_tensors
+        dzq = label_ce_bwd_lowres(zq, ctx.size, labels, weight if ctx.has_w else None, acc, g.reshape(1).to(torch.float32).contiguous(),
+                                  ctx.invT, ctx.flags, ctx.th)
+        return dzq, None, None, None, None, None, None, None
+
+
+def label_ce_lowres(zq, size, labels, weight, invT, mode=LCE_UNWEIGHTED, th=0.0, empty_nan=False, reduce_acc=None):
+    """Mean cross entropy of ``F.interpolate(zq, size, 'bilinear', align_corners=False) * invT`` against ``labels`` u8 [N,H,W]
+    (255 = none) with per-pixel weights, differentiable in ``zq``; the upsampled logits and their gradient never exist.  ``mode``:
+    LCE_UNWEIGHTED (mean over the labelled pixels), LCE_WEIGHTED (``weight * ce``) or LCE_THRESHOLD (``(th < weight) * ce``), the last
+    two averaged over the non-zero terms.  No labelled (non-zero) pixel: 0, or NaN with ``empty_nan``.  Returns (loss, acc)."""
+    flags = int(mode) | (_lib.LCE_EMPTY_NAN if empty_nan else 0)
+    return _LabelCELowRes.apply(zq, (int(size[0]), int(size[1])), labels, weight, invT, flags, float(th), reduce_acc)
+
+
+def online_plbl_reference(zq_p, featq, size, spx, mask, targets=None, bits=None, invT=1.0, weight_wo_proto=False, zq=None, invT_ce=None,
+                          mode=LCE_UNWEIGHTED, th=0.0, empty_nan=False, grad=None, labels=None, weight=None):
+    """``online_pseudo_labels`` and ``label_ce_lowres`` on HOST tensors: the library's plain loop through csrc/online_plbl.h
+    (``mas_online_plbl_reference``), the CPU-side statement of the arithmetic the kernels are checked against.  Needs no GPU.
+    With ``zq_p`` None the label and weight maps are the given ``labels`` / ``weight``.  Returns a dict: labels, weight, gmax (the
+    arg-pixel table, when labels were generated), and with ``zq``: loss f32 [1], acc i64 [2], and with ``grad`` (f32 [1]) dzq_fix."""
+    out = {}
+    lib = _lib.load()
+    for t in (zq_p, featq, spx, mask, zq, grad, labels, weight, bits, targets):
+        if t is not None and (t.is_cuda or not t.is_contiguous()):
+            raise ValueError("online_plbl_reference takes contiguous host tensors")
+    src = zq_p if zq_p is not None else zq
+    N, C, h, w = src.shape
+    H, W = int(size[0]), int(size[1])
+    if zq_p is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        bits = _plbl_bits_host(targets, bits)
+        _plbl_shapes(zq_p, featq, size, spx, mask, bits)
+        Ch, S = featq.shape[1], bits.shape[1]
+        labels = torch.empty((N, H, W), dtype=torch.uint8)
+        weight = torch.empty((N, H, W), dtype=torch.float32)
+        gmax = out['gmax'] = torch.zeros((N, S, C), dtype=torch.int64)
+        gen = (zq_p.data_ptr(), featq.data_ptr(), Ch, h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr())
+    else:
+        S, gmax = 1, None
+        gen = (None, None, 1, h, w, None, 0, None, None)
+    acc = loss = fix = None
+    if zq is not None:
+        acc, loss = torch.zeros(2, dtype=torch.int64), torch.zeros(1, dtype=torch.float32)
+        fix = torch.zeros(zq.shape, dtype=torch.int64) if grad is not None else None
+    flags = int(mode) | (_lib.LCE_EMPTY_NAN if empty_nan else 0)
+    _lib.check(lib.mas_online_plbl_reference(*gen, N, C, H, W, S, invT, _lib.OPL_WEIGHT_WO_PROTO if weight_wo_proto else 0, _opt(gmax),
+                                             labels.data_ptr(), _opt(weight), _opt(zq), invT if invT_ce is None else invT_ce, flags, float(th),
+                                             _opt(grad), _opt(acc), _opt(loss), _opt(fix)), "mas_online_plbl_reference")
+    out.update(labels=labels, weight=weight)
+    if zq is not None:
+        out.update(loss=loss, acc=acc)
+        if fix is not None:
+            out['dzq_fix'] = fix
+    return out
+
+
+def _plbl_bits_host(targets, bits):
+    """``target_bits`` on the host (the reference function has no device to run the kernel on)."""
+    if (targets is None) == (bits is None):
+        raise ValueError("give either targets (u8 [N,S,cols]) or bits (int32 [N,S])")
+    if bits is not None:
+        return bits
+    cols = targets.shape[-1]
+    if cols > _lib.MAX_CLASSES:
+        raise ValueError("at most %d target columns" % _lib.MAX_CLASSES)
+    v = ((targets != 0).to(torch.int64) << torch.arange(cols, dtype=torch.int64)).sum(-1)
+    return torch.where(v >= 2 ** 31, v - 2 ** 32, v).to(torch.int32).contiguous()           # (bit 31 set: the same 32 bits as int32)
+
+
+# ------------------------------------------------------------------------------------------------
 # K4: ordering + budgeted selection walk
 # ------------------------------------------------------------------------------------------------
 def path_ranks(paths):

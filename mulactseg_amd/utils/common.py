@@ -88,6 +88,12 @@ def get_parser():
     a("--partial_loss", default='choice', choices=['choice', 'rc', 'topone'],
       help="term of a multi-hot pixel in the lossdecomp trainers: the reference's -log sum_Y p, the risk-consistent weighting, "
            "or -log max_Y p")
+    # online local-prototype pseudo labels (the active_online*plbl trainers; refused for every other --method)
+    a("--lamparam", type=float, default=0.1, help="ramp up param")
+    a("--lamscale", type=float, default=1.0, help="ramp up scale")
+    a('--dorampup', action='store_true', default=False)
+    a("--th_wplbl", type=float, default=None)
+    a('--weight_wo_proto', action='store_true', default=False)
     # active learning
     a("--seed", type=int, default=0)
     a("--start_over", action='store_true', default=False)
@@ -236,6 +242,11 @@ def preprocess(args):
 PARTIAL_LOSS_METHODS = ('active_joint_multi_predignore_lossdecomp', 'active_joint_multi_lossdecomp')
 
 
+# the trainers that read --lamparam / --lamscale / --dorampup / --th_wplbl / --weight_wo_proto, and those flags' defaults
+ONLINE_PLBL_METHODS = ('active_onlineplbl_multi_predignore', 'active_onlinewplbl_multi_predignore', 'active_onlinewplblonly_multi_predignore')
+ONLINE_PLBL_DEFAULTS = dict(lamparam=0.1, lamscale=1.0, dorampup=False, th_wplbl=None, weight_wo_proto=False)
+
+
 def arg_assert(args):
     """Consistency of the flags -- ``utils/common.py:205-231``."""
     assert args.init_checkpoint is not None
@@ -257,6 +268,11 @@ def arg_assert(args):
     if getattr(args, 'partial_loss', 'choice') != 'choice' and args.method not in PARTIAL_LOSS_METHODS:
         raise NotImplementedError("--partial_loss %s is honoured by --method %s only (got %s)"
                                   % (args.partial_loss, ' / '.join(PARTIAL_LOSS_METHODS), args.method))
+    if args.method not in ONLINE_PLBL_METHODS:
+        changed = [k for k, v in ONLINE_PLBL_DEFAULTS.items() if getattr(args, k, v) != v]
+        if changed:
+            raise NotImplementedError("--%s is honoured by --method %s only (got %s)"
+                                      % (' / --'.join(changed), ' / '.join(ONLINE_PLBL_METHODS), args.method))
     from ..ops import stage2_threshold_method       # NotImplementedError here; the reference raises it at the first picture
     stage2_threshold_method(getattr(args, 'cosprop_threshold_method', 'median'))            # (trainer/eval_save_cosplbl_prop.py:253)
 

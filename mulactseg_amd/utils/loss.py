@@ -24,6 +24,12 @@ class here                     reference definition
                                backward scan -- what ``train_impl`` of the production trainer uses;
                                ``multi_hot='choice'|'rc'|'topone'`` names the multi-hot pixel term
                                (``csrc/partial_label.h``), ``group=False`` leaves the group term out
+``LocalProtoCE``               ``trainer/active_onlineplbl_multi_predignore.py:14-141`` (online local-prototype pseudo
+                               labels of the multi-hot superpixels + CE on them; ``csrc/online_plbl.hip``)
+``LocalWProtoCE``              ``trainer/active_onlinewplbl_multi_predignore.py:15-148`` (the CE weighted by the
+                               network's confidence in the label, or gated by ``--th_wplbl``; mean over non-zero terms)
+``JointLocalProtoCE``          ``trainer/active_onlinewplblonly_multi_predignore.py:15-137`` (weighted; the mean of an
+                               empty set is NaN, as the reference's)
 =============================  =================================================================
 
 Inputs must be ROCm tensors; there is no CPU path (``_lib.MulActSegHipError`` otherwise).
@@ -348,3 +354,87 @@ class FusedPartialLabelLoss(nn.Module):
         total, parts, self.last_acc = _WeightedLowResLossFn.apply(quarter_logits, tuple(size), targets.contiguous(), targets.shape[-1], superpixels, spmasks,
                                                                   ops.inv_temperature(self.temp), self.flags, self.sync_normalisers, self._w)
         return total, parts[2], parts[0], parts[1]
+
+
+class LocalProtoCE(nn.Module):
+    """Online local-prototype pseudo labels and the cross entropy on them -- reference
+    ``trainer/active_onlineplbl_multi_predignore.py:14-141``.  For every candidate class of a selected multi-hot superpixel the pixel
+    with the largest predicted probability is the class's local prototype; every pixel of the superpixel takes the class of the
+    prototype whose feature is nearest to its own (``generate_plbl``); the loss is the mean CE of the training-mode logits on those
+    labels, 0 when there is none.
+
+    ``forward`` takes the reference's full-resolution tensors.  ``forward_lowres`` takes what the model computes -- quarter-resolution
+    logits and features of the eval-mode forward, quarter-resolution training logits -- and evaluates the x4 bilinear upsampling
+    inside the kernels: neither ``feat_forward``'s ``[N,256,H,W]`` features nor any ``[N,C,H,W]`` logits exist.  No host
+    synchronisation; run-to-run identical bytes; under torch.distributed the sum and the count are all-reduced before the division
+    (the loss over the global batch, see ``_run``)."""
+    _mode = _lib.LCE_UNWEIGHTED
+    _empty_nan = False
+    _honours_weight_wo_proto = False
+
+    def __init__(self, args, num_superpixel, temperature=1.0, reduction='mean'):
+        super().__init__()
+        if reduction != 'mean':
+            raise NotImplementedError("only reduction='mean' exists (the reference asserts it)")
+        self.args = args
+        self.num_superpixel = num_superpixel
+        self.temp = temperature
+        self.reduction = reduction
+        self.eps = 1e-8
+        self.sync_normalisers = True
+
+    def generate_plbl(self, inputs_plbl, feats_plbl, targets, superpixels, spmasks, size=None):
+        """(weight f32 [N,H,W], nn_plbl u8 [N,H,W]) as the reference's ``generate_plbl`` returns them (255 = no label, weight 0).
+        ``size`` None: the tensors are at the resolution of ``superpixels``; else they are quarter-resolution maps upsampled
+        in-kernel to ``size``."""
+        if targets.shape[1] != self.num_superpixel:
+            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        if size is None:
+            size = superpixels.shape[-2:]
+        wo_proto = self._honours_weight_wo_proto and bool(getattr(self.args, 'weight_wo_proto', False))
+        with torch.no_grad():
+            labels, weight = ops.online_pseudo_labels(inputs_plbl.detach().contiguous(), feats_plbl.detach().contiguous(), size,
+                                                      superpixels.contiguous(), spmasks.contiguous(), targets=targets,
+                                                      invT=ops.inv_temperature(self.temp), weight_wo_proto=wo_proto)
+        return weight, labels
+
+    def _mode_th(self):
+        return self._mode, 0.0
+
+    def _loss(self, inputs, size, labels, weight):
+        mode, th = self._mode_th()
+        loss, self.last_acc = ops.label_ce_lowres(inputs, size, labels, None if mode == _lib.LCE_UNWEIGHTED else weight,
+                                                  ops.inv_temperature(self.temp), mode=mode, th=th, empty_nan=self._empty_nan,
+                                                  reduce_acc=_all_reduce_sum if self.sync_normalisers else None)
+        return loss
+
+    def forward(self, inputs_plbl, feats_plbl, inputs, targets, superpixels, spmasks):
+        weight, labels = self.generate_plbl(inputs_plbl, feats_plbl, targets, superpixels, spmasks)
+        return self._loss(inputs, inputs.shape[-2:], labels, weight)
+
+    def forward_lowres(self, zq_p, featq, zq, size, targets, superpixels, spmasks):
+        """``zq_p`` [N,C,h,w] / ``featq`` [N,Ch,h,w]: logits and normalised point features of the eval-mode forward
+        (``net.feat_forward_quarter``); ``zq`` [N,C,h,w]: the training-mode logits (``net(images, lowres=True)``); ``size`` = (H, W)."""
+        size = (int(size[0]), int(size[1]))
+        weight, labels = self.generate_plbl(zq_p, featq, targets, superpixels, spmasks, size=size)
+        return self._loss(zq, size, labels, weight)
+
+
+class LocalWProtoCE(LocalProtoCE):
+    """``LocalProtoCE`` with every pixel's CE weighted by the network's own probability of its pseudo label (``args.weight_wo_proto``:
+    prototype pixels weigh 1), or, with ``args.th_wplbl``, kept only where that probability exceeds the threshold; the mean runs over
+    the non-zero terms -- reference ``trainer/active_onlinewplbl_multi_predignore.py:15-148``."""
+    _mode = _lib.LCE_WEIGHTED
+    _honours_weight_wo_proto = True
+
+    def _mode_th(self):
+        th = getattr(self.args, 'th_wplbl', None)
+        return (_lib.LCE_WEIGHTED, 0.0) if th is None else (_lib.LCE_THRESHOLD, float(th))
+
+
+class JointLocalProtoCE(LocalProtoCE):
+    """The weighted CE alone, as the only loss of its trainer -- reference ``trainer/active_onlinewplblonly_multi_predignore.py:15-137``:
+    neither ``--th_wplbl`` nor ``--weight_wo_proto`` is read, and a batch without a non-zero term gives NaN (the mean of an empty
+    tensor), which the trainer's ``update`` raises on."""
+    _mode = _lib.LCE_WEIGHTED
+    _empty_nan = True

@@ -1,0 +1,262 @@
+"""The online local-prototype pseudo labels on the GPU: the kernels of csrc/online_plbl.hip against the library's host loop through
+csrc/online_plbl.h (``ops.online_plbl_reference``) bit for bit -- labels, weight bits, both accumulators, the int64 sums of dzq --, the
+modules against the executed reference (tests/golden/g15_online_plbl.npz), ``forward_lowres`` against ``forward`` on materialised
+tensors, run-to-run identity, the empty case, and the trainer end to end."""
+import logging
+import tempfile
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from mulactseg_amd import synth
+
+import online_plbl_restated as R
+from test_online_plbl_cpu import golden, golden_inputs
+
+pytestmark = pytest.mark.gpu
+MODES = ((0, 0.0), (1, 0.0), (2, R.TH))          # (mode, th): unweighted, weighted, threshold
+
+
+def _gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from mulactseg_amd import ops
+    return ops
+
+
+def _tensors(case):
+    return {k: torch.from_numpy(np.ascontiguousarray(case[k])) for k in ('zq_p', 'featq', 'zq', 'tgt', 'spx', 'msk')}
+
+
+def _bit_for_bit(ops, t, size, id_types=(torch.int64,), wo_proto=(False, True)):
+    invT = ops.inv_temperature(R.T)
+    d = {k: v.cuda() for k, v in t.items()}
+    grad = torch.tensor([16.0])
+    labelled = 0
+    for wo in wo_proto:
+        ref = ops.online_plbl_reference(t['zq_p'], t['featq'], size, t['spx'], t['msk'], targets=t['tgt'], invT=invT, weight_wo_proto=wo)
+        for dt in id_types:
+            labels, weight = ops.online_pseudo_labels(d['zq_p'], d['featq'], size, d['spx'].to(dt), d['msk'], targets=d['tgt'], invT=invT,
+                                                      weight_wo_proto=wo)
+            assert torch.equal(labels.cpu(), ref['labels']), (wo, dt)
+            assert torch.equal(weight.cpu().view(torch.int32), ref['weight'].view(torch.int32)), (wo, dt)
+        labelled = int((ref['labels'] != 255).sum())
+        for mode, th in MODES:
+            r = ops.online_plbl_reference(None, None, size, None, None, zq=t['zq'], invT_ce=invT, mode=mode, th=th, grad=grad,
+                                          labels=ref['labels'], weight=ref['weight'])
+            loss, acc = ops.label_ce_fwd_lowres(d['zq'], size, labels, None if mode == 0 else weight, invT, mode, th)
+            assert torch.equal(acc.cpu(), r['acc']), (wo, mode)
+            assert torch.equal(loss.cpu().view(torch.int32), r['loss'].view(torch.int32)), (wo, mode)
+            dzq, fix = ops.label_ce_bwd_lowres(d['zq'], size, labels, None if mode == 0 else weight, acc, grad.cuda(), invT, mode, th,
+                                               want_fix=True)
+            assert torch.equal(fix.cpu(), r['dzq_fix']), (wo, mode)
+            assert torch.equal(dzq.cpu(), (r['dzq_fix'].double() * 2.0 ** -44).float())
+            if labelled:
+                assert int(r['acc'][1]) > 0 or mode == 2
+    return labelled
+
+
+def test_kernels_equal_the_host_reference_on_the_golden_shape():
+    ops = _gpu()
+    t = dict(zip(('zq_p', 'featq', 'zq', 'tgt', 'spx', 'msk'), golden_inputs()))
+    assert _bit_for_bit(ops, t, (R.H, R.W), id_types=(torch.int64, torch.int32)) > 500
+
+
+def test_kernels_equal_the_host_reference_on_the_edge_case():
+    """37 x 45 from its quarter size (nothing a multiple of 4); a picture without a selected pixel, one without a multi-hot superpixel,
+    a superpixel with all 20 bits, ids >= S outside the mask, a prototype on pixel 0, two classes sharing a prototype pixel"""
+    ops = _gpu()
+    e = R.edge_case()
+    t = _tensors(e)
+    assert _bit_for_bit(ops, t, e['size'], id_types=(torch.int64, torch.int32)) > 500
+    labels, _ = ops.online_pseudo_labels(t['zq_p'].cuda(), t['featq'].cuda(), e['size'], t['spx'].cuda(), t['msk'].cuda(),
+                                         targets=t['tgt'].cuda(), invT=ops.inv_temperature(R.T))
+    lab = labels.cpu().numpy()
+    assert np.all(lab[1] == 255) and np.all(lab[2] == 255)
+    assert np.all(lab[3][e['spx'][3] == e['pair']] == 3)                    # the shared prototype pixel: the lower class
+    assert np.all(lab[3][e['spx'][3] >= e['S']] == 255)
+
+
+@pytest.mark.parametrize("c,ch,h,w,s", [(19, 64, 9, 300, 24), (7, 33, 21, 50, 12), (21, 256, 16, 24, 8)])
+def test_kernels_equal_the_host_reference_on_other_paths(c, ch, h, w, s):
+    """more than one tile across (W > 256), the generic class count (no LDS image in the backward), 19 and 21 classes, a picture whose
+    sides are multiples of 4, other feature widths"""
+    ops = _gpu()
+    zq_p, featq, zq, tgt, spx, msk = R.inputs(31 + c, 2, c, ch, h, w, R.quarter(h), R.quarter(w), s, frac=0.6)
+    t = _tensors(dict(zq_p=zq_p, featq=featq, zq=zq, tgt=tgt, spx=spx, msk=msk))
+    assert _bit_for_bit(ops, t, (h, w), wo_proto=(True,)) > 0
+
+
+def test_bad_arguments_launch_nothing():
+    ops = _gpu()
+    from mulactseg_amd._lib import MulActSegHipError
+    t = {k: v.cuda() for k, v in dict(zip(('zq_p', 'featq', 'zq', 'tgt', 'spx', 'msk'), golden_inputs())).items()}
+    invT = ops.inv_temperature(R.T)
+    big = torch.zeros((R.N, 2049, R.HQ, R.WQ), device='cuda')
+    with pytest.raises(MulActSegHipError):          # a feature width beyond MAS_OPL_MAX_FEAT
+        ops.online_pseudo_labels(t['zq_p'], big, (R.H, R.W), t['spx'], t['msk'], targets=t['tgt'], invT=invT)
+    with pytest.raises(MulActSegHipError):          # the quarter map larger than the picture
+        ops.online_pseudo_labels(t['zq_p'], t['featq'], (R.HQ - 1, R.WQ - 1), t['spx'][:, :R.HQ - 1, :R.WQ - 1].contiguous(),
+                                 t['msk'][:, :R.HQ - 1, :R.WQ - 1].contiguous(), targets=t['tgt'], invT=invT)
+    with pytest.raises(MulActSegHipError):          # 33 classes
+        ops.label_ce_fwd_lowres(torch.zeros((1, 33, 2, 2), device='cuda'), (8, 8), torch.zeros((1, 8, 8), dtype=torch.uint8, device='cuda'),
+                                None, invT, 0)
+    with pytest.raises(ValueError):                 # a weighted mode without weights
+        ops.label_ce_fwd_lowres(t['zq'], (R.H, R.W), torch.zeros((R.N, R.H, R.W), dtype=torch.uint8, device='cuda'), None, invT, 1)
+    torch.cuda.synchronize()
+
+
+def _args(**kw):
+    return types.SimpleNamespace(nseg=kw.pop('nseg', R.S), weight_wo_proto=kw.get('wo', False), th_wplbl=kw.get('th'))
+
+
+CLASSES = [('plain', 'LocalProtoCE', {}), ('w', 'LocalWProtoCE', {}), ('wo', 'LocalWProtoCE', {'wo': True}),
+           ('th', 'LocalWProtoCE', {'th': R.TH}), ('joint', 'JointLocalProtoCE', {})]
+
+
+@pytest.mark.parametrize("name,cls,kw", CLASSES)
+def test_modules_match_the_executed_reference(name, cls, kw):
+    """value within 2e-6 of the reference's, gradient against the golden gradient pushed through the transpose of the bilinear
+    upsampling within 1e-4 of its maximum"""
+    _gpu()
+    from mulactseg_amd.utils import loss as L
+    g = golden()
+    zq_p, featq, zq, tgt, spx, msk = [a.cuda() for a in golden_inputs()]
+    crit = getattr(L, cls)(_args(**kw), R.S, R.T)
+    zt = zq.clone().requires_grad_(True)
+    loss = crit.forward_lowres(zq_p, featq, zt, (R.H, R.W), tgt, spx, msk)
+    loss.backward()
+    ref = float(g[name + '_loss'])
+    print("%s: %.7f against %.7f" % (name, float(loss), ref))
+    assert abs(float(loss) - ref) <= 2e-6 * abs(ref)
+    if name == 'joint':
+        name = 'w'
+    zc = golden_inputs()[2].clone().requires_grad_(True)
+    (want,) = torch.autograd.grad(R.upsample(zc, (R.H, R.W)), zc, grad_outputs=torch.from_numpy(g[name + '_grad']))
+    err, scale = float((zt.grad.cpu() - want).abs().max()), float(want.abs().max())
+    print("%s gradient: max error %.3e of max|ref| %.3e" % (name, err, scale))
+    assert scale > 0 and err <= 1e-4 * scale
+    # two runs give the same bytes
+    z2 = zq.clone().requires_grad_(True)
+    loss2 = crit.forward_lowres(zq_p, featq, z2, (R.H, R.W), tgt, spx, msk)
+    loss2.backward()
+    assert torch.equal(loss2.view(torch.int32), loss.view(torch.int32)) and torch.equal(z2.grad, zt.grad)
+
+
+@pytest.mark.parametrize("name,cls,kw", CLASSES[:4])
+def test_forward_lowres_equals_forward_on_materialised_tensors(name, cls, kw):
+    ops = _gpu()
+    from mulactseg_amd.utils import loss as L
+    zq_p, featq, zq, tgt, spx, msk = [a.cuda() for a in golden_inputs()]
+    size = (R.H, R.W)
+    crit = getattr(L, cls)(_args(**kw), R.S, R.T)
+    low = crit.forward_lowres(zq_p, featq, zq, size, tgt, spx, msk)
+    acc_low = crit.last_acc.clone()
+    full = crit(ops.upsample_bilinear(zq_p, size), ops.upsample_bilinear(featq, size), ops.upsample_bilinear(zq, size), tgt, spx, msk)
+    assert torch.equal(acc_low, crit.last_acc) and torch.equal(low.view(torch.int32), full.view(torch.int32)) and float(low) > 0
+    w_low, l_low = crit.generate_plbl(zq_p, featq, tgt, spx, msk, size=size)
+    w_full, l_full = crit.generate_plbl(ops.upsample_bilinear(zq_p, size), ops.upsample_bilinear(featq, size), tgt, spx, msk)
+    assert torch.equal(l_low, l_full) and torch.equal(w_low, w_full)
+
+
+@pytest.mark.parametrize("cls,empty", [('LocalProtoCE', 0.0), ('LocalWProtoCE', 0.0), ('JointLocalProtoCE', float('nan'))])
+def test_no_labelled_pixel_gives_zero_or_nan_and_a_zero_gradient(cls, empty):
+    _gpu()
+    from mulactseg_amd.utils import loss as L
+    zq_p, featq, zq, tgt, spx, msk = [a.cuda() for a in golden_inputs()]
+    zt = zq.clone().requires_grad_(True)
+    loss = getattr(L, cls)(_args(), R.S, R.T).forward_lowres(zq_p, featq, zt, (R.H, R.W), tgt, spx, torch.zeros_like(msk))
+    loss.backward()
+    v = float(loss)
+    assert (v != v) if empty != empty else v == 0.0
+    assert float(zt.grad.abs().max()) == 0.0
+
+
+# ---- trainer ------------------------------------------------------------------------------------------------------------------------
+N_CLS, TS, TH_, TW_ = 19, 64, 128, 160
+
+
+class _Train(torch.utils.data.Dataset):
+    selection_iter = 1
+
+    def __len__(self):
+        return 2
+
+    def __getitem__(self, i):
+        rs = np.random.RandomState(100 + i)
+        spx, msk = synth.train_crop(200 + i, TH_, TW_, TS, frac_selected=0.4)
+        return {'images': torch.from_numpy(rs.standard_normal((3, TH_, TW_)).astype(np.float32)),
+                'labels': torch.from_numpy(synth.multi_hot_targets(300 + i, TS, N_CLS + 1, p_counts=R.P_COUNTS)),
+                'spx': torch.from_numpy(spx), 'spmask': torch.from_numpy(msk)}
+
+
+class _Val(torch.utils.data.Dataset):
+    def __len__(self):
+        return 1
+
+    def __getitem__(self, i):
+        return {'images': torch.zeros((3, TH_, TW_)), 'labels': torch.zeros((TH_, TW_), dtype=torch.int64)}
+
+
+def test_trainer_runs_two_steps_with_fresh_pseudo_labels():
+    """two steps of active_onlinewplbl_multi_predignore: finite losses, moving parameters, the reference's meters; the eval-mode forward of
+    step 2 sees the parameters step 1 left (it differs from step 1's on the same pictures, and agrees with itself after every cache of packed
+    weights and folded BatchNorm constants is dropped); the module is in training mode after each pseudo-label forward"""
+    ops = _gpu()
+    import importlib
+    from mulactseg_amd import dataloader
+    from mulactseg_amd.utils import common, loss as L
+    method = 'active_onlinewplbl_multi_predignore'
+    a = common.get_parser().parse_args([
+        '-m', 'deeplabv3pluswn_resnet50deepstem', '--separable_conv', '--method', method, '--ce_temp', '0.1', '--multi_ce_temp', '0.1',
+        '--group_ce_temp', '0.1', '--coeff', '16.0', '--or_labeling', '--fair_counting', '--nseg', str(TS), '--train_batch_size', '2',
+        '--val_batch_size', '1', '--num_workers', '0', '--val_num_workers', '0', '--train_lr', '2e-4', '--finetune_itrs', '2',
+        '--val_period', '1000', '--log_period', '1', '--dorampup', '--lamscale', '2.0', '--weight_wo_proto', '-p', tempfile.mkdtemp()])
+    a.pretrained_backbone = False
+    dataloader.register_dataset_factory(lambda args, name, data_root, datalist, imageset: _Val())
+    torch.manual_seed(0)
+    tr = importlib.import_module("mulactseg_amd.trainer." + method).ActiveTrainer(a, logging.getLogger("test"), 1)
+    assert isinstance(tr.multi_local_proto_loss, L.LocalWProtoCE) and isinstance(tr.multi_pos_loss, L.MultiChoiceCE_)
+    seen = dict(plbl=[], meters=[], lowres=[])
+    plf, meter, fwd = tr.pseudo_label_forward, tr.update_average_meter, tr.forward_train
+
+    def pseudo_label_forward(images, lowres):
+        feats, logits = plf(images, lowres)
+        assert tr.net.training                                  # restored after the eval-mode forward
+        ops.invalidate_parameter_caches()                       # every derived constant is rebuilt: the same result means none was stale
+        feats2, logits2 = plf(images, lowres)
+        # (cosine logits and unit features: re-association noise of another kernel plan stays below 1e-5, an optimizer step at
+        #  lr 2e-4 -- ten times that in the head -- moves them by far more than 1e-4, asserted between the steps below)
+        assert float((logits - logits2).abs().max()) <= 1e-5 and float((feats - feats2).abs().max()) <= 1e-5 and not logits.requires_grad
+        seen['plbl'].append((images.clone(), logits.clone(), lowres))
+        return feats, logits
+
+    def update_average_meter(values):
+        seen['meters'].append({k: v.detach().clone() for k, v in values.items()})
+        return meter(values)
+
+    def forward_train(images, **kw):
+        seen['lowres'].append(kw.get('lowres', False))
+        return fwd(images, **kw)
+
+    tr.pseudo_label_forward, tr.update_average_meter, tr.forward_train = pseudo_label_forward, update_average_meter, forward_train
+    tr._wandb_log = lambda payload, step: None
+    before = [p.detach().clone() for p in tr.net.parameters()]
+    tr.train(types.SimpleNamespace(selection_iter=1, get_trainset=lambda: _Train()))
+    assert len(seen['plbl']) == 2 and all(low for _, _, low in seen['plbl']) and seen['lowres'] == [True, True]
+    assert tuple(seen['plbl'][0][1].shape) == (2, N_CLS + 1, TH_ // 4, TW_ // 4)
+    for m in seen['meters']:
+        assert set(m) == {'train-loss', 'pos-loss', 'local-proto-loss'} and all(bool(torch.isfinite(v)) for v in m.values())
+    assert float(seen['meters'][0]['local-proto-loss']) > 0 and float(seen['meters'][0]['pos-loss']) > 0
+    moved = sum(float((p.detach() - q).abs().sum()) for p, q in zip(tr.net.parameters(), before))
+    assert moved > 0 and np.isfinite(moved)
+    (im1, z1, _), (im2, z2, _) = seen['plbl']
+    for j in range(2):                                          # the same two pictures, in the loader's order of that step
+        k = [i for i in range(2) if torch.equal(im1[i], im2[j])]
+        assert len(k) == 1 and float((z1[k[0]] - z2[j]).abs().max()) > 1e-4
+    assert tr.net.training
+    # lambda of step 0 is ramp_up(0) = 0: the first train-loss is coeff * pos
+    first = seen['meters'][0]
+    assert abs(float(first['train-loss']) - 16.0 * float(first['pos-loss'])) <= 1e-5 * abs(float(first['train-loss']))
