@@ -364,7 +364,8 @@ __global__ __launch_bounds__(kThreads) void k_region_finalize(const mas_u64* __r
                                                                int C, int ban_class, float* __restrict__ score,
                                                                int* __restrict__ dominant, unsigned* __restrict__ count,
                                                                long long* __restrict__ hist_i64) {
-    // rows of C histogram words are staged through LDS with flat coalesced loads (see k_region_finalize_weighted)
+    // a thread owns a region, but rows of C words are not coalescable per thread: the workgroup's 256 rows of histogram words are
+    // staged through LDS with flat, fully coalesced loads (row stride padded to an odd word count: conflict-free per-thread reads)
     extern __shared__ __attribute__((aligned(16))) unsigned char fin_smem[];
     unsigned* s_hist = reinterpret_cast<unsigned*>(fin_smem);
     const int CP = C | 1;

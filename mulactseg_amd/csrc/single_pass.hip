@@ -488,13 +488,14 @@ __global__ __launch_bounds__(kThreads, 2) void k_single_pass_ring(const float* _
                                                                    mas_u64* __restrict__ class_sum, unsigned* __restrict__ hist) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     mas_u64* t_sum = reinterpret_cast<mas_u64*>(smem);                                        // [kSlots * C]
-    mas_u64* s_part = reinterpret_cast<mas_u64*>(smem + sizeof(mas_u64) * kSlots * C);         // [4][CT]
+    mas_u64* s_tot = reinterpret_cast<mas_u64*>(smem + sizeof(mas_u64) * kSlots * C);          // [CT] (of the 4 * CT in smem_bytes)
     unsigned* t_hist = reinterpret_cast<unsigned*>(smem + sizeof(mas_u64) * (kSlots * C + 4 * CT));   // [kSlots * C]
     int* t_keys = reinterpret_cast<int*>(smem + sizeof(mas_u64) * (kSlots * C + 4 * CT) + sizeof(unsigned) * kSlots * C);
     unsigned* s_acc = reinterpret_cast<unsigned*>(t_keys + kSlots);                            // [CT][kThreads]
 
     for (int i = threadIdx.x; i < kSlots; i += kThreads) t_keys[i] = -1;
     for (int i = threadIdx.x; i < kSlots * C; i += kThreads) { t_sum[i] = 0; t_hist[i] = 0; }
+    if (threadIdx.x < CT) s_tot[threadIdx.x] = 0;
 #pragma unroll
     for (int c = 0; c < CT; ++c) s_acc[c * kThreads + threadIdx.x] = 0;
     __syncthreads();
@@ -522,6 +523,12 @@ __global__ __launch_bounds__(kThreads, 2) void k_single_pass_ring(const float* _
         return (unsigned)y * (unsigned)W + xc;
     };
     auto ok_of = [&](int it) -> bool { return okx && (ybase + it * 4 < H); };
+    // where the trip past the end points: the first four pixels of this wave's LAST row in this tile column (clamped as off_of
+    // clamps), the same for all 64 lanes -- the 16 bytes lane 0 asked for one issue earlier, so they are on their way or in L2.
+    // The row is < H and tx * kTileW + 4 <= W, so it lies inside picture b for every shape the launcher sends here; W % 4 == 0
+    // makes it a multiple of four elements, which is 16 B of logits and 32 / 16 / 8 B of i64 / i32 / u16 ids
+    const int ylast = ybase + (kRingRows - 1) * 4;
+    const unsigned off_dead = (unsigned)(ylast < H ? ylast : H - 1) * (unsigned)W + (unsigned)(tx * kTileW);
 
     RowRegs<CT, IdT> A, B;
     int last_id = -2, last_slot = -1;
@@ -532,26 +539,37 @@ __global__ __launch_bounds__(kThreads, 2) void k_single_pass_ring(const float* _
         __builtin_amdgcn_sched_barrier(0);
         ring_consume<CT, EXACT, IdT>(A, ok_of(it), C, S, invT, s_acc, t_keys, t_sum, t_hist, gsum, ghist, last_id, last_slot);
         __builtin_amdgcn_sched_barrier(0);
-        // the last trip re-reads its own second row (an L2 hit, never consumed): the wait counts stay static
-        ring_issue<CT, EXACT, IdT>(A, zb, sb, C, HW, off_of(it + 2 < kRingRows ? it + 2 : kRingRows - 1));
+        // the last trip issues a row nobody consumes, so that the wait counts stay static.  The logits are loaded non-temporally:
+        // a re-read of a real row would come from HBM again (one row in sixteen).  With one address for the whole wave it asks
+        // for a single 16-B segment per class and id load instead (k_class_prob_sum_ring, scorer.hip, does the same)
+        ring_issue<CT, EXACT, IdT>(A, zb, sb, C, HW, it + 2 < kRingRows ? off_of(it + 2) : off_dead);
         __builtin_amdgcn_sched_barrier(0);
         ring_consume<CT, EXACT, IdT>(B, ok_of(it + 1), C, S, invT, s_acc, t_keys, t_sum, t_hist, gsum, ghist, last_id, last_slot);
         __builtin_amdgcn_sched_barrier(0);
     }
 
     __syncthreads();
+    // class sums of the strip: wave w takes classes w, w + 4, ..; a lane adds the four 64-word quarters of a class row (independent,
+    // conflict-free reads; the bias comes off each word in 32-bit arithmetic) and sends its share to the class's LDS total.  No
+    // step waits for another: the reads are issued together and the adds are fire-and-forget
+    constexpr int kWaves = kThreads / MAS_WAVE;
+    unsigned w4[(CT + kWaves - 1) / kWaves][4];
 #pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        mas_u64 a = s_acc[c * kThreads + threadIdx.x] - (unsigned)(kRingRows * 4) * MAS_PROBQ_BIAS;
+    for (int i = 0; i < (CT + kWaves - 1) / kWaves; ++i) {
+        const int c = min(wave + i * kWaves, CT - 1);       // a class past the end reads the last row (unconditional reads) and adds nothing
 #pragma unroll
-        for (int off = MAS_WAVE / 2; off > 0; off >>= 1) a += __shfl_down(a, off, MAS_WAVE);
-        if (lane == 0) s_part[wave * CT + c] = a;
+        for (int k = 0; k < 4; ++k) w4[i][k] = s_acc[c * kThreads + k * MAS_WAVE + lane];
+    }
+#pragma unroll
+    for (int i = 0; i < (CT + kWaves - 1) / kWaves; ++i) {
+        const int c = wave + i * kWaves;
+        const unsigned bias = (unsigned)(kRingRows * 4) * MAS_PROBQ_BIAS;
+        const mas_u64 a = ((mas_u64)(w4[i][0] - bias) + (mas_u64)(w4[i][1] - bias)) + ((mas_u64)(w4[i][2] - bias) + (mas_u64)(w4[i][3] - bias));
+        if (c < CT) lds_add(&s_tot[c], a);
     }
     __syncthreads();
     if (threadIdx.x < CT && (EXACT || (int)threadIdx.x < C)) {
-        mas_u64 a = 0;
-#pragma unroll
-        for (int w = 0; w < kThreads / MAS_WAVE; ++w) a += s_part[w * CT + threadIdx.x];
+        const mas_u64 a = s_tot[threadIdx.x];
         if (a) atomicAdd(&prob_sum[(size_t)b * C + threadIdx.x], a);
     }
     for (int i = threadIdx.x; i < kSlots * C; i += kThreads) {
@@ -565,49 +583,126 @@ __global__ __launch_bounds__(kThreads, 2) void k_single_pass_ring(const float* _
     }
 }
 
+// all-reduce over a 16-lane row in four DPP steps: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_ror:8
+template <int CTRL>
+__device__ __forceinline__ unsigned row_peer(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false); }
+__device__ __forceinline__ void row_sum(unsigned& v) {
+    v += row_peer<0xB1>(v); v += row_peer<0x4E>(v); v += row_peer<0x141>(v); v += row_peer<0x128>(v);
+}
+__device__ __forceinline__ unsigned row_max(unsigned v) {
+    v = max(v, row_peer<0xB1>(v)); v = max(v, row_peer<0x4E>(v)); v = max(v, row_peer<0x141>(v)); return max(v, row_peer<0x128>(v));
+}
+__device__ __forceinline__ unsigned row_min(unsigned v) {
+    v = min(v, row_peer<0xB1>(v)); v = min(v, row_peer<0x4E>(v)); v = min(v, row_peer<0x141>(v)); return min(v, row_peer<0x128>(v));
+}
+
 // score[r] = floor( (sum_c class_sum[r,c] * W31[c]) >> 31  /  n_r ) * 2^-40 ; dominant class; ban
-__global__ __launch_bounds__(kThreads) void k_region_finalize_weighted(const mas_u64* __restrict__ class_sum,
+// PAIRS: C even and the tensors aligned for the two-class vector accesses (the launcher checks); it fits 128 registers (4 waves/SIMD)
+// without scratch, the element-wise form needs a few more
+template <bool PAIRS>
+__global__ __launch_bounds__(kThreads, PAIRS ? 4 : 3) void k_region_finalize_weighted(const mas_u64* __restrict__ class_sum,
                                                                         const unsigned* __restrict__ hist, long long n_regions,
                                                                         int C, const unsigned* __restrict__ w31, int ban_class,
                                                                         float* __restrict__ score, int* __restrict__ dominant,
                                                                         unsigned* __restrict__ count,
                                                                         long long* __restrict__ hist_i64) {
-    // a thread owns a region, but rows of C words are not coalescable per thread: the workgroup's 256 rows are staged
-    // through LDS with flat, fully coalesced loads (row stride padded to an odd word count: conflict-free per-thread reads)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int CP = C | 1;
-    mas_u64* s_sum = reinterpret_cast<mas_u64*>(smem);                          // [kThreads][CP]
-    unsigned* s_hist = reinterpret_cast<unsigned*>(s_sum + (size_t)kThreads * CP);   // [kThreads][CP]
-    const long long r0 = (long long)blockIdx.x * kThreads;
-    const long long rows = (n_regions - r0) < kThreads ? (n_regions - r0) : kThreads;
-    const long long words = rows * C;
-    for (long long i = threadIdx.x; i < words; i += kThreads) {
-        const int row = (int)(i / C), col = (int)(i - (long long)row * C);
-        const unsigned hv = hist[r0 * C + i];
-        s_sum[row * CP + col] = class_sum[r0 * C + i];
-        s_hist[row * CP + col] = hv;
-        if (hist_i64) hist_i64[r0 * C + i] = (long long)hv;
+    // A wave owns 64 consecutive regions and reads them in 16 trips.  In a trip each 16-lane row reads ONE region's row of C words,
+    // lane j of the row the classes 2j and 2j + 1 (one 16-B and one 8-B load when PAIRS), so a load instruction covers whole rows
+    // and nothing is staged through LDS.  Row g takes region 16 g + trip: after the row-wide reduction (DPP, every lane of the
+    // row gets the totals) lane j keeps those of trip j, which leaves region l of the wave in lane l for the division and the
+    // coalesced stores.  All sums are integers, so the order of the additions does not show in the result.
+    const int lane = threadIdx.x & (MAS_WAVE - 1);
+    const int j = lane & 15;
+    // first region of this wave, in a scalar register: the row bases below are scalar and a lane's offsets 32-bit
+    const long long r0 = (long long)blockIdx.x * kThreads + __builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~(MAS_WAVE - 1)));
+    if (r0 >= n_regions) return;
+    const int rows = (int)((n_regions - r0) < MAS_WAVE ? (n_regions - r0) : MAS_WAVE);
+    const mas_u64* cs = class_sum + r0 * C;          // at most 64 * 32 words from here
+    const unsigned* hs = hist + r0 * C;
+    long long* ho = hist_i64 ? hist_i64 + r0 * C : nullptr;
+    const int c0 = 2 * j;
+    const bool in0 = c0 < C, in1 = c0 + 1 < C;       // PAIRS (C even): in0 == in1
+    const unsigned wa = in0 ? w31[c0] : 0u, wb = in1 ? w31[c0 + 1] : 0u;
+
+    // eight trips' loads are in flight at a time (48 registers); two such halves
+    constexpr int kTrips = MAS_WAVE / 8;
+    unsigned n_lo = 0, n_hi = 0, arg = 0, l0 = 0, l1 = 0, l2 = 0, l3 = 0;
+#pragma unroll 1
+    for (int t0 = 0; t0 < 2 * kTrips; t0 += kTrips) {
+        uint2 hv[kTrips];
+        mas_u64 sa[kTrips], sb[kTrips];
+#pragma unroll
+        for (int t = 0; t < kTrips; ++t) {
+            const int row = (lane & 48) + t0 + t;
+            // no branch around a load: a lane with nothing to read takes the wave's first word and drops it
+            const bool live0 = in0 && row < rows, live1 = in1 && row < rows;
+            const unsigned o = (unsigned)(row * C + c0);
+            if (PAIRS) {
+                hv[t] = *reinterpret_cast<const uint2*>(hs + (live0 ? o : 0u));
+                const ulonglong2 q = *reinterpret_cast<const ulonglong2*>(cs + (live0 ? o : 0u));
+                sa[t] = q.x; sb[t] = q.y;
+            } else {
+                hv[t] = make_uint2(hs[live0 ? o : 0u], hs[live1 ? o + 1u : 0u]);
+                sa[t] = cs[live0 ? o : 0u];
+                sb[t] = cs[live1 ? o + 1u : 0u];
+            }
+            hv[t].x = live0 ? hv[t].x : 0u;
+            hv[t].y = live1 ? hv[t].y : 0u;
+        }
+
+#pragma unroll
+        for (int t = 0; t < kTrips; ++t) {
+            const int row = (lane & 48) + t0 + t;
+            const unsigned o = (unsigned)(row * C + c0);
+            const unsigned va = hv[t].x, vb = hv[t].y;
+            if (ho && row < rows) {
+                if (PAIRS) {
+                    if (in0) *reinterpret_cast<longlong2*>(ho + o) = make_longlong2((long long)va, (long long)vb);
+                } else {
+                    if (in0) ho[o] = (long long)va;
+                    if (in1) ho[o + 1u] = (long long)vb;
+                }
+            }
+            uint64_t hi = 0, lo = 0;
+            mas_mac_u64_u32(va ? (uint64_t)sa[t] : 0u, wa, &hi, &lo);      // classes without pixels do not count, whatever their sum holds
+            mas_mac_u64_u32(vb ? (uint64_t)sb[t] : 0u, wb, &hi, &lo);
+            // a lane's two products are below 2^97 and a row has 16 lanes: four 27-bit limbs hold the lane's value, and their sums
+            // over the row stay below 2^31
+            const unsigned m27 = (1u << 27) - 1u;
+            unsigned q0 = (unsigned)lo & m27;
+            unsigned q1 = (unsigned)(lo >> 27) & m27;
+            unsigned q2 = (unsigned)((lo >> 54) | (hi << 10)) & m27;
+            unsigned q3 = (unsigned)(hi >> 17);
+            // pixel counts: 24-bit limbs (a lane's two counts are below 2^33)
+            const mas_u64 nn = (mas_u64)va + vb;
+            unsigned p0 = (unsigned)nn & 0xffffffu, p1 = (unsigned)(nn >> 24);
+            // dominant class: the largest count, the lowest class among equals (all counts zero: class 0)
+            unsigned best = va > vb ? va : vb;
+            row_sum(q0); row_sum(q1); row_sum(q2); row_sum(q3); row_sum(p0); row_sum(p1);
+            best = row_max(best);
+            unsigned a = va == best ? (unsigned)c0 : (vb == best ? (unsigned)c0 + 1u : 64u);
+            a = row_min(a);
+            const bool mine = j == t0 + t;
+            l0 = mine ? q0 : l0; l1 = mine ? q1 : l1; l2 = mine ? q2 : l2; l3 = mine ? q3 : l3;
+            n_lo = mine ? p0 : n_lo; n_hi = mine ? p1 : n_hi;
+            arg = mine ? a : arg;
+        }
     }
-    __syncthreads();
-    if ((long long)threadIdx.x >= rows) return;
-    const long long r = r0 + threadIdx.x;
-    const unsigned* h = s_hist + threadIdx.x * CP;
-    const mas_u64* cs = s_sum + threadIdx.x * CP;
-    unsigned long long n = 0;
-    unsigned best = 0;
-    int arg = 0;
-    uint64_t hi = 0, lo = 0;
-    for (int c = 0; c < C; ++c) {
-        const unsigned v = h[c];
-        n += v;
-        if (v > best) { best = v; arg = c; }
-        if (v) mas_mac_u64_u32((uint64_t)cs[c], w31[c], &hi, &lo);
-    }
+
+    if (lane >= rows) return;
+    const long long r = r0 + lane;
+    // (hi:lo) = l0 + l1 * 2^27 + l2 * 2^54 + l3 * 2^81
+    uint64_t lo = (uint64_t)l0 + ((uint64_t)l1 << 27);                   // < 2^59
+    uint64_t hi = ((uint64_t)l2 >> 10) + ((uint64_t)l3 << 17);
+    const uint64_t m = (uint64_t)l2 << 54;
+    lo += m;
+    hi += lo < m ? 1u : 0u;
+    const unsigned long long n = (unsigned long long)n_lo + ((unsigned long long)n_hi << 24);
     float sc = 0.0f;
     if (n) sc = mas_fixed_mean(mas_shr31_u128(hi, lo), n, MAS_SCORE_FRAC);
-    if (ban_class >= 0 && arg == ban_class) sc = 0.0f;
+    if (ban_class >= 0 && (int)arg == ban_class) sc = 0.0f;
     score[r] = sc;
-    if (dominant) dominant[r] = arg;
+    if (dominant) dominant[r] = (int)arg;
     if (count) count[r] = (unsigned)n;
 }
 
@@ -768,9 +863,14 @@ extern "C" int mas_region_finalize_weighted(const uint64_t* class_sum, const uin
     if (C < 1 || C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
     const long long nblk = (n_regions + kThreads - 1) / kThreads;
     if (nblk > 0x7fffffffLL) return MAS_ERR_SHAPE;
-    const size_t smem = (sizeof(mas_u64) + sizeof(unsigned)) * (size_t)kThreads * (C | 1);
-    hipLaunchKernelGGL(k_region_finalize_weighted, dim3((unsigned)nblk), dim3(kThreads), smem, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const mas_u64*>(class_sum), hist, (long long)n_regions, C, w31, ban_class, score, dominant,
-                       count, reinterpret_cast<long long*>(hist_i64));
+    const bool pairs = C % 2 == 0 && ((uintptr_t)class_sum & 15) == 0 && ((uintptr_t)hist & 7) == 0 && ((uintptr_t)hist_i64 & 15) == 0;
+    if (pairs)
+        hipLaunchKernelGGL(k_region_finalize_weighted<true>, dim3((unsigned)nblk), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                           reinterpret_cast<const mas_u64*>(class_sum), hist, (long long)n_regions, C, w31, ban_class, score,
+                           dominant, count, reinterpret_cast<long long*>(hist_i64));
+    else
+        hipLaunchKernelGGL(k_region_finalize_weighted<false>, dim3((unsigned)nblk), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                           reinterpret_cast<const mas_u64*>(class_sum), hist, (long long)n_regions, C, w31, ban_class, score,
+                           dominant, count, reinterpret_cast<long long*>(hist_i64));
     return mas_launch_status();
 }
