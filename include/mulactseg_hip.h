@@ -59,7 +59,8 @@ extern "C" {
  * mas_uncertainty_accum_lowres and mas_uncertainty_reference, then mas_train_augment_u8, mas_photometric and
  * mas_photometric_reference, then mas_partial_loss_reference and the MAS_LOSS_RC / MAS_LOSS_TOPONE flag bits (a library built before
  * them treats the bits as unset), then mas_online_plbl_labels, mas_label_ce_fwd_lowres / _bwd_lowres / _value and
- * mas_online_plbl_reference: new entry
+ * mas_online_plbl_reference, then mas_online_soft_weights, mas_soft_ce_fwd_lowres / _bwd_lowres and mas_simw_plbl_reference with the
+ * MAS_OPL_WEIGHT_SIM and MAS_LCE_SIGNED flag bits (a library built before them answers MAS_ERR_RANGE to either bit): new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -238,10 +239,13 @@ int mas_partial_loss_reference(const float* z, const void* spx, int spx_dtype, c
  * mas_partial_loss_fwd_lowres with MAS_LOSS_GROUP | MAS_LOSS_GROUP_ONLY_MULTI, which this call runs.  A valid pixel takes the class
  * whose prototype feature has the largest inner product (a sequential fma chain over the channels) with its own feature, candidates
  * walked in ascending class order, replaced on strict '>'.  labels u8 [N,H,W] (255 = none), weight f32 [N,H,W] (0 = none) =
- * softmax(up(zq_p) * invT)[label]; with MAS_OPL_WEIGHT_WO_PROTO a prototype pixel's weight is 1.0.
+ * softmax(up(zq_p) * invT)[label]; with MAS_OPL_WEIGHT_WO_PROTO a prototype pixel's weight is 1.0.  With MAS_OPL_WEIGHT_SIM
+ * (trainer/active_onlinesimwplbl_multi_predignore.py:15-125, LocalsimWProtoCE) the weight is the inner product with the chosen
+ * prototype itself, which may be negative; the labels are the same.  Both weight flags at once: MAS_ERR_RANGE.
  * 1 <= Ch <= MAS_OPL_MAX_FEAT (MAS_ERR_RANGE), 2 <= C <= MAS_MAX_CLASSES; `work`: mas_online_plbl_work_bytes(N, S, C) bytes, 8-byte
  * aligned, not initialised by the caller (u64 acc[8] | the table u64 [N,S,C]).  Every check happens before the first launch. */
 #define MAS_OPL_WEIGHT_WO_PROTO 1
+#define MAS_OPL_WEIGHT_SIM 2
 #define MAS_OPL_MAX_FEAT 2048
 size_t mas_online_plbl_work_bytes(int N, int S, int C);
 int mas_online_plbl_labels(const float* zq_p, const float* featq, int Ch, int h, int w, const void* spx, int spx_dtype,
@@ -256,11 +260,15 @@ int mas_online_plbl_labels(const float* zq_p, const float* featq, int Ch, int h,
  * zeroes acc first; loss (may be NULL: a data-parallel caller all-reduces acc and calls mas_label_ce_value) = acc[0] / acc[1], and
  * for acc[1] == 0: 0, or NaN with MAS_LCE_EMPTY_NAN.  Backward: d zq from (grad[0] / acc[1]) * invT * wgt * (softmax - onehot) of the
  * pixels that were counted, added through the four taps into dzq_fix [N,C,h,w] (zeroed by the call; MAS_GRAD_FRAC_BITS, integer
- * atomics) and, with dzq != NULL, converted by mas_fix_to_float.  weight may be NULL for MAS_LCE_UNWEIGHTED. */
+ * atomics) and, with dzq != NULL, converted by mas_fix_to_float.  weight may be NULL for MAS_LCE_UNWEIGHTED.
+ * MAS_LCE_SIGNED (with MAS_LCE_WEIGHTED only, else MAS_ERR_RANGE) is for weights that may be negative: acc[0] is a two's complement
+ * sum, a negative term subtracts floor(|term| * 2^MAS_LOSS_FRAC_BITS), and the value is (int64)acc[0] / acc[1].  Without it a negative
+ * term adds 0, as before. */
 #define MAS_LCE_UNWEIGHTED 0
 #define MAS_LCE_WEIGHTED 1
 #define MAS_LCE_THRESHOLD 2
 #define MAS_LCE_EMPTY_NAN 4
+#define MAS_LCE_SIGNED 8
 int mas_label_ce_fwd_lowres(const float* zq, int h, int w, const uint8_t* labels, const float* weight, int N, int C, int H, int W,
                             float invT, int flags, float th, uint64_t* acc /* [2] */, float* loss /* [1] or NULL */, void* stream);
 int mas_label_ce_value(const uint64_t* acc, int flags, float* loss, void* stream);
@@ -276,6 +284,40 @@ int mas_online_plbl_reference(const float* zq_p, const float* featq, int Ch, int
                               const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, float invT, int flags,
                               uint64_t* gmax, uint8_t* labels, float* weight, const float* zq, float invT_ce, int ce_flags, float th,
                               const float* grad, uint64_t* acc, float* loss, int64_t* dzq_fix);
+
+/* ---------------------------------------------------------------------------------------------
+ * Soft targets from the prototype similarities and the cross entropy against them (trainer/active_pwce_multi_predignore.py:17-155,
+ * JointLocalProtoWeightingCE).  Per-pixel arithmetic: csrc/online_plbl.h.
+ *
+ * mas_online_soft_weights: one call for the batch, no host round trip: memset, the group scan (the prototype table of
+ * mas_online_plbl_labels), then one lane per pixel.  softw f32 [N,C,H,W] need not be initialised; only the entries (n, c, pixel) of a
+ * valid pixel's candidate classes c are written: the softmax over those candidates of sim(pixel, prototype of c) * invtau.  live
+ * int32 [N] (4-byte aligned) is zeroed by the call and set to 1 for every picture with a valid pixel.  invtau > 0 (MAS_ERR_RANGE);
+ * `work` as for mas_online_plbl_labels.
+ *
+ * mas_soft_ce_fwd_lowres / _bwd_lowres: a pixel is counted when its mask byte is set, its id lies in [0, S) and its picture is live (the
+ * reference skips a picture without a valid pixel, with its one-hot pixels; a masked pixel with an id outside [0, S), on which the
+ * reference raises, is not counted).  With p = softmax(up(zq) * invT): a valid pixel adds sum_c softw[n,c,pixel] * -log(p_c + 1e-8)
+ * over its candidates, a pixel with one candidate -log(p_c + 1e-8), one with none 0.  acc, loss, grad, dzq_fix and dzq as for
+ * mas_label_ce_fwd_lowres / _bwd_lowres (the value of an empty batch is 0; mas_label_ce_value with flags 0 turns an all-reduced acc
+ * into the loss).  Every check happens before the first launch. */
+int mas_online_soft_weights(const float* zq_p, const float* featq, int Ch, int h, int w, const void* spx, int spx_dtype,
+                            const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, float invT, float invtau,
+                            void* work, size_t work_bytes, float* softw, int32_t* live, void* stream);
+int mas_soft_ce_fwd_lowres(const float* zq, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits,
+                           const float* softw, const int32_t* live, int N, int C, int H, int W, int S, float invT,
+                           uint64_t* acc /* [2] */, float* loss /* [1] or NULL */, void* stream);
+int mas_soft_ce_bwd_lowres(const float* zq, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits,
+                           const float* softw, const int32_t* live, const uint64_t* acc, const float* grad /* [1] */, int N, int C, int H,
+                           int W, int S, float invT, int64_t* dzq_fix /* [N,C,h,w] */, float* dzq /* [N,C,h,w] or NULL */, void* stream);
+
+/* The CPU-side statement of the three entry points above: HOST pointers, no device is touched.  With zq_p != NULL it writes softw (where
+ * defined) and live; with zq_p == NULL both are the caller's.  With zq != NULL it then writes acc [2], loss [1] (may be NULL) and, for
+ * grad [1], dzq_fix [N,C,h,w] (may be NULL). */
+int mas_simw_plbl_reference(const float* zq_p, const float* featq, int Ch, int h, int w, const void* spx, int spx_dtype,
+                            const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, float invT, float invtau,
+                            float* softw, int32_t* live, const float* zq, float invT_ce, const float* grad, uint64_t* acc, float* loss,
+                            int64_t* dzq_fix);
 
 /* =============================================================================================
  * K4  ordering of the region scores and the budgeted selection walk

@@ -26,7 +26,9 @@ LOWRES_GENERIC = 1
 UNC_BVSB, UNC_MARGIN, UNC_LEAST_CONFIDENCE, UNC_ENTROPY = 0, 1, 2, 3
 STAGE2_THR_MEDIAN, STAGE2_THR_MIN = 0, 1
 OPL_WEIGHT_WO_PROTO = 1                 # mas_online_plbl_labels: a prototype pixel's weight is 1.0 (--weight_wo_proto)
+OPL_WEIGHT_SIM = 2                      # ... the weight is the inner product with the chosen prototype (LocalsimWProtoCE)
 LCE_UNWEIGHTED, LCE_WEIGHTED, LCE_THRESHOLD, LCE_EMPTY_NAN = 0, 1, 2, 4     # mas_label_ce_*: the weight mode, and NaN for an empty mean
+LCE_SIGNED = 8                          # mas_label_ce_*: weights may be negative, the sum is two's complement
 PM_BRIGHTNESS, PM_CONTRAST, PM_SATURATION, PM_HUE = 0, 1, 2, 3
 ABI_VERSION = 9        # MAS_ABI_VERSION of include/mulactseg_hip.h this table was written against (load() refuses any other library)
 
@@ -175,6 +177,11 @@ SIGNATURES = {
     "mas_label_ce_bwd_lowres": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp]),
     "mas_online_plbl_reference": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _f, _i, _f,
                                        _vp, _vp, _vp, _vp]),
+    "mas_online_soft_weights": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _c.c_size_t, _vp, _vp, _vp]),
+    "mas_soft_ce_fwd_lowres": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "mas_soft_ce_bwd_lowres": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "mas_simw_plbl_reference": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _f, _vp, _vp, _vp,
+                                     _vp]),
 }
 
 _lib = None

@@ -16,6 +16,22 @@
  *             term != 0.0f.  A term below zero (the rounding of mas_logf next to p = 1) is counted and adds 0 (mas_fix).
  *   gradient  k = ((grad / (float)count) * invT) * wgt ;  d_c = k * (p_c - [c == label]) ;  every tap adds
  *             round_to_nearest_even(d_c * (ly * lx) * 2^MAS_GRAD_FRAC_BITS) to its element.
+ *
+ * The similarity-weighted forms (LocalsimWProtoCE, JointLocalProtoWeightingCE):
+ *   sim weight   with MAS_OPL_WEIGHT_SIM the weight of a valid pixel is the chain value `best` of the chosen candidate, which may be
+ *                negative; labels are unchanged.
+ *   signed term  with MAS_LCE_SIGNED (mode WEIGHTED) the sum is two's complement: mas_fix(|term|) is added for term > 0 and subtracted
+ *                for term < 0; value = (double)(int64)sum * 2^-MAS_LOSS_FRAC_BITS / count.  Counting and gradient are unchanged
+ *                (k = scale * wgt carries the sign).
+ *   live         a picture is live when it has at least one valid pixel.
+ *   counted      mask set, id in [0, S), picture live.  (A masked pixel with an id outside [0, S) makes the reference raise an index
+ *                error; here it is not counted.)
+ *   soft weight  of a valid pixel, over its candidates c in Y (ascending): m = max sim_c ; e_c = exp_np(fma(sim_c, invtau, -(m*invtau))) ;
+ *                sum = ((e_0+e_1)+...) ; w_c = e_c * (1/sum)  -- the operation order of mas_opl_softmax.
+ *   soft term    p = softmax(up(zq) * invT).  Valid pixel: t = sum over c in Y ascending of w_c * (-log(p_c + 1e-8f)), added in f32 from
+ *                0.0f; a counted pixel with one candidate: t = -log(p_c + 1e-8f); with none: t = 0.  acc[0] += mas_fix(t), acc[1] += 1.
+ *   soft grad    q_c = p_c / (p_c + 1e-8f) ; A = sum over c in Y ascending of w_c * q_c (w = 1 for a one-candidate pixel) ;
+ *                d_j = ((grad / (float)count) * invT) * (p_j * A - w_j * q_j), w_j = 0 off Y; through the taps as above.
  */
 #ifndef MULACTSEG_ONLINE_PLBL_H
 #define MULACTSEG_ONLINE_PLBL_H
@@ -107,12 +123,76 @@ MAS_HD float mas_opl_term(int mode, float wgt, float ce, int* counted) {
     return t;
 }
 
-/* acc = {sum, count} -> the loss value */
+/* what one counted term adds to the u64 sum: mas_fix(term) (0 for a negative term), or with `sgn` the two's complement of
+ * mas_fix(|term|) for a negative one */
+MAS_HD uint64_t mas_opl_fix_term(float term, int sgn) {
+    if (!sgn) return mas_fix(term, MAS_LOSS_FRAC_BITS);
+    const uint64_t q = mas_fix(mas_u2f(mas_f2u(term) & 0x7fffffffu), MAS_LOSS_FRAC_BITS);
+    return (term < 0.0f) ? (uint64_t)0 - q : q;
+}
+
+/* acc = {sum, count} -> the loss value; with MAS_LCE_SIGNED the sum is read as two's complement */
 MAS_HD float mas_opl_value(uint64_t sum, uint64_t count, int flags) {
     if (count == 0) return (flags & MAS_LCE_EMPTY_NAN) ? mas_u2f(0x7fc00000u) : 0.0f;
     union { double d; uint64_t u; } s;
     s.u = (uint64_t)(1023 - MAS_LOSS_FRAC_BITS) << 52;
-    return (float)(((double)sum * s.d) / (double)count);
+    const double v = (flags & MAS_LCE_SIGNED) ? (double)(int64_t)sum : (double)sum;
+    return (float)((v * s.d) / (double)count);
+}
+
+/* ---- soft targets from the prototype similarities ---- */
+#define MAS_OPL_EPS 1e-8f
+
+/* the raw similarities of one pixel, `stride` floats apart at the classes of Y, become its soft weights in place */
+MAS_HD void mas_opl_soft_normalise(float* sw, size_t stride, uint32_t Y, float invtau) {
+    if (!Y) return;
+    float m = sw[(size_t)__builtin_ctz(Y) * stride];
+    for (uint32_t y = Y & (Y - 1u); y; y &= y - 1u) {
+        const float v = sw[(size_t)__builtin_ctz(y) * stride];
+        m = (v > m) ? v : m;
+    }
+    const float negM = -(m * invtau);
+    float sum = 0.0f;
+    for (uint32_t y = Y; y; y &= y - 1u) {
+        float* p = sw + (size_t)__builtin_ctz(y) * stride;
+        const float e = mas_expf_np(mas_fmaf(*p, invtau, negM));
+        *p = e;
+        sum = (y == Y) ? e : (sum + e);
+    }
+    const float rinv = 1.0f / sum;
+    for (uint32_t y = Y; y; y &= y - 1u) {
+        float* p = sw + (size_t)__builtin_ctz(y) * stride;
+        *p = *p * rinv;
+    }
+}
+
+/* the candidates of a counted pixel within the C classes, and whether it reads soft weights (a valid pixel) */
+MAS_HD uint32_t mas_opl_cands(uint32_t Y, int C, int* multi) {
+    *multi = __builtin_popcount(Y) > 1;
+    return C < 32 ? (Y & ((1u << C) - 1u)) : Y;
+}
+
+/* soft CE term of a counted pixel with probabilities p: its candidates Yc, soft weights `stride` apart at sw (read when multi).
+ * *A = sum w_c * q_c for the gradient. */
+template <int CT>
+MAS_HD float mas_opl_soft_term(const float (&p)[CT], int C, uint32_t Yc, int multi, const float* sw, size_t stride, float* A) {
+    float t = 0.0f, a = 0.0f;
+    MAS_OPL_UNROLL
+    for (int c = 0; c < CT; ++c) {
+        if (c < C && ((Yc >> c) & 1u)) {
+            const float w = multi ? sw[(size_t)c * stride] : 1.0f;
+            const float pe = p[c] + MAS_OPL_EPS;
+            t = t + w * (-mas_logf(pe));
+            a = a + w * (p[c] / pe);
+        }
+    }
+    *A = a;
+    return t;
+}
+
+/* d_j / k of the soft CE: p_j * A - w_j * q_j */
+MAS_HD float mas_opl_soft_dir(float pj, float A, int in_y, float wj) {
+    return in_y ? (pj * A - wj * (pj / (pj + MAS_OPL_EPS))) : (pj * A);
 }
 
 /* signed fixed point (MAS_GRAD_FRAC_BITS) of one gradient contribution, round to nearest even -- grad_fix of losses.hip */

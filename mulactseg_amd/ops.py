@@ -351,6 +351,7 @@ def partial_loss_bwd_fused(z, size, spx, mask, state, grad, invT, weights=None, 
 # online local-prototype pseudo labels and the cross entropy on them (csrc/online_plbl.hip)
 # ------------------------------------------------------------------------------------------------
 LCE_UNWEIGHTED, LCE_WEIGHTED, LCE_THRESHOLD, LCE_EMPTY_NAN = _lib.LCE_UNWEIGHTED, _lib.LCE_WEIGHTED, _lib.LCE_THRESHOLD, _lib.LCE_EMPTY_NAN
+LCE_SIGNED = _lib.LCE_SIGNED
 
 
 def _plbl_bits(targets, bits):
@@ -372,11 +373,17 @@ def _plbl_shapes(zq_p, featq, size, spx, mask, bits):
     return N, C, h, w, H, W, featq.shape[1], bits.shape[1]
 
 
-def online_pseudo_labels(zq_p, featq, size, spx, mask, targets=None, bits=None, invT=1.0, weight_wo_proto=False):
+def _weight_flags(weight_wo_proto, weight_sim):
+    return (_lib.OPL_WEIGHT_WO_PROTO if weight_wo_proto else 0) | (_lib.OPL_WEIGHT_SIM if weight_sim else 0)
+
+
+def online_pseudo_labels(zq_p, featq, size, spx, mask, targets=None, bits=None, invT=1.0, weight_wo_proto=False, weight_sim=False):
     """The reference's ``generate_plbl`` (``trainer/active_onlinewplbl_multi_predignore.py:20-125``) for the whole batch in ONE library
     call and without a host round trip: ``zq_p`` [N,C,h,w] quarter-resolution logits of the eval-mode forward, ``featq`` [N,Ch,h,w]
     its L2-normalised point features, both interpolated to ``size`` = (H, W) per pixel inside the kernel; ``spx`` / ``mask`` [N,H,W];
-    ``targets`` u8 [N,S,cols] or ready ``bits`` int32 [N,S].  Returns (labels u8 [N,H,W], 255 = none; weight f32 [N,H,W], 0 = none)."""
+    ``targets`` u8 [N,S,cols] or ready ``bits`` int32 [N,S].  Returns (labels u8 [N,H,W], 255 = none; weight f32 [N,H,W], 0 = none).
+    ``weight_sim``: the weight is the pixel's inner product with the chosen prototype (``LocalsimWProtoCE``), which may be negative,
+    instead of the softmax probability of the label; the library refuses it together with ``weight_wo_proto``."""
     _need(zq_p, "inputs_plbl", torch.float32)
     _need(featq, "feats_plbl", torch.float32)
     _need(spx, "superpixels")
@@ -391,7 +398,7 @@ def online_pseudo_labels(zq_p, featq, size, spx, mask, targets=None, bits=None, 
     weight = torch.empty((N, H, W), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(lib.mas_online_plbl_labels(zq_p.data_ptr(), featq.data_ptr(), Ch, h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(),
-                                              bits.data_ptr(), N, C, H, W, S, invT, _lib.OPL_WEIGHT_WO_PROTO if weight_wo_proto else 0,
+                                              bits.data_ptr(), N, C, H, W, S, invT, _weight_flags(weight_wo_proto, weight_sim),
                                               work.data_ptr(), work.numel() * 8, labels.data_ptr(), weight.data_ptr(), _stream(zq_p)),
                    "mas_online_plbl_labels")
     return labels, weight
@@ -461,20 +468,23 @@ class _LabelCELowRes(torch.autograd.Function):
         return dzq, None, None, None, None, None, None, None
 
 
-def label_ce_lowres(zq, size, labels, weight, invT, mode=LCE_UNWEIGHTED, th=0.0, empty_nan=False, reduce_acc=None):
+def label_ce_lowres(zq, size, labels, weight, invT, mode=LCE_UNWEIGHTED, th=0.0, empty_nan=False, reduce_acc=None, signed=False):
     """Mean cross entropy of ``F.interpolate(zq, size, 'bilinear', align_corners=False) * invT`` against ``labels`` u8 [N,H,W]
     (255 = none) with per-pixel weights, differentiable in ``zq``; the upsampled logits and their gradient never exist.  ``mode``:
     LCE_UNWEIGHTED (mean over the labelled pixels), LCE_WEIGHTED (``weight * ce``) or LCE_THRESHOLD (``(th < weight) * ce``), the last
-    two averaged over the non-zero terms.  No labelled (non-zero) pixel: 0, or NaN with ``empty_nan``.  Returns (loss, acc)."""
-    flags = int(mode) | (_lib.LCE_EMPTY_NAN if empty_nan else 0)
+    two averaged over the non-zero terms.  No labelled (non-zero) pixel: 0, or NaN with ``empty_nan``.  ``signed`` (LCE_WEIGHTED only):
+    the weights may be negative and a negative term subtracts from the sum; without it such a term adds 0.  Returns (loss, acc).  The
+    ``label_ce_fwd_lowres`` / ``_bwd_lowres`` halves take the same bit as ``LCE_SIGNED`` in ``flags``."""
+    flags = int(mode) | (_lib.LCE_EMPTY_NAN if empty_nan else 0) | (_lib.LCE_SIGNED if signed else 0)
     return _LabelCELowRes.apply(zq, (int(size[0]), int(size[1])), labels, weight, invT, flags, float(th), reduce_acc)
 
 
 def online_plbl_reference(zq_p, featq, size, spx, mask, targets=None, bits=None, invT=1.0, weight_wo_proto=False, zq=None, invT_ce=None,
-                          mode=LCE_UNWEIGHTED, th=0.0, empty_nan=False, grad=None, labels=None, weight=None):
+                          mode=LCE_UNWEIGHTED, th=0.0, empty_nan=False, grad=None, labels=None, weight=None, weight_sim=False, signed=False):
     """``online_pseudo_labels`` and ``label_ce_lowres`` on HOST tensors: the library's plain loop through csrc/online_plbl.h
     (``mas_online_plbl_reference``), the CPU-side statement of the arithmetic the kernels are checked against.  Needs no GPU.
-    With ``zq_p`` None the label and weight maps are the given ``labels`` / ``weight``.  Returns a dict: labels, weight, gmax (the
+    With ``zq_p`` None the label and weight maps are the given ``labels`` / ``weight``.  ``weight_sim`` / ``signed`` as in
+    ``online_pseudo_labels`` / ``label_ce_lowres``.  Returns a dict: labels, weight, gmax (the
     arg-pixel table, when labels were generated), and with ``zq``: loss f32 [1], acc i64 [2], and with ``grad`` (f32 [1]) dzq_fix."""
     out = {}
     lib = _lib.load()
@@ -501,11 +511,148 @@ def online_plbl_reference(zq_p, featq, size, spx, mask, targets=None, bits=None,
     if zq is not None:
         acc, loss = torch.zeros(2, dtype=torch.int64), torch.zeros(1, dtype=torch.float32)
         fix = torch.zeros(zq.shape, dtype=torch.int64) if grad is not None else None
-    flags = int(mode) | (_lib.LCE_EMPTY_NAN if empty_nan else 0)
-    _lib.check(lib.mas_online_plbl_reference(*gen, N, C, H, W, S, invT, _lib.OPL_WEIGHT_WO_PROTO if weight_wo_proto else 0, _opt(gmax),
+    flags = int(mode) | (_lib.LCE_EMPTY_NAN if empty_nan else 0) | (_lib.LCE_SIGNED if signed else 0)
+    _lib.check(lib.mas_online_plbl_reference(*gen, N, C, H, W, S, invT, _weight_flags(weight_wo_proto, weight_sim), _opt(gmax),
                                              labels.data_ptr(), _opt(weight), _opt(zq), invT if invT_ce is None else invT_ce, flags, float(th),
                                              _opt(grad), _opt(acc), _opt(loss), _opt(fix)), "mas_online_plbl_reference")
     out.update(labels=labels, weight=weight)
+    if zq is not None:
+        out.update(loss=loss, acc=acc)
+        if fix is not None:
+            out['dzq_fix'] = fix
+    return out
+
+
+def online_soft_weights(zq_p, featq, size, spx, mask, targets=None, bits=None, invT=1.0, inv_tau=1.0):
+    """The soft targets of the reference's ``JointLocalProtoWeightingCE`` (``trainer/active_pwce_multi_predignore.py:73-139``) for the
+    whole batch in ONE library call, no host round trip; arguments as ``online_pseudo_labels``.  Every valid pixel (selected, id in
+    range, multi-hot superpixel) gets, over its candidate classes, the softmax of its inner products with the classes' local prototypes
+    at ``inv_tau`` = ``inv_temperature(simw_temp)``.  Returns (softw f32 [N,C,H,W], allocated uninitialised: only the candidate planes
+    of valid pixels are written or read; live int32 [N]: the pictures with a valid pixel; bits int32 [N,S])."""
+    _need(zq_p, "inputs_plbl", torch.float32)
+    _need(featq, "feats_plbl", torch.float32)
+    _need(spx, "superpixels")
+    mask = _mask_u8(mask)
+    bits = _need(_plbl_bits(targets, bits), "bits", torch.int32)
+    N, C, h, w, H, W, Ch, S = _plbl_shapes(zq_p, featq, size, spx, mask, bits)
+    dev = zq_p.device
+    lib = _lib.load()
+    nbytes = int(lib.mas_online_plbl_work_bytes(N, S, C))
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)           # (zeroed inside the call)
+    softw = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
+    live = torch.empty(N, dtype=torch.int32, device=dev)                           # (zeroed inside the call)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mas_online_soft_weights(zq_p.data_ptr(), featq.data_ptr(), Ch, h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(),
+                                               bits.data_ptr(), N, C, H, W, S, invT, inv_tau, work.data_ptr(), work.numel() * 8,
+                                               softw.data_ptr(), live.data_ptr(), _stream(zq_p)), "mas_online_soft_weights")
+    return softw, live, bits
+
+
+def _soft_ce_check(zq, size, spx, mask, bits, softw, live):
+    N, C, h, w = zq.shape
+    H, W = int(size[0]), int(size[1])
+    if (tuple(spx.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W) or bits.dim() != 2 or bits.shape[0] != N
+            or tuple(softw.shape) != (N, C, H, W) or tuple(live.shape) != (N,)):
+        raise ValueError("shape mismatch between logits %s at size %s, superpixels %s, spmasks %s, bits %s, soft weights %s, live %s"
+                         % (tuple(zq.shape), (H, W), tuple(spx.shape), tuple(mask.shape), tuple(bits.shape), tuple(softw.shape),
+                            tuple(live.shape)))
+    return N, C, h, w, H, W, bits.shape[1]
+
+
+def soft_ce_fwd_lowres(zq, size, spx, mask, bits, softw, live, invT, reduce_acc=None):
+    """Forward half of ``soft_ce_lowres``: (loss f32 [1], acc i64 [2] = fixed-point sum and count); ``reduce_acc`` as in
+    ``label_ce_fwd_lowres``."""
+    _need(zq, "inputs", torch.float32)
+    _need(spx, "superpixels")
+    _need(mask, "spmasks", torch.uint8)
+    _need(bits, "bits", torch.int32)
+    _need(softw, "softw", torch.float32)
+    _need(live, "live", torch.int32)
+    N, C, h, w, H, W, S = _soft_ce_check(zq, size, spx, mask, bits, softw, live)
+    acc = torch.empty(2, dtype=torch.int64, device=zq.device)                     # (zeroed inside the call)
+    loss = torch.empty(1, dtype=torch.float32, device=zq.device)
+    lib = _lib.load()
+    with torch.cuda.device(zq.device):
+        st = _stream(zq)
+        _lib.check(lib.mas_soft_ce_fwd_lowres(zq.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
+                                              softw.data_ptr(), live.data_ptr(), N, C, H, W, S, invT, acc.data_ptr(),
+                                              None if reduce_acc is not None else loss.data_ptr(), st), "mas_soft_ce_fwd_lowres")
+        if reduce_acc is not None:
+            reduce_acc(acc)
+            _lib.check(lib.mas_label_ce_value(acc.data_ptr(), 0, loss.data_ptr(), st), "mas_label_ce_value")
+    return loss, acc
+
+
+def soft_ce_bwd_lowres(zq, size, spx, mask, bits, softw, live, acc, grad, invT, want_fix=False):
+    """Backward half: dzq [N,C,h,w] f32 for the upstream gradient ``grad`` f32 [1] (and the int64 sums it was rounded from)."""
+    _need(grad, "grad", torch.float32)
+    N, C, h, w, H, W, S = _soft_ce_check(zq, size, spx, mask, bits, softw, live)
+    fix = torch.empty((N, C, h, w), dtype=torch.int64, device=zq.device)          # (zeroed inside the call)
+    dzq = torch.empty_like(zq)
+    with torch.cuda.device(zq.device):
+        _lib.check(_lib.load().mas_soft_ce_bwd_lowres(zq.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
+                                                      softw.data_ptr(), live.data_ptr(), acc.data_ptr(), grad.data_ptr(), N, C, H, W, S,
+                                                      invT, fix.data_ptr(), dzq.data_ptr(), _stream(zq)), "mas_soft_ce_bwd_lowres")
+    return (dzq, fix) if want_fix else dzq
+
+
+class _SoftCELowRes(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, zq, size, spx, mask, bits, softw, live, invT, reduce_acc):
+        zq = zq.contiguous()
+        loss, acc = soft_ce_fwd_lowres(zq, size, spx, mask, bits, softw, live, invT, reduce_acc)
+        ctx.save_for_backward(zq, spx, mask, bits, softw, live, acc)
+        ctx.size, ctx.invT = size, invT
+        ctx.mark_non_differentiable(acc)
+        return loss[0], acc
+
+    @staticmethod
+    def backward(ctx, g, _g_acc):
+        zq, spx, mask, bits, softw, live, acc = ctx.saved_tensors
+        dzq = soft_ce_bwd_lowres(zq, ctx.size, spx, mask, bits, softw, live, acc, g.reshape(1).to(torch.float32).contiguous(), ctx.invT)
+        return dzq, None, None, None, None, None, None, None, None
+
+
+def soft_ce_lowres(zq, size, spx, mask, bits, softw, live, invT, reduce_acc=None):
+    """Mean over the counted pixels (selected, id in range, in a ``live`` picture) of the cross entropy of
+    ``softmax(F.interpolate(zq, size, 'bilinear', align_corners=False) * invT)`` against the soft targets of ``online_soft_weights``:
+    ``sum_c softw_c * -log(p_c + 1e-8)`` for a pixel of a multi-hot superpixel, ``-log(p_c + 1e-8)`` for a one-hot one; 0 without a
+    counted pixel.  Differentiable in ``zq``; the upsampled logits and their gradient never exist.  Returns (loss, acc)."""
+    return _SoftCELowRes.apply(zq, (int(size[0]), int(size[1])), spx.contiguous(), _mask_u8(mask), bits, softw, live, invT, reduce_acc)
+
+
+def simw_plbl_reference(size, spx, mask, targets=None, bits=None, zq_p=None, featq=None, invT=1.0, inv_tau=1.0, softw=None, live=None,
+                        zq=None, invT_ce=None, grad=None):
+    """``online_soft_weights`` and ``soft_ce_lowres`` on HOST tensors: the library's plain loop through csrc/online_plbl.h
+    (``mas_simw_plbl_reference``).  Needs no GPU.  With ``zq_p`` / ``featq`` the soft weights and the live flags are computed (entries
+    that are not defined stay NaN), otherwise they are the given ``softw`` [N,C,H,W] / ``live`` int32 [N].  Returns a dict: softw, live,
+    and with ``zq``: loss f32 [1], acc i64 [2], and with ``grad`` (f32 [1]) dzq_fix."""
+    lib = _lib.load()
+    for t in (zq_p, featq, spx, mask, zq, grad, softw, live, bits, targets):
+        if t is not None and (t.is_cuda or not t.is_contiguous()):
+            raise ValueError("simw_plbl_reference takes contiguous host tensors")
+    src = zq_p if zq_p is not None else zq
+    N, C, h, w = src.shape
+    H, W = int(size[0]), int(size[1])
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    bits = _plbl_bits_host(targets, bits)
+    S, Ch = bits.shape[1], 1
+    if zq_p is not None:
+        _plbl_shapes(zq_p, featq, size, spx, mask, bits)
+        Ch = featq.shape[1]
+        softw = torch.full((N, C, H, W), float('nan'), dtype=torch.float32)
+        live = torch.zeros(N, dtype=torch.int32)
+    acc = loss = fix = None
+    if zq is not None:
+        _soft_ce_check(zq, size, spx, mask, bits, softw, live)
+        acc, loss = torch.zeros(2, dtype=torch.int64), torch.zeros(1, dtype=torch.float32)
+        fix = torch.zeros(zq.shape, dtype=torch.int64) if grad is not None else None
+    _lib.check(lib.mas_simw_plbl_reference(_opt(zq_p), _opt(featq), Ch, h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
+                                           N, C, H, W, S, invT, inv_tau, softw.data_ptr(), live.data_ptr(), _opt(zq),
+                                           invT if invT_ce is None else invT_ce, _opt(grad), _opt(acc), _opt(loss), _opt(fix)),
+               "mas_simw_plbl_reference")
+    out = dict(softw=softw, live=live, bits=bits)
     if zq is not None:
         out.update(loss=loss, acc=acc)
         if fix is not None:

@@ -94,6 +94,9 @@ def get_parser():
     a('--dorampup', action='store_true', default=False)
     a("--th_wplbl", type=float, default=None)
     a('--weight_wo_proto', action='store_true', default=False)
+    # similarity-weighted soft targets (active_pwce_multi_predignore; refused for every other --method)
+    a("--simw_temp", type=float, default=0.1, help="temperature of the softmax over the prototype similarities")
+    a('--simw_temp_schedule', action='store_true', default=False, help="hold --simw_temp at 1000 for the first 20000 iterations")
     # active learning
     a("--seed", type=int, default=0)
     a("--start_over", action='store_true', default=False)
@@ -245,6 +248,15 @@ PARTIAL_LOSS_METHODS = ('active_joint_multi_predignore_lossdecomp', 'active_join
 # the trainers that read --lamparam / --lamscale / --dorampup / --th_wplbl / --weight_wo_proto, and those flags' defaults
 ONLINE_PLBL_METHODS = ('active_onlineplbl_multi_predignore', 'active_onlinewplbl_multi_predignore', 'active_onlinewplblonly_multi_predignore')
 ONLINE_PLBL_DEFAULTS = dict(lamparam=0.1, lamscale=1.0, dorampup=False, th_wplbl=None, weight_wo_proto=False)
+# the similarity-weighted trainers: the first reads the online flags except --weight_wo_proto, the second --simw_temp / --simw_temp_schedule only
+SIMW_PLBL_METHODS = ('active_onlinesimwplbl_multi_predignore', 'active_pwce_multi_predignore')
+SIMW_DEFAULTS = dict(simw_temp=0.1, simw_temp_schedule=False)
+
+
+def _refuse_changed(args, defaults, honoured_by):
+    changed = [k for k, v in defaults.items() if getattr(args, k, v) != v]
+    if changed:
+        raise NotImplementedError("--%s is honoured by --method %s only (got %s)" % (' / --'.join(changed), ' / '.join(honoured_by), args.method))
 
 
 def arg_assert(args):
@@ -268,11 +280,13 @@ def arg_assert(args):
     if getattr(args, 'partial_loss', 'choice') != 'choice' and args.method not in PARTIAL_LOSS_METHODS:
         raise NotImplementedError("--partial_loss %s is honoured by --method %s only (got %s)"
                                   % (args.partial_loss, ' / '.join(PARTIAL_LOSS_METHODS), args.method))
-    if args.method not in ONLINE_PLBL_METHODS:
-        changed = [k for k, v in ONLINE_PLBL_DEFAULTS.items() if getattr(args, k, v) != v]
-        if changed:
-            raise NotImplementedError("--%s is honoured by --method %s only (got %s)"
-                                      % (' / --'.join(changed), ' / '.join(ONLINE_PLBL_METHODS), args.method))
+    online = ONLINE_PLBL_METHODS + SIMW_PLBL_METHODS[:1]
+    if args.method == SIMW_PLBL_METHODS[0]:         # LocalsimWProtoCE.generate_plbl never reads --weight_wo_proto
+        _refuse_changed(args, dict(weight_wo_proto=False), ONLINE_PLBL_METHODS[1:2])
+    elif args.method not in ONLINE_PLBL_METHODS:
+        _refuse_changed(args, ONLINE_PLBL_DEFAULTS, online)
+    if args.method != SIMW_PLBL_METHODS[1]:
+        _refuse_changed(args, SIMW_DEFAULTS, SIMW_PLBL_METHODS[1:])
     from ..ops import stage2_threshold_method       # NotImplementedError here; the reference raises it at the first picture
     stage2_threshold_method(getattr(args, 'cosprop_threshold_method', 'median'))            # (trainer/eval_save_cosplbl_prop.py:253)
 

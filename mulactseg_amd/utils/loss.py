@@ -30,6 +30,10 @@ class here                     reference definition
                                network's confidence in the label, or gated by ``--th_wplbl``; mean over non-zero terms)
 ``JointLocalProtoCE``          ``trainer/active_onlinewplblonly_multi_predignore.py:15-137`` (weighted; the mean of an
                                empty set is NaN, as the reference's)
+``LocalsimWProtoCE``           ``trainer/active_onlinesimwplbl_multi_predignore.py:15-148`` (the CE weighted by the pixel's
+                               inner product with its nearest prototype, negative ones included, or gated by ``--th_wplbl``)
+``JointLocalProtoWeightingCE`` ``trainer/active_pwce_multi_predignore.py:17-155`` (no hard label: CE against the softmax of
+                               the prototype similarities over the candidate classes; one-hot superpixels keep plain CE)
 =============================  =================================================================
 
 Inputs must be ROCm tensors; there is no CPU path (``_lib.MulActSegHipError`` otherwise).
@@ -371,6 +375,7 @@ class LocalProtoCE(nn.Module):
     _mode = _lib.LCE_UNWEIGHTED
     _empty_nan = False
     _honours_weight_wo_proto = False
+    _weight_sim = False             # the weight map holds prototype similarities, which may be negative (LocalsimWProtoCE)
 
     def __init__(self, args, num_superpixel, temperature=1.0, reduction='mean'):
         super().__init__()
@@ -395,7 +400,8 @@ class LocalProtoCE(nn.Module):
         with torch.no_grad():
             labels, weight = ops.online_pseudo_labels(inputs_plbl.detach().contiguous(), feats_plbl.detach().contiguous(), size,
                                                       superpixels.contiguous(), spmasks.contiguous(), targets=targets,
-                                                      invT=ops.inv_temperature(self.temp), weight_wo_proto=wo_proto)
+                                                      invT=ops.inv_temperature(self.temp), weight_wo_proto=wo_proto,
+                                                      weight_sim=self._weight_sim)
         return weight, labels
 
     def _mode_th(self):
@@ -405,7 +411,8 @@ class LocalProtoCE(nn.Module):
         mode, th = self._mode_th()
         loss, self.last_acc = ops.label_ce_lowres(inputs, size, labels, None if mode == _lib.LCE_UNWEIGHTED else weight,
                                                   ops.inv_temperature(self.temp), mode=mode, th=th, empty_nan=self._empty_nan,
-                                                  reduce_acc=_all_reduce_sum if self.sync_normalisers else None)
+                                                  reduce_acc=_all_reduce_sum if self.sync_normalisers else None,
+                                                  signed=self._weight_sim and mode == _lib.LCE_WEIGHTED)
         return loss
 
     def forward(self, inputs_plbl, feats_plbl, inputs, targets, superpixels, spmasks):
@@ -438,3 +445,66 @@ class JointLocalProtoCE(LocalProtoCE):
     tensor), which the trainer's ``update`` raises on."""
     _mode = _lib.LCE_WEIGHTED
     _empty_nan = True
+
+
+class LocalsimWProtoCE(LocalWProtoCE):
+    """``LocalProtoCE`` with every pixel's CE weighted by its inner product with the nearest prototype -- the similarity that chose the
+    label, not the network's confidence -- or, with ``args.th_wplbl``, kept only where that similarity exceeds the threshold; the mean
+    runs over the non-zero terms, 0 when there is none -- reference ``trainer/active_onlinesimwplbl_multi_predignore.py:15-148``.  A
+    similarity can be negative, and the reference's ``weight * CE`` is then negative too: the sum is signed.  ``args.weight_wo_proto``
+    is not read (the reference's ``generate_plbl`` never does)."""
+    _honours_weight_wo_proto = False
+    _weight_sim = True
+
+
+class JointLocalProtoWeightingCE(nn.Module):
+    """Prototype-similarity soft targets instead of hard pseudo labels -- reference ``trainer/active_pwce_multi_predignore.py:17-155``.
+    Every selected pixel of a multi-hot superpixel gets a target over its candidate classes: the softmax, at temperature
+    ``args.simw_temp`` (read at call time, or the ``simw_temp`` argument), of its inner products with the classes' local prototypes.
+    The loss is the mean over the selected pixels of ``sum_c w_c * -log(p_c + 1e-8)``; pixels of one-hot superpixels keep plain CE.
+
+    Replicated from the reference as it runs: both softmaxes -- the prototype pick and the training logits -- use ``args.ce_temp``; the
+    ``temperature`` the class is constructed with (the trainer passes ``group_ce_temp``) is stored and ignored.  A picture without a
+    selected multi-hot pixel is skipped whole, its selected one-hot pixels entering neither the sum nor the count.  An empty batch
+    gives 0.  One difference: a selected pixel whose superpixel id lies outside ``[0, nseg)`` makes the reference raise; here it is
+    not counted.
+
+    ``forward`` / ``forward_lowres`` as ``LocalProtoCE``'s."""
+
+    def __init__(self, args, num_superpixel, temperature=1.0, reduction='mean'):
+        super().__init__()
+        if reduction != 'mean':
+            raise NotImplementedError("only reduction='mean' exists (the reference asserts it)")
+        self.args = args
+        self.num_superpixel = num_superpixel
+        self.ce_temp = args.ce_temp
+        self.temp = temperature
+        self.reduction = reduction
+        self.eps = 1e-8
+        self.sync_normalisers = True
+
+    def soft_weights(self, inputs_plbl, feats_plbl, targets, superpixels, spmasks, size=None, simw_temp=None):
+        """(softw f32 [N,C,H,W], defined on the candidate planes of the valid pixels; live int32 [N]; bits int32 [N,S])"""
+        if targets.shape[1] != self.num_superpixel:
+            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        if size is None:
+            size = superpixels.shape[-2:]
+        tau = self.args.simw_temp if simw_temp is None else simw_temp
+        with torch.no_grad():
+            return ops.online_soft_weights(inputs_plbl.detach().contiguous(), feats_plbl.detach().contiguous(), size,
+                                           superpixels.contiguous(), spmasks.contiguous(), targets=targets,
+                                           invT=ops.inv_temperature(self.ce_temp), inv_tau=ops.inv_temperature(tau))
+
+    def _loss(self, inputs, size, superpixels, spmasks, softw, live, bits):
+        loss, self.last_acc = ops.soft_ce_lowres(inputs, size, superpixels, spmasks, bits, softw, live, ops.inv_temperature(self.ce_temp),
+                                                 reduce_acc=_all_reduce_sum if self.sync_normalisers else None)
+        return loss
+
+    def forward(self, inputs_plbl, feats_plbl, inputs, targets, superpixels, spmasks, simw_temp=None):
+        softw, live, bits = self.soft_weights(inputs_plbl, feats_plbl, targets, superpixels, spmasks, simw_temp=simw_temp)
+        return self._loss(inputs, inputs.shape[-2:], superpixels, spmasks, softw, live, bits)
+
+    def forward_lowres(self, zq_p, featq, zq, size, targets, superpixels, spmasks, simw_temp=None):
+        size = (int(size[0]), int(size[1]))
+        softw, live, bits = self.soft_weights(zq_p, featq, targets, superpixels, spmasks, size=size, simw_temp=simw_temp)
+        return self._loss(zq, size, superpixels, spmasks, softw, live, bits)
