@@ -1,29 +1,34 @@
 // online_plbl.hip -- online local-prototype pseudo labels and the cross entropy on them, for gfx950.
 //
 // Reference: trainer/active_onlineplbl_multi_predignore.py:25-141 (LocalProtoCE), active_onlinewplbl_multi_predignore.py:20-148
-// (LocalWProtoCE), active_onlinewplblonly_multi_predignore.py:20-137 (JointLocalProtoCE): a Python loop over the pictures with
-// nonzero() / scatter_max / unique per picture on feat_forward's full-resolution [N,256,H,W] features.  Here, per batch:
-//   mas_online_plbl_labels   memset of the work buffer -> the group scan of losses.hip (MAS_LOSS_GROUP | MAS_LOSS_GROUP_ONLY_MULTI,
-//                            quarter-resolution form), which leaves the arg-pixel of every (superpixel, candidate class) ->
-//                            k_online_assign: one lane per pixel; a valid pixel interpolates its own feature and the features of its
-//                            superpixel's prototype pixels channel by channel from the quarter-resolution map (four candidates per sweep
-//                            over the channels) and keeps the nearest; label u8 and weight f32 are written for every pixel.  Prototype
-//                            features are re-interpolated per use: nothing is staged, so nothing is sized by a device-side count.
-//   k_label_ce_fwd / _bwd    the labelled pixels of a 4 x 256 tile are compacted into an LDS queue and processed one per lane (the
-//                            scheme of k_partial_loss_fwd / _bwd); sums are integers (u64 fixed point), the gradient of zq is added
-//                            through the four taps into an LDS image of the tile's quarter-resolution footprint and from there into
-//                            the int64 accumulator -- no float atomics, run-to-run identical bytes.
-//   mas_online_plbl_reference   the same through online_plbl.h on host pointers.
-//
-// The similarity-weighted siblings: trainer/active_onlinesimwplbl_multi_predignore.py:15-148 (LocalsimWProtoCE: the same labels, the
-// weight is the inner product with the chosen prototype -- MAS_OPL_WEIGHT_SIM in k_online_assign, a signed sum with MAS_LCE_SIGNED in
-// k_label_ce_fwd) and trainer/active_pwce_multi_predignore.py:17-155 (JointLocalProtoWeightingCE: no hard label):
-//   mas_online_soft_weights  memsets -> the same group scan -> k_online_soft: one lane per pixel with the sweep of k_online_assign;
-//                            every candidate's raw similarity goes to its plane of softw [N,C,H,W], the pixel's own entries are
-//                            normalised in place, the picture is marked live.
-//   k_soft_ce_fwd / _bwd     the tile queue of k_label_ce_fwd / _bwd holding the counted pixels (mask set, id in range, live picture);
-//                            cross entropy against the soft target, the same LDS image and int64 gradient.
-//   mas_simw_plbl_reference  the same on host pointers.
+// (LocalWProtoCE), active_onlinewplblonly_multi_predignore.py:20-137 (JointLocalProtoCE), and the similarity-weighted siblings
+// active_onlinesimwplbl_multi_predignore.py:15-148 (LocalsimWProtoCE) and active_pwce_multi_predignore.py:17-155
+// (JointLocalProtoWeightingCE, no hard label): a Python loop over the pictures with nonzero() / scatter_max / unique per picture on
+// feat_forward's full-resolution [N,256,H,W] features.  Here every piece exists once and the two families are its two users:
+//   scan_prototypes     the prologue of mas_online_plbl_labels and mas_online_soft_weights: checks, memset of the work buffer, the
+//                       group scan of losses.hip (MAS_LOSS_GROUP | MAS_LOSS_GROUP_ONLY_MULTI, quarter-resolution form), which leaves the
+//                       arg-pixel of every (superpixel, candidate class).
+//   sweep_candidates    one lane per pixel: a valid pixel interpolates its own feature and the features of its superpixel's prototype
+//                       pixels channel by channel from the quarter-resolution map (kSweep candidates per sweep over the channels) and
+//                       hands every (class, similarity, is_prototype) to its caller.  Prototype features are re-interpolated per use:
+//                       nothing is staged, so nothing is sized by a device-side count.
+//                         k_online_assign  keeps the nearest; label u8 and weight f32 (the label's probability, 1 on a prototype with
+//                                          MAS_OPL_WEIGHT_WO_PROTO, the similarity itself with MAS_OPL_WEIGHT_SIM) for every pixel.
+//                         k_online_soft    stores every similarity to its plane of softw [N,C,H,W], normalises the pixel's own
+//                                          entries in place and marks the picture live.
+//   ce_fwd / ce_bwd     the tile-queue core: the selected pixels of a 4 x 256 tile are compacted into an LDS queue and processed one
+//                       per lane (the scheme of k_partial_loss_fwd / _bwd); sums are integers (u64 fixed point), the gradient of zq is
+//                       added through the four taps into QuarterImage, an LDS image of the tile's quarter-resolution footprint, and from
+//                       there into the int64 accumulator -- no float atomics, run-to-run identical bytes.  A policy says which pictures
+//                       and pixels take part and what a queued pixel yields:
+//                         LabelCe  (k_label_ce_fwd / _bwd)  the labelled pixels; the mode's weight, MAS_LCE_SIGNED sums.
+//                         SoftCe   (k_soft_ce_fwd / _bwd)   the counted pixels (mask set, id in range) of the live pictures; cross
+//                                                           entropy against the soft target.
+//   host_ce             the same two passes on host pointers through online_plbl.h, with host policies of its own:
+//                       mas_online_plbl_reference and mas_simw_plbl_reference, the statement the kernels are tested against.
+// losses.hip keeps a twin of queue_push, the tile compaction and the LDS image (another tap struct, the benchmarked training step).
+#include <type_traits>
+
 #include "common.h"
 #include "online_plbl.h"
 
@@ -38,6 +43,50 @@ struct Geo { int C, Ch, h, w, H, W, S; float sh, sw; };
 
 inline Geo make_geo(int C, int Ch, int h, int w, int H, int W, int S) {
     return Geo{C, Ch, h, w, H, W, S, (float)h / (float)H, (float)w / (float)W};
+}
+
+// ---- the per-pixel kernels -----------------------------------------------------------------------------------------------------------
+// The candidates Yc of a pixel with tap t, kSweep per pass over the channels of fb: the prototype pixel of each is decoded from its
+// word of gm, the similarity is the chain of online_plbl.h (sim), and emit(class, similarity, is_prototype) sees them class-ascending.
+template <typename Emit>
+__device__ __forceinline__ void sweep_candidates(const float* __restrict__ fb, const mas_u64* __restrict__ gm, unsigned Yc, const OplTap& t,
+                                                 int pix, const Geo& g, Emit emit) {
+    const int HW = g.H * g.W;
+    const size_t hw = (size_t)g.h * g.w;
+    while (Yc) {
+        int cls[kSweep];
+        OplTap tp[kSweep];
+        float acc[kSweep];
+        bool proto[kSweep];
+#pragma unroll
+        for (int u = 0; u < kSweep; ++u) {
+            cls[u] = -1;
+            tp[u] = t;
+            acc[u] = 0.0f;
+            proto[u] = false;
+            if (Yc) {
+                const int c = __ffs(Yc) - 1;
+                Yc &= Yc - 1u;
+                const mas_u64 w64 = gm[c];
+                const unsigned pp = mas_opl_word_pixel(w64);
+                if ((unsigned)(w64 >> 32) != 0u && pp < (unsigned)HW) {     // (always, for a valid pixel: it is in the scan itself)
+                    cls[u] = c;
+                    tp[u] = mas_opl_tap(g.sh, g.sw, (int)pp / g.W, (int)pp % g.W, g.h, g.w);
+                    proto[u] = pp == (unsigned)pix;
+                }
+            }
+        }
+        for (int k = 0; k < g.Ch; ++k) {
+            const float* fk = fb + (size_t)k * hw;
+            const float fx = mas_opl_at(fk, t);
+#pragma unroll
+            for (int u = 0; u < kSweep; ++u)
+                if (cls[u] >= 0) acc[u] = mas_fmaf(mas_opl_at(fk, tp[u]), fx, acc[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < kSweep; ++u)
+            if (cls[u] >= 0) emit(cls[u], acc[u], proto[u]);
+    }
 }
 
 template <int CT, bool EXACT, typename IdT>
@@ -61,48 +110,17 @@ __global__ __launch_bounds__(kThreads) void k_online_assign(const float* __restr
             const unsigned Y = bits[(size_t)n * g.S + id];
             if (__popc(Y) > 1) {
                 const OplTap t = mas_opl_tap(g.sh, g.sw, pix / g.W, pix % g.W, g.h, g.w);
-                const mas_u64* gm = gmax + ((size_t)n * g.S + id) * C;
-                const float* fb = featq + (size_t)n * g.Ch * hw;
-                unsigned Yc = C < 32 ? (Y & ((1u << C) - 1u)) : Y;
                 float best = 0.0f;
                 int arg = -1;
                 bool is_proto = false;
-                while (Yc) {
-                    int cls[kSweep];
-                    OplTap tp[kSweep];
-                    float acc[kSweep];
-#pragma unroll
-                    for (int u = 0; u < kSweep; ++u) {
-                        cls[u] = -1;
-                        tp[u] = t;
-                        acc[u] = 0.0f;
-                        if (Yc) {
-                            const int c = __ffs(Yc) - 1;
-                            Yc &= Yc - 1u;
-                            const mas_u64 w64 = gm[c];
-                            const unsigned pp = mas_opl_word_pixel(w64);
-                            if ((unsigned)(w64 >> 32) != 0u && pp < (unsigned)HW) {     // (always, for a valid pixel: it is in the scan itself)
-                                cls[u] = c;
-                                tp[u] = mas_opl_tap(g.sh, g.sw, (int)pp / g.W, (int)pp % g.W, g.h, g.w);
-                                is_proto = is_proto || pp == (unsigned)pix;
-                            }
-                        }
-                    }
-                    for (int k = 0; k < g.Ch; ++k) {
-                        const float* fk = fb + (size_t)k * hw;
-                        const float fx = mas_opl_at(fk, t);
-#pragma unroll
-                        for (int u = 0; u < kSweep; ++u)
-                            if (cls[u] >= 0) acc[u] = mas_fmaf(mas_opl_at(fk, tp[u]), fx, acc[u]);
-                    }
-#pragma unroll
-                    for (int u = 0; u < kSweep; ++u) {
-                        if (cls[u] >= 0 && (arg < 0 || acc[u] > best)) {
-                            best = acc[u];
-                            arg = cls[u];
-                        }
-                    }
-                }
+                sweep_candidates(featq + (size_t)n * g.Ch * hw, gmax + ((size_t)n * g.S + id) * C, C < 32 ? (Y & ((1u << C) - 1u)) : Y, t,
+                                 pix, g, [&](int c, float sim, bool proto) {
+                                     is_proto = is_proto || proto;
+                                     if (arg < 0 || sim > best) {
+                                         best = sim;
+                                         arg = c;
+                                     }
+                                 });
                 if (arg >= 0) {
                     label = arg;
                     if (flags & MAS_OPL_WEIGHT_SIM) {                            // (uniform) the similarity itself, sign and all
@@ -122,186 +140,7 @@ __global__ __launch_bounds__(kThreads) void k_online_assign(const float* __restr
     weight[i] = wgt;
 }
 
-// ---- cross entropy on a label map ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void queue_push(bool sel, unsigned short off, unsigned short* queue, int* qcount) {
-    const unsigned long long bal = __ballot(sel);
-    if (bal == 0) return;
-    const int lane = threadIdx.x & (MAS_WAVE - 1);
-    int base = 0;
-    if (lane == 0) base = atomicAdd(qcount, (int)__popcll(bal));
-    base = __shfl(base, 0, MAS_WAVE);
-    if (sel) queue[base + (int)__popcll(bal & ((1ull << lane) - 1ull))] = off;
-}
-
-// the labelled pixels of the tile (one row per wave) into the queue as (row << 8 | column)
-__device__ __forceinline__ void tile_compact(const unsigned char* __restrict__ lb, int C, int H, int W, int tx, int ty,
-                                             unsigned short* queue, int* qcount) {
-    const int lane = threadIdx.x & (MAS_WAVE - 1);
-    const int ry = threadIdx.x / MAS_WAVE;
-    const int y = ty * kTileH + ry;
-    if (y >= H) return;                       // (wave-uniform)
-    const size_t row = (size_t)y * W;
-#pragma unroll
-    for (int k = 0; k < kTileW / MAS_WAVE; ++k) {
-        const int rx = k * MAS_WAVE + lane;
-        const int x = tx * kTileW + rx;
-        const bool sel = (x < W) && ((int)lb[row + (x < W ? x : 0)] < C);
-        queue_push(sel, (unsigned short)((ry << 8) | rx), queue, qcount);
-    }
-}
-
-struct CeArgs {
-    const float* zq; const unsigned char* labels; const float* weight;
-    Geo g; float invT; int mode; float th; int tiles_x, tiles_y; int sgn;
-};
-
-// probabilities of the queued pixel, its label and the weight its mode gives it
-template <int CT, bool EXACT>
-__device__ __forceinline__ void ce_pixel(const CeArgs& a, int n, int py, int px, float (&v)[CT], OplTap& t, int& lab, float& wgt) {
-    const int C = EXACT ? CT : a.g.C;
-    const size_t hw = (size_t)a.g.h * a.g.w;
-    const size_t pix = (size_t)n * a.g.H * a.g.W + (size_t)py * a.g.W + px;
-    lab = a.labels[pix];
-    t = mas_opl_tap(a.g.sh, a.g.sw, py, px, a.g.h, a.g.w);
-    mas_opl_logits<CT>(a.zq + (size_t)n * C * hw, hw, t, C, v);
-    mas_opl_softmax<CT>(v, C, a.invT);
-    wgt = mas_opl_mode_weight(a.mode, a.mode == MAS_LCE_UNWEIGHTED ? 1.0f : a.weight[pix], a.th);
-}
-
-template <int CT, bool EXACT>
-__global__ __launch_bounds__(kThreads) void k_label_ce_fwd(const CeArgs a, mas_u64* __restrict__ acc) {
-    __shared__ int qcount[2];
-    __shared__ unsigned short queue[kTilePx];
-    __shared__ mas_u64 s_red[kThreads / MAS_WAVE][2];
-    const int C = EXACT ? CT : a.g.C;
-    if (threadIdx.x == 0) qcount[0] = 0;
-    __syncthreads();
-    int bid = blockIdx.x;
-    const int tx = bid % a.tiles_x; bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int n = bid / a.tiles_y;
-    tile_compact(a.labels + (size_t)n * a.g.H * a.g.W, C, a.g.H, a.g.W, tx, ty, queue, qcount);
-    __syncthreads();
-    const int nq = qcount[0];
-    if (nq == 0) return;                      // (uniform)
-    mas_u64 sum = 0, cnt = 0;
-    for (int i = threadIdx.x; i < nq; i += kThreads) {
-        const unsigned off = queue[i];
-        float v[CT];
-        OplTap t;
-        int lab;
-        float wgt;
-        ce_pixel<CT, EXACT>(a, n, ty * kTileH + (int)(off >> 8), tx * kTileW + (int)(off & 255u), v, t, lab, wgt);
-        int counted;
-        const float term = mas_opl_term(a.mode, wgt, mas_opl_ce(mas_opl_pick<CT>(v, C, lab)), &counted);
-        if (counted) {
-            sum += mas_opl_fix_term(term, a.sgn);
-            cnt += 1;
-        }
-    }
-    const int lane = threadIdx.x & (MAS_WAVE - 1), wave = threadIdx.x / MAS_WAVE;
-#pragma unroll
-    for (int off = MAS_WAVE / 2; off > 0; off >>= 1) {
-        sum += __shfl_down(sum, off, MAS_WAVE);
-        cnt += __shfl_down(cnt, off, MAS_WAVE);
-    }
-    if (lane == 0) { s_red[wave][0] = sum; s_red[wave][1] = cnt; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        mas_u64 r = 0;
-        for (int wv = 0; wv < kThreads / MAS_WAVE; ++wv) r += s_red[wv][threadIdx.x];
-        if (r) atomicAdd(&acc[threadIdx.x], r);
-    }
-}
-
-__global__ void k_label_ce_value(const mas_u64* __restrict__ acc, int flags, float* __restrict__ loss) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    loss[0] = mas_opl_value(acc[0], acc[1], flags);
-}
-
-// The quarter-resolution footprint of a 4 x 256 tile (<= 4 rows x 72 columns per class for the x4 ratio of the model) is summed in LDS
-// first; only its non-zero entries go to memory.  Taps outside that image (other ratios) go to memory directly.
-template <int CT, bool EXACT>
-__global__ __launch_bounds__(kThreads) void k_label_ce_bwd(const CeArgs a, const mas_u64* __restrict__ acc, const float* __restrict__ grad,
-                                                            mas_u64* __restrict__ dq) {
-    constexpr int kLR = 4, kLC = 72;
-    __shared__ int qcount[2];
-    __shared__ unsigned short queue[kTilePx];
-    __shared__ mas_u64 s_acc[EXACT ? CT * kLR * kLC : 1];
-    const int C = EXACT ? CT : a.g.C;
-    if (threadIdx.x == 0) qcount[0] = 0;
-    __syncthreads();
-    int bid = blockIdx.x;
-    const int tx = bid % a.tiles_x; bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int n = bid / a.tiles_y;
-    tile_compact(a.labels + (size_t)n * a.g.H * a.g.W, C, a.g.H, a.g.W, tx, ty, queue, qcount);
-    __syncthreads();
-    const int nq = qcount[0];
-    if (nq == 0) return;                      // (uniform)
-    const int hw = a.g.h * a.g.w;
-    mas_u64* qb = dq + (size_t)n * C * hw;
-    const int ry0 = make_tap(a.g.sh, ty * kTileH, a.g.h).i0;
-    const int rx0 = make_tap(a.g.sw, tx * kTileW, a.g.w).i0;
-    if (EXACT) {
-        for (int i = threadIdx.x; i < CT * kLR * kLC; i += kThreads) s_acc[i] = 0;
-        __syncthreads();
-    }
-    // r, x: the tap's place in the LDS image, or r < 0 when it lies outside (then the add goes to memory)
-    auto place = [&](int o, int& r, int& x) {
-        r = o / a.g.w - ry0;
-        x = o % a.g.w - rx0;
-        if (!EXACT || r >= kLR || x >= kLC) r = -1;
-    };
-    auto add_q = [&](int c, int o, int r, int x, long long val) {
-        if (EXACT && r >= 0) atomicAdd(&s_acc[(c * kLR + r) * kLC + x], (mas_u64)val);
-        else atomicAdd(qb + (size_t)c * hw + o, (mas_u64)val);
-    };
-    const float scale = (grad[0] / (float)acc[1]) * a.invT;
-    for (int i = threadIdx.x; i < nq; i += kThreads) {
-        const unsigned off = queue[i];
-        float v[CT];
-        OplTap t;
-        int lab;
-        float wgt;
-        ce_pixel<CT, EXACT>(a, n, ty * kTileH + (int)(off >> 8), tx * kTileW + (int)(off & 255u), v, t, lab, wgt);
-        int counted;
-        (void)mas_opl_term(a.mode, wgt, mas_opl_ce(mas_opl_pick<CT>(v, C, lab)), &counted);
-        if (!counted) continue;
-        const float k = scale * wgt;
-        const float w00 = t.l0h * t.l0w, w01 = t.l0h * t.l1w, w10 = t.l1h * t.l0w, w11 = t.l1h * t.l1w;
-        int r00, x00, r01, x01, r10, x10, r11, x11;
-        place(t.o00, r00, x00);
-        place(t.o01, r01, x01);
-        place(t.o10, r10, x10);
-        place(t.o11, r11, x11);
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            if (EXACT || c < C) {
-                const float d = k * (v[c] - ((c == lab) ? 1.0f : 0.0f));
-                add_q(c, t.o00, r00, x00, mas_opl_grad_fix(d * w00));
-                add_q(c, t.o01, r01, x01, mas_opl_grad_fix(d * w01));
-                add_q(c, t.o10, r10, x10, mas_opl_grad_fix(d * w10));
-                add_q(c, t.o11, r11, x11, mas_opl_grad_fix(d * w11));
-            }
-        }
-    }
-    if (EXACT) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < CT * kLR * kLC; i += kThreads) {
-            const mas_u64 val = s_acc[i];
-            if (val) {
-                const int c = i / (kLR * kLC), rem = i - c * (kLR * kLC);
-                const int r = rem / kLC, x = rem - r * kLC;
-                atomicAdd(qb + (size_t)c * hw + (size_t)(ry0 + r) * a.g.w + (rx0 + x), val);
-            }
-        }
-    }
-}
-
-// ---- soft targets from the prototype similarities, and the cross entropy against them ------------------------------------------------
-// One lane per pixel, the sweep of k_online_assign: every candidate's raw similarity goes to its plane of softw [N,C,H,W], then the
-// pixel's own entries are normalised in place (mas_opl_soft_normalise).  Only the candidate planes of valid pixels are written.
+// Only the candidate planes of valid pixels are written.
 template <typename IdT>
 __global__ __launch_bounds__(kThreads) void k_online_soft(const float* __restrict__ featq, const IdT* __restrict__ spx,
                                                            const unsigned char* __restrict__ mask, const unsigned* __restrict__ bits,
@@ -320,52 +159,93 @@ __global__ __launch_bounds__(kThreads) void k_online_soft(const float* __restric
     live[n] = 1;
     const size_t hw = (size_t)g.h * g.w;
     const OplTap t = mas_opl_tap(g.sh, g.sw, pix / g.W, pix % g.W, g.h, g.w);
-    const mas_u64* gm = gmax + ((size_t)n * g.S + id) * g.C;
-    const float* fb = featq + (size_t)n * g.Ch * hw;
     float* sw = softw + (size_t)n * g.C * HW + pix;
-    unsigned Yc = g.C < 32 ? (Y & ((1u << g.C) - 1u)) : Y;
     unsigned done = 0;
-    while (Yc) {
-        int cls[kSweep];
-        OplTap tp[kSweep];
-        float acc[kSweep];
-#pragma unroll
-        for (int u = 0; u < kSweep; ++u) {
-            cls[u] = -1;
-            tp[u] = t;
-            acc[u] = 0.0f;
-            if (Yc) {
-                const int c = __ffs(Yc) - 1;
-                Yc &= Yc - 1u;
-                const mas_u64 w64 = gm[c];
-                const unsigned pp = mas_opl_word_pixel(w64);
-                if ((unsigned)(w64 >> 32) != 0u && pp < (unsigned)HW) {     // (always, for a valid pixel: it is in the scan itself)
-                    cls[u] = c;
-                    tp[u] = mas_opl_tap(g.sh, g.sw, (int)pp / g.W, (int)pp % g.W, g.h, g.w);
-                }
-            }
-        }
-        for (int k = 0; k < g.Ch; ++k) {
-            const float* fk = fb + (size_t)k * hw;
-            const float fx = mas_opl_at(fk, t);
-#pragma unroll
-            for (int u = 0; u < kSweep; ++u)
-                if (cls[u] >= 0) acc[u] = mas_fmaf(mas_opl_at(fk, tp[u]), fx, acc[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < kSweep; ++u) {
-            if (cls[u] >= 0) {
-                sw[(size_t)cls[u] * HW] = acc[u];
-                done |= 1u << cls[u];
-            }
-        }
-    }
+    sweep_candidates(featq + (size_t)n * g.Ch * hw, gmax + ((size_t)n * g.S + id) * g.C, g.C < 32 ? (Y & ((1u << g.C) - 1u)) : Y, t, pix, g,
+                     [&](int c, float sim, bool) {
+                         sw[(size_t)c * HW] = sim;
+                         done |= 1u << c;
+                     });
     mas_opl_soft_normalise(sw, (size_t)HW, done, invtau);
 }
 
-struct SoftArgs {
-    const float* zq; const void* spx; const unsigned char* mask; const unsigned* bits; const float* softw; const int* live;
-    Geo g; float invT; int spx_dtype; int tiles_x, tiles_y;
+// ---- the tile-queue cross entropy ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void queue_push(bool sel, unsigned short off, unsigned short* queue, int* qcount) {
+    const unsigned long long bal = __ballot(sel);
+    if (bal == 0) return;
+    const int lane = threadIdx.x & (MAS_WAVE - 1);
+    int base = 0;
+    if (lane == 0) base = atomicAdd(qcount, (int)__popcll(bal));
+    base = __shfl(base, 0, MAS_WAVE);
+    if (sel) queue[base + (int)__popcll(bal & ((1ull << lane) - 1ull))] = off;
+}
+
+// The workgroup's tile (n, ty, tx) and, in the queue as (row << 8 | column), the pixels of it that the policy selects (one row per
+// wave).  Returns their number (uniform); 0 also for a picture the policy leaves out.
+template <typename P>
+__device__ __forceinline__ int tile_queue(const P& a, int C, unsigned short* queue, int* qcount, int& n, int& ty, int& tx) {
+    int bid = blockIdx.x;
+    tx = bid % a.tiles_x; bid /= a.tiles_x;
+    ty = bid % a.tiles_y;
+    n = bid / a.tiles_y;
+    if (!a.runs(n)) return 0;                 // (uniform)
+    if (threadIdx.x == 0) qcount[0] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & (MAS_WAVE - 1);
+    const int ry = threadIdx.x / MAS_WAVE;
+    const int y = ty * kTileH + ry;
+    if (y < a.g.H) {                          // (wave-uniform)
+        const size_t row = ((size_t)n * a.g.H + y) * a.g.W;
+#pragma unroll
+        for (int k = 0; k < kTileW / MAS_WAVE; ++k) {
+            const int rx = k * MAS_WAVE + lane;
+            const int x = tx * kTileW + rx;
+            const bool sel = (x < a.g.W) && a.selects(row + (x < a.g.W ? x : 0), C);
+            queue_push(sel, (unsigned short)((ry << 8) | rx), queue, qcount);
+        }
+    }
+    __syncthreads();
+    return qcount[0];
+}
+
+// probabilities of pixel (py, px) of picture n and its tap
+template <int CT, bool EXACT>
+__device__ __forceinline__ void ce_probs(const float* __restrict__ zq, const Geo& g, float invT, int n, int py, int px, float (&v)[CT],
+                                         OplTap& t) {
+    const int C = EXACT ? CT : g.C;
+    const size_t hw = (size_t)g.h * g.w;
+    t = mas_opl_tap(g.sh, g.sw, py, px, g.h, g.w);
+    mas_opl_logits<CT>(zq + (size_t)n * C * hw, hw, t, C, v);
+    mas_opl_softmax<CT>(v, C, invT);
+}
+
+// A policy of the core is the kernel's argument struct (zq, g, invT, tiles_x, tiles_y and its own) with
+//   runs(n)                   whether picture n takes part at all;
+//   selects(i, C)             whether pixel i of [N,H,W] goes into the queue;
+//   pixel(n, py, px, v, t, s, term)   probabilities v and tap t of a queued pixel, the policy's state s and the pixel's term;
+//                             returns whether it is counted;
+//   fix(term)                 what a counted term adds to the u64 sum;
+//   k(s, scale), dir(s, c, p_c)   the gradient of class c is k * dir.
+struct LabelCe {
+    const float* zq; const unsigned char* labels; const float* weight;
+    Geo g; float invT; int mode; float th; int tiles_x, tiles_y; int sgn;
+    struct Px { int lab; float wgt; };
+
+    __device__ __forceinline__ bool runs(int) const { return true; }
+    __device__ __forceinline__ bool selects(size_t i, int C) const { return (int)labels[i] < C; }
+    template <int CT, bool EXACT>
+    __device__ __forceinline__ bool pixel(int n, int py, int px, float (&v)[CT], OplTap& t, Px& s, float& term) const {
+        const size_t i = ((size_t)n * g.H + py) * g.W + px;
+        s.lab = labels[i];
+        ce_probs<CT, EXACT>(zq, g, invT, n, py, px, v, t);
+        s.wgt = mas_opl_mode_weight(mode, mode == MAS_LCE_UNWEIGHTED ? 1.0f : weight[i], th);
+        int counted;
+        term = mas_opl_term(mode, s.wgt, mas_opl_ce(mas_opl_pick<CT>(v, EXACT ? CT : g.C, s.lab)), &counted);
+        return counted != 0;
+    }
+    __device__ __forceinline__ mas_u64 fix(float term) const { return mas_opl_fix_term(term, sgn); }
+    __device__ __forceinline__ float k(const Px& s, float scale) const { return scale * s.wgt; }
+    __device__ __forceinline__ float dir(const Px& s, int c, float pc) const { return pc - ((c == s.lab) ? 1.0f : 0.0f); }
 };
 
 __device__ __forceinline__ int load_id_any(const void* spx, int dtype, size_t i) {          // (dtype is uniform)
@@ -374,71 +254,56 @@ __device__ __forceinline__ int load_id_any(const void* spx, int dtype, size_t i)
     return (int)static_cast<const unsigned short*>(spx)[i];
 }
 
-// the counted pixels of the tile (mask set, id in range; the caller has seen that the picture is live) into the queue
-__device__ __forceinline__ void tile_compact_soft(const SoftArgs& a, int n, int tx, int ty, unsigned short* queue, int* qcount) {
-    const int lane = threadIdx.x & (MAS_WAVE - 1);
-    const int ry = threadIdx.x / MAS_WAVE;
-    const int y = ty * kTileH + ry;
-    if (y >= a.g.H) return;                   // (wave-uniform)
-    const size_t row = ((size_t)n * a.g.H + y) * a.g.W;
-#pragma unroll
-    for (int k = 0; k < kTileW / MAS_WAVE; ++k) {
-        const int rx = k * MAS_WAVE + lane;
-        const int x = tx * kTileW + rx;
-        bool sel = false;
-        if (x < a.g.W && a.mask[row + x]) {
-            const int id = load_id_any(a.spx, a.spx_dtype, row + x);
-            sel = id >= 0 && id < a.g.S;
-        }
-        queue_push(sel, (unsigned short)((ry << 8) | rx), queue, qcount);
+struct SoftCe {
+    const float* zq; const void* spx; const unsigned char* mask; const unsigned* bits; const float* softw; const int* live;
+    Geo g; float invT; int spx_dtype; int tiles_x, tiles_y;
+    struct Px { unsigned Yc; int multi; const float* sw; float A; };     // candidates, whether they carry soft weights, where those start
+
+    __device__ __forceinline__ bool runs(int n) const { return live[n] != 0; }            // a picture without a valid pixel adds nothing
+    __device__ __forceinline__ bool selects(size_t i, int) const {
+        if (!mask[i]) return false;
+        const int id = load_id_any(spx, spx_dtype, i);
+        return id >= 0 && id < g.S;
     }
-}
+    template <int CT, bool EXACT>
+    __device__ __forceinline__ bool pixel(int n, int py, int px, float (&v)[CT], OplTap& t, Px& s, float& term) const {
+        const int C = EXACT ? CT : g.C;
+        const size_t HW = (size_t)g.H * g.W, pix = (size_t)py * g.W + px;
+        const int id = load_id_any(spx, spx_dtype, (size_t)n * HW + pix);
+        s.Yc = mas_opl_cands(bits[(size_t)n * g.S + id], C, &s.multi);
+        s.sw = softw + (size_t)n * C * HW + pix;
+        ce_probs<CT, EXACT>(zq, g, invT, n, py, px, v, t);
+        term = mas_opl_soft_term<CT>(v, C, s.Yc, s.multi, s.sw, HW, &s.A);
+        return true;
+    }
+    __device__ __forceinline__ mas_u64 fix(float term) const { return mas_fix(term, MAS_LOSS_FRAC_BITS); }
+    __device__ __forceinline__ float k(const Px&, float scale) const { return scale; }
+    __device__ __forceinline__ float dir(const Px& s, int c, float pc) const {
+        const int in_y = (int)((s.Yc >> c) & 1u);
+        const float wj = (in_y && s.multi) ? s.sw[(size_t)c * ((size_t)g.H * g.W)] : 1.0f;
+        return mas_opl_soft_dir(pc, s.A, in_y, wj);
+    }
+};
 
-// probabilities of the queued pixel, its candidates, whether they carry soft weights, and where those start
-template <int CT, bool EXACT>
-__device__ __forceinline__ void soft_pixel(const SoftArgs& a, int n, int py, int px, float (&v)[CT], OplTap& t, unsigned& Yc, int& multi,
-                                           const float*& sw) {
-    const int C = EXACT ? CT : a.g.C;
-    const size_t hw = (size_t)a.g.h * a.g.w, HW = (size_t)a.g.H * a.g.W;
-    const size_t pix = (size_t)py * a.g.W + px;
-    const int id = load_id_any(a.spx, a.spx_dtype, (size_t)n * HW + pix);
-    Yc = mas_opl_cands(a.bits[(size_t)n * a.g.S + id], C, &multi);
-    sw = a.softw + (size_t)n * C * HW + pix;
-    t = mas_opl_tap(a.g.sh, a.g.sw, py, px, a.g.h, a.g.w);
-    mas_opl_logits<CT>(a.zq + (size_t)n * C * hw, hw, t, C, v);
-    mas_opl_softmax<CT>(v, C, a.invT);
-}
-
-template <int CT, bool EXACT>
-__global__ __launch_bounds__(kThreads) void k_soft_ce_fwd(const SoftArgs a, mas_u64* __restrict__ acc) {
+template <int CT, bool EXACT, typename P>
+__device__ __forceinline__ void ce_fwd(const P& a, mas_u64* __restrict__ acc) {
     __shared__ int qcount[2];
     __shared__ unsigned short queue[kTilePx];
     __shared__ mas_u64 s_red[kThreads / MAS_WAVE][2];
-    const int C = EXACT ? CT : a.g.C;
-    int bid = blockIdx.x;
-    const int tx = bid % a.tiles_x; bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int n = bid / a.tiles_y;
-    if (!a.live[n]) return;                   // (uniform) a picture without a valid pixel adds nothing
-    if (threadIdx.x == 0) qcount[0] = 0;
-    __syncthreads();
-    tile_compact_soft(a, n, tx, ty, queue, qcount);
-    __syncthreads();
-    const int nq = qcount[0];
+    int n, ty, tx;
+    const int nq = tile_queue(a, EXACT ? CT : a.g.C, queue, qcount, n, ty, tx);
     if (nq == 0) return;                      // (uniform)
     mas_u64 sum = 0, cnt = 0;
     for (int i = threadIdx.x; i < nq; i += kThreads) {
         const unsigned off = queue[i];
         float v[CT];
         OplTap t;
-        unsigned Yc;
-        int multi;
-        const float* sw;
-        soft_pixel<CT, EXACT>(a, n, ty * kTileH + (int)(off >> 8), tx * kTileW + (int)(off & 255u), v, t, Yc, multi, sw);
-        float A;
-        const float term = mas_opl_soft_term<CT>(v, C, Yc, multi, sw, (size_t)a.g.H * a.g.W, &A);
-        sum += mas_fix(term, MAS_LOSS_FRAC_BITS);
-        cnt += 1;
+        typename P::Px s;
+        float term;
+        if (a.template pixel<CT, EXACT>(n, ty * kTileH + (int)(off >> 8), tx * kTileW + (int)(off & 255u), v, t, s, term)) {
+            sum += a.fix(term);
+            cnt += 1;
+        }
     }
     const int lane = threadIdx.x & (MAS_WAVE - 1), wave = threadIdx.x / MAS_WAVE;
 #pragma unroll
@@ -455,145 +320,147 @@ __global__ __launch_bounds__(kThreads) void k_soft_ce_fwd(const SoftArgs a, mas_
     }
 }
 
-// the LDS image of k_label_ce_bwd for the tile's quarter-resolution footprint; other class counts add to memory directly
+// The quarter-resolution footprint of a 4 x 256 tile (<= 4 rows x 72 columns per class for the x4 ratio of the model) is summed in LDS
+// first; only its non-zero entries go to memory.  Taps outside that image (other ratios) go to memory directly, and so does every tap
+// of the generic class count, which has no image.
+// The image is held through a pointer typed as LDS.  Through a generic one the optimiser merges the two adds of a tap into one flat
+// atomic on a selected pointer (no DS atomic left, 80 registers more, a wave less: profiles/opl_core/README.md).
+typedef __attribute__((address_space(3))) mas_u64 lds_u64;
+
 template <int CT, bool EXACT>
-__global__ __launch_bounds__(kThreads) void k_soft_ce_bwd(const SoftArgs a, const mas_u64* __restrict__ acc, const float* __restrict__ grad,
-                                                           mas_u64* __restrict__ dq) {
-    constexpr int kLR = 4, kLC = 72;
-    __shared__ int qcount[2];
-    __shared__ unsigned short queue[kTilePx];
-    __shared__ mas_u64 s_acc[EXACT ? CT * kLR * kLC : 1];
-    const int C = EXACT ? CT : a.g.C;
-    int bid = blockIdx.x;
-    const int tx = bid % a.tiles_x; bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int n = bid / a.tiles_y;
-    if (!a.live[n]) return;                   // (uniform)
-    if (threadIdx.x == 0) qcount[0] = 0;
-    __syncthreads();
-    tile_compact_soft(a, n, tx, ty, queue, qcount);
-    __syncthreads();
-    const int nq = qcount[0];
-    if (nq == 0) return;                      // (uniform)
-    const int hw = a.g.h * a.g.w;
-    const size_t HW = (size_t)a.g.H * a.g.W;
-    mas_u64* qb = dq + (size_t)n * C * hw;
-    const int ry0 = make_tap(a.g.sh, ty * kTileH, a.g.h).i0;
-    const int rx0 = make_tap(a.g.sw, tx * kTileW, a.g.w).i0;
-    if (EXACT) {
-        for (int i = threadIdx.x; i < CT * kLR * kLC; i += kThreads) s_acc[i] = 0;
+struct QuarterImage {
+    static constexpr int kLR = 4, kLC = 72, kPlane = kLR * kLC, kSize = EXACT ? CT * kPlane : 1;
+    lds_u64* s_acc;               // [kSize]
+    mas_u64* qb;                  // the picture's planes [C, h*w] in memory
+    int hw, w, ry0, rx0;
+
+    __device__ __forceinline__ void zero() const {
+        if (!EXACT) return;
+        for (int i = threadIdx.x; i < kSize; i += kThreads) s_acc[i] = 0;
         __syncthreads();
     }
-    auto place = [&](int o, int& r, int& x) {
-        r = o / a.g.w - ry0;
-        x = o % a.g.w - rx0;
-        if (!EXACT || r >= kLR || x >= kLC) r = -1;
-    };
-    auto add_q = [&](int c, int o, int r, int x, long long val) {
-        if (EXACT && r >= 0) atomicAdd(&s_acc[(c * kLR + r) * kLC + x], (mas_u64)val);
+    // the place of element o of a plane within the image's plane, or -1 when it lies outside (then the add goes to memory)
+    __device__ __forceinline__ int place(int o) const {
+        const int r = o / w - ry0, x = o % w - rx0;
+        return (!EXACT || r >= kLR || x >= kLC) ? -1 : r * kLC + x;
+    }
+    __device__ __forceinline__ void add(int c, int o, int at, long long val) const {
+        if (EXACT && at >= 0) __hip_atomic_fetch_add(&s_acc[c * kPlane + at], (mas_u64)val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else atomicAdd(qb + (size_t)c * hw + o, (mas_u64)val);
-    };
-    const float k = (grad[0] / (float)acc[1]) * a.invT;
+    }
+    __device__ __forceinline__ void flush() const {
+        if (!EXACT) return;
+        __syncthreads();
+        for (int i = threadIdx.x; i < kSize; i += kThreads) {
+            const mas_u64 val = s_acc[i];
+            if (val) {
+                const int c = i / kPlane, rem = i - c * kPlane;
+                const int r = rem / kLC, x = rem - r * kLC;
+                atomicAdd(qb + (size_t)c * hw + (size_t)(ry0 + r) * w + (rx0 + x), val);
+            }
+        }
+    }
+};
+
+template <int CT, bool EXACT, typename P>
+__device__ __forceinline__ void ce_bwd(const P& a, const mas_u64* __restrict__ acc, const float* __restrict__ grad, mas_u64* __restrict__ dq) {
+    __shared__ int qcount[2];
+    __shared__ unsigned short queue[kTilePx];
+    __shared__ mas_u64 s_acc[QuarterImage<CT, EXACT>::kSize];
+    const int C = EXACT ? CT : a.g.C;
+    int n, ty, tx;
+    const int nq = tile_queue(a, C, queue, qcount, n, ty, tx);
+    if (nq == 0) return;                      // (uniform)
+    const int hw = a.g.h * a.g.w;
+    const QuarterImage<CT, EXACT> img{(lds_u64*)s_acc, dq + (size_t)n * C * hw, hw, a.g.w, make_tap(a.g.sh, ty * kTileH, a.g.h).i0,
+                                      make_tap(a.g.sw, tx * kTileW, a.g.w).i0};
+    img.zero();
+    const float scale = (grad[0] / (float)acc[1]) * a.invT;
     for (int i = threadIdx.x; i < nq; i += kThreads) {
         const unsigned off = queue[i];
         float v[CT];
         OplTap t;
-        unsigned Yc;
-        int multi;
-        const float* sw;
-        soft_pixel<CT, EXACT>(a, n, ty * kTileH + (int)(off >> 8), tx * kTileW + (int)(off & 255u), v, t, Yc, multi, sw);
-        float A;
-        (void)mas_opl_soft_term<CT>(v, C, Yc, multi, sw, HW, &A);
+        typename P::Px s;
+        float term;
+        if (!a.template pixel<CT, EXACT>(n, ty * kTileH + (int)(off >> 8), tx * kTileW + (int)(off & 255u), v, t, s, term)) continue;
+        const float k = a.k(s, scale);
         const float w00 = t.l0h * t.l0w, w01 = t.l0h * t.l1w, w10 = t.l1h * t.l0w, w11 = t.l1h * t.l1w;
-        int r00, x00, r01, x01, r10, x10, r11, x11;
-        place(t.o00, r00, x00);
-        place(t.o01, r01, x01);
-        place(t.o10, r10, x10);
-        place(t.o11, r11, x11);
+        const int at00 = img.place(t.o00), at01 = img.place(t.o01), at10 = img.place(t.o10), at11 = img.place(t.o11);
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
             if (EXACT || c < C) {
-                const int in_y = (int)((Yc >> c) & 1u);
-                const float wj = (in_y && multi) ? sw[(size_t)c * HW] : 1.0f;
-                const float d = k * mas_opl_soft_dir(v[c], A, in_y, wj);
-                add_q(c, t.o00, r00, x00, mas_opl_grad_fix(d * w00));
-                add_q(c, t.o01, r01, x01, mas_opl_grad_fix(d * w01));
-                add_q(c, t.o10, r10, x10, mas_opl_grad_fix(d * w10));
-                add_q(c, t.o11, r11, x11, mas_opl_grad_fix(d * w11));
+                const float d = k * a.dir(s, c, v[c]);
+                img.add(c, t.o00, at00, mas_opl_grad_fix(d * w00));
+                img.add(c, t.o01, at01, mas_opl_grad_fix(d * w01));
+                img.add(c, t.o10, at10, mas_opl_grad_fix(d * w10));
+                img.add(c, t.o11, at11, mas_opl_grad_fix(d * w11));
             }
         }
     }
-    if (EXACT) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < CT * kLR * kLC; i += kThreads) {
-            const mas_u64 val = s_acc[i];
-            if (val) {
-                const int c = i / (kLR * kLC), rem = i - c * (kLR * kLC);
-                const int r = rem / kLC, x = rem - r * kLC;
-                atomicAdd(qb + (size_t)c * hw + (size_t)(ry0 + r) * a.g.w + (rx0 + x), val);
-            }
-        }
+    img.flush();
+}
+
+// the entry names of the traces and profiles: thin shells over the core
+template <int CT, bool EXACT>
+__global__ __launch_bounds__(kThreads) void k_label_ce_fwd(const LabelCe a, mas_u64* __restrict__ acc) { ce_fwd<CT, EXACT>(a, acc); }
+template <int CT, bool EXACT>
+__global__ __launch_bounds__(kThreads) void k_label_ce_bwd(const LabelCe a, const mas_u64* __restrict__ acc, const float* __restrict__ grad,
+                                                            mas_u64* __restrict__ dq) { ce_bwd<CT, EXACT>(a, acc, grad, dq); }
+template <int CT, bool EXACT>
+__global__ __launch_bounds__(kThreads) void k_soft_ce_fwd(const SoftCe a, mas_u64* __restrict__ acc) { ce_fwd<CT, EXACT>(a, acc); }
+template <int CT, bool EXACT>
+__global__ __launch_bounds__(kThreads) void k_soft_ce_bwd(const SoftCe a, const mas_u64* __restrict__ acc, const float* __restrict__ grad,
+                                                           mas_u64* __restrict__ dq) { ce_bwd<CT, EXACT>(a, acc, grad, dq); }
+
+template <int CT, bool EXACT> auto fwd_kernel(const LabelCe&) { return &k_label_ce_fwd<CT, EXACT>; }
+template <int CT, bool EXACT> auto bwd_kernel(const LabelCe&) { return &k_label_ce_bwd<CT, EXACT>; }
+template <int CT, bool EXACT> auto fwd_kernel(const SoftCe&) { return &k_soft_ce_fwd<CT, EXACT>; }
+template <int CT, bool EXACT> auto bwd_kernel(const SoftCe&) { return &k_soft_ce_bwd<CT, EXACT>; }
+
+__global__ void k_label_ce_value(const mas_u64* __restrict__ acc, int flags, float* __restrict__ loss) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    loss[0] = mas_opl_value(acc[0], acc[1], flags);
+}
+
+// ---- dispatch -----------------------------------------------------------------------------------------------------------------------
+// f(class extent, exact) for the class counts with a build of their own, else for the generic one
+template <typename F>
+int for_class_count(int C, F f) {
+    switch (C) {
+        case 19: return f(std::integral_constant<int, 19>{}, std::true_type{});
+        case 20: return f(std::integral_constant<int, 20>{}, std::true_type{});
+        case 21: return f(std::integral_constant<int, 21>{}, std::true_type{});
+        default: return f(std::integral_constant<int, MAS_MAX_CLASSES>{}, std::false_type{});
     }
 }
 
-template <int CT, bool EXACT>
-int launch_soft_ce(const SoftArgs& a, unsigned nblk, const mas_u64* acc_in, const float* grad, mas_u64* out, bool backward, hipStream_t st) {
-    if (!backward) hipLaunchKernelGGL((k_soft_ce_fwd<CT, EXACT>), dim3(nblk), dim3(kThreads), 0, st, a, out);
-    else hipLaunchKernelGGL((k_soft_ce_bwd<CT, EXACT>), dim3(nblk), dim3(kThreads), 0, st, a, acc_in, grad, out);
-    return mas_launch_status();
-}
+bool id_dtype_ok(int spx_dtype) { return spx_dtype == MAS_ID_I64 || spx_dtype == MAS_ID_I32 || spx_dtype == MAS_ID_U16; }
 
-int dispatch_soft_ce(const SoftArgs& a0, int N, const mas_u64* acc_in, const float* grad, mas_u64* out, bool backward, hipStream_t st) {
-    SoftArgs a = a0;
-    a.tiles_x = (a.g.W + kTileW - 1) / kTileW;
-    a.tiles_y = (a.g.H + kTileH - 1) / kTileH;
-    const long long nblk = (long long)N * a.tiles_x * a.tiles_y;
-    if (nblk <= 0 || nblk > 0x7fffffffLL) return MAS_ERR_SHAPE;
-    switch (a.g.C) {
-        case 19: return launch_soft_ce<19, true>(a, (unsigned)nblk, acc_in, grad, out, backward, st);
-        case 20: return launch_soft_ce<20, true>(a, (unsigned)nblk, acc_in, grad, out, backward, st);
-        case 21: return launch_soft_ce<21, true>(a, (unsigned)nblk, acc_in, grad, out, backward, st);
-        default: return launch_soft_ce<MAS_MAX_CLASSES, false>(a, (unsigned)nblk, acc_in, grad, out, backward, st);
-    }
-}
-
-template <int CT, bool EXACT>
-int launch_assign(int spx_dtype, const float* zq, const float* featq, const void* spx, const unsigned char* mask, const unsigned* bits,
-                  const mas_u64* gmax, const Geo& g, long long total, float invT, int flags, unsigned char* labels, float* weight,
-                  hipStream_t st) {
-    const dim3 grid((unsigned)((total + kThreads - 1) / kThreads)), block(kThreads);
-#define MAS_OPL_ASSIGN(IDT)                                                                                                              \
-    hipLaunchKernelGGL((k_online_assign<CT, EXACT, IDT>), grid, block, 0, st, zq, featq, static_cast<const IDT*>(spx), mask, bits, gmax, g, \
-                       total, invT, flags, labels, weight)
+// f(typed id pointer); the entry points have refused every other dtype (id_dtype_ok)
+template <typename F>
+int for_id_type(const void* spx, int spx_dtype, F f) {
     switch (spx_dtype) {
-        case MAS_ID_I64: MAS_OPL_ASSIGN(long long); break;
-        case MAS_ID_I32: MAS_OPL_ASSIGN(int); break;
-        case MAS_ID_U16: MAS_OPL_ASSIGN(unsigned short); break;
+        case MAS_ID_I64: return f(static_cast<const long long*>(spx));
+        case MAS_ID_I32: return f(static_cast<const int*>(spx));
+        case MAS_ID_U16: return f(static_cast<const unsigned short*>(spx));
         default: return MAS_ERR_DTYPE;
     }
-#undef MAS_OPL_ASSIGN
-    return mas_launch_status();
 }
 
-template <int CT, bool EXACT>
-int launch_ce(const CeArgs& a, unsigned nblk, const mas_u64* acc_in, const float* grad, mas_u64* out, bool backward, hipStream_t st) {
-    if (!backward) hipLaunchKernelGGL((k_label_ce_fwd<CT, EXACT>), dim3(nblk), dim3(kThreads), 0, st, a, out);
-    else hipLaunchKernelGGL((k_label_ce_bwd<CT, EXACT>), dim3(nblk), dim3(kThreads), 0, st, a, acc_in, grad, out);
-    return mas_launch_status();
-}
-
-int dispatch_ce(const CeArgs& a0, int N, const mas_u64* acc_in, const float* grad, mas_u64* out, bool backward, hipStream_t st) {
-    CeArgs a = a0;
+// one workgroup per tile of every picture: the forward into out = acc when grad is null, else the backward into out = dq
+template <typename P>
+int launch_ce(P a, int N, const mas_u64* acc_in, const float* grad, mas_u64* out, hipStream_t st) {
     a.tiles_x = (a.g.W + kTileW - 1) / kTileW;
     a.tiles_y = (a.g.H + kTileH - 1) / kTileH;
     const long long nblk = (long long)N * a.tiles_x * a.tiles_y;
     if (nblk <= 0 || nblk > 0x7fffffffLL) return MAS_ERR_SHAPE;
-    switch (a.g.C) {
-        case 19: return launch_ce<19, true>(a, (unsigned)nblk, acc_in, grad, out, backward, st);
-        case 20: return launch_ce<20, true>(a, (unsigned)nblk, acc_in, grad, out, backward, st);
-        case 21: return launch_ce<21, true>(a, (unsigned)nblk, acc_in, grad, out, backward, st);
-        default: return launch_ce<MAS_MAX_CLASSES, false>(a, (unsigned)nblk, acc_in, grad, out, backward, st);
-    }
+    return for_class_count(a.g.C, [&](auto ct, auto exact) {
+        constexpr int CT = decltype(ct)::value;
+        constexpr bool EXACT = decltype(exact)::value;
+        if (!grad) hipLaunchKernelGGL((fwd_kernel<CT, EXACT>(a)), dim3((unsigned)nblk), dim3(kThreads), 0, st, a, out);
+        else hipLaunchKernelGGL((bwd_kernel<CT, EXACT>(a)), dim3((unsigned)nblk), dim3(kThreads), 0, st, a, acc_in, grad, out);
+        return mas_launch_status();
+    });
 }
 
 // shape / range checks shared by the entry points; nothing is launched when one fails
@@ -614,13 +481,72 @@ int check_ce(const float* zq, const unsigned char* labels, const float* weight, 
     return 0;
 }
 
+int check_soft(const float* zq, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits, const float* softw, const int* live,
+               int N, int C, int h, int w, int H, int W, int S) {
+    if (!zq || !spx || !mask || !bits || !softw || !live) return MAS_ERR_NULL;
+    if (S <= 0) return MAS_ERR_SHAPE;
+    if (int e = check_geometry(N, C, h, w, H, W)) return e;
+    if (!id_dtype_ok(spx_dtype)) return MAS_ERR_DTYPE;
+    return 0;
+}
+
 // MAS_OPL_WEIGHT_SIM never reads the prototype flag: both at once is a caller's mistake
 bool weight_flags_ok(int flags) {
     if (flags & ~(MAS_OPL_WEIGHT_WO_PROTO | MAS_OPL_WEIGHT_SIM)) return false;
     return (flags & (MAS_OPL_WEIGHT_WO_PROTO | MAS_OPL_WEIGHT_SIM)) != (MAS_OPL_WEIGHT_WO_PROTO | MAS_OPL_WEIGHT_SIM);
 }
 
-bool id_dtype_ok(int spx_dtype) { return spx_dtype == MAS_ID_I64 || spx_dtype == MAS_ID_I32 || spx_dtype == MAS_ID_U16; }
+// The prologue of the two per-pixel entry points.  `given`: every pointer is there; `range_ok`: the entry's own scalar is in range;
+// `live`, when the entry has one, is zeroed with the work buffer.  Leaves in *gmax the per-(superpixel, class) arg-pixel table: the
+// existing group scan and its key encoding.
+int scan_prototypes(bool given, const float* zq_p, int Ch, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask,
+                    const uint32_t* bits, int N, int C, int H, int W, int S, float invT, bool range_ok, void* work, size_t work_bytes,
+                    int32_t* live, void* stream, const mas_u64** gmax) {
+    if (!given) return MAS_ERR_NULL;
+    if (S <= 0) return MAS_ERR_SHAPE;
+    if (int e = check_geometry(N, C, h, w, H, W)) return e;
+    if (Ch < 1 || Ch > MAS_OPL_MAX_FEAT || !range_ok) return MAS_ERR_RANGE;
+    if (!id_dtype_ok(spx_dtype)) return MAS_ERR_DTYPE;
+    const size_t need = mas_online_plbl_work_bytes(N, S, C);
+    if (work_bytes < need) return MAS_ERR_WORKSPACE;
+    if ((uintptr_t)work % 8 != 0 || (uintptr_t)live % 4 != 0) return MAS_ERR_ALIGN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t me = hipMemsetAsync(work, 0, need, st);
+    if (me == hipSuccess && live) me = hipMemsetAsync(live, 0, (size_t)N * sizeof(int32_t), st);
+    if (me != hipSuccess) return (int)me;
+    uint64_t* acc = static_cast<uint64_t*>(work);
+    *gmax = reinterpret_cast<const mas_u64*>(acc + 8);
+    return mas_partial_loss_fwd_lowres(zq_p, h, w, spx, spx_dtype, mask, bits, N, C, H, W, S, invT, MAS_LOSS_GROUP | MAS_LOSS_GROUP_ONLY_MULTI,
+                                       acc + 8, acc, stream);
+}
+
+// the tail of the forward entry points: acc is zeroed, filled, and turned into the value when the caller wants it
+template <typename P>
+int ce_forward(const P& a, int N, uint64_t* acc, int value_flags, float* loss, void* stream) {
+    if ((uintptr_t)acc % 8 != 0) return MAS_ERR_ALIGN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const hipError_t me = hipMemsetAsync(acc, 0, 2 * sizeof(uint64_t), st);
+    if (me != hipSuccess) return (int)me;
+    if (int e = launch_ce(a, N, nullptr, nullptr, reinterpret_cast<mas_u64*>(acc), st)) return e;
+    return loss ? mas_label_ce_value(acc, value_flags, loss, stream) : 0;
+}
+
+// the tail of the backward entry points: dzq_fix [N,C,h,w] is zeroed, filled, and converted when the caller wants floats
+template <typename P>
+int ce_backward(const P& a, int N, const uint64_t* acc, const float* grad, int64_t* dzq_fix, float* dzq, void* stream) {
+    if ((uintptr_t)dzq_fix % 8 != 0) return MAS_ERR_ALIGN;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t nq = (size_t)N * a.g.C * a.g.h * a.g.w;
+    const hipError_t me = hipMemsetAsync(dzq_fix, 0, nq * sizeof(int64_t), st);
+    if (me != hipSuccess) return (int)me;
+    if (int e = launch_ce(a, N, reinterpret_cast<const mas_u64*>(acc), grad, reinterpret_cast<mas_u64*>(dzq_fix), st)) return e;
+    return dzq ? mas_fix_to_float(dzq_fix, (int64_t)nq, MAS_GRAD_FRAC_BITS, dzq, stream) : 0;
+}
+
+LabelCe label_ce(const float* zq, int h, int w, const uint8_t* labels, const float* weight, int C, int H, int W, float invT, int flags,
+                 float th) {
+    return LabelCe{zq, labels, weight, make_geo(C, 0, h, w, H, W, 0), invT, flags & 3, th, 0, 0, (flags & MAS_LCE_SIGNED) ? 1 : 0};
+}
 }  // namespace
 
 extern "C" size_t mas_online_plbl_work_bytes(int N, int S, int C) {
@@ -631,33 +557,37 @@ extern "C" size_t mas_online_plbl_work_bytes(int N, int S, int C) {
 extern "C" int mas_online_plbl_labels(const float* zq_p, const float* featq, int Ch, int h, int w, const void* spx, int spx_dtype,
                                       const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, float invT, int flags,
                                       void* work, size_t work_bytes, uint8_t* labels, float* weight, void* stream) {
-    if (!zq_p || !featq || !spx || !mask || !bits || !work || !labels || !weight) return MAS_ERR_NULL;
-    if (S <= 0) return MAS_ERR_SHAPE;
-    if (int e = check_geometry(N, C, h, w, H, W)) return e;
-    if (Ch < 1 || Ch > MAS_OPL_MAX_FEAT || !weight_flags_ok(flags)) return MAS_ERR_RANGE;
-    if (!id_dtype_ok(spx_dtype)) return MAS_ERR_DTYPE;
-    const size_t need = mas_online_plbl_work_bytes(N, S, C);
-    if (work_bytes < need) return MAS_ERR_WORKSPACE;
-    if ((uintptr_t)work % 8 != 0) return MAS_ERR_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const hipError_t me = hipMemsetAsync(work, 0, need, st);
-    if (me != hipSuccess) return (int)me;
-    mas_u64* acc = static_cast<mas_u64*>(work);
-    mas_u64* gmax = acc + 8;
-    // the per-(superpixel, class) arg-pixel table: the existing group scan and its key encoding
-    if (int e = mas_partial_loss_fwd_lowres(zq_p, h, w, spx, spx_dtype, mask, bits, N, C, H, W, S, invT,
-                                            MAS_LOSS_GROUP | MAS_LOSS_GROUP_ONLY_MULTI, reinterpret_cast<uint64_t*>(gmax),
-                                            reinterpret_cast<uint64_t*>(acc), stream))
+    const mas_u64* gmax;
+    if (int e = scan_prototypes(zq_p && featq && spx && mask && bits && work && labels && weight, zq_p, Ch, h, w, spx, spx_dtype, mask, bits, N,
+                                C, H, W, S, invT, weight_flags_ok(flags), work, work_bytes, nullptr, stream, &gmax))
         return e;
     const Geo g = make_geo(C, Ch, h, w, H, W, S);
     const long long total = (long long)N * H * W;
-    switch (C) {
-        case 19: return launch_assign<19, true>(spx_dtype, zq_p, featq, spx, mask, bits, gmax, g, total, invT, flags, labels, weight, st);
-        case 20: return launch_assign<20, true>(spx_dtype, zq_p, featq, spx, mask, bits, gmax, g, total, invT, flags, labels, weight, st);
-        case 21: return launch_assign<21, true>(spx_dtype, zq_p, featq, spx, mask, bits, gmax, g, total, invT, flags, labels, weight, st);
-        default: return launch_assign<MAS_MAX_CLASSES, false>(spx_dtype, zq_p, featq, spx, mask, bits, gmax, g, total, invT, flags, labels,
-                                                              weight, st);
-    }
+    const dim3 grid((unsigned)((total + kThreads - 1) / kThreads));
+    return for_class_count(C, [&](auto ct, auto exact) {
+        return for_id_type(spx, spx_dtype, [&](auto ids) {
+            hipLaunchKernelGGL((k_online_assign<decltype(ct)::value, decltype(exact)::value>), grid, dim3(kThreads), 0,
+                               static_cast<hipStream_t>(stream), zq_p, featq, ids, mask, bits, gmax, g, total, invT, flags, labels, weight);
+            return mas_launch_status();
+        });
+    });
+}
+
+extern "C" int mas_online_soft_weights(const float* zq_p, const float* featq, int Ch, int h, int w, const void* spx, int spx_dtype,
+                                       const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, float invT, float invtau,
+                                       void* work, size_t work_bytes, float* softw, int32_t* live, void* stream) {
+    const mas_u64* gmax;
+    if (int e = scan_prototypes(zq_p && featq && spx && mask && bits && work && softw && live, zq_p, Ch, h, w, spx, spx_dtype, mask, bits, N, C,
+                                H, W, S, invT, invtau > 0.0f, work, work_bytes, live, stream, &gmax))
+        return e;
+    const Geo g = make_geo(C, Ch, h, w, H, W, S);
+    const long long total = (long long)N * H * W;
+    const dim3 grid((unsigned)((total + kThreads - 1) / kThreads));
+    return for_id_type(spx, spx_dtype, [&](auto ids) {
+        hipLaunchKernelGGL(k_online_soft, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), featq, ids, mask, bits, gmax, g, total,
+                           invtau, softw, live);
+        return mas_launch_status();
+    });
 }
 
 extern "C" int mas_label_ce_value(const uint64_t* acc, int flags, float* loss, void* stream) {
@@ -671,13 +601,7 @@ extern "C" int mas_label_ce_fwd_lowres(const float* zq, int h, int w, const uint
                                        float invT, int flags, float th, uint64_t* acc, float* loss, void* stream) {
     if (!acc) return MAS_ERR_NULL;
     if (int e = check_ce(zq, labels, weight, N, C, h, w, H, W, flags)) return e;
-    if ((uintptr_t)acc % 8 != 0) return MAS_ERR_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const hipError_t me = hipMemsetAsync(acc, 0, 2 * sizeof(uint64_t), st);
-    if (me != hipSuccess) return (int)me;
-    const CeArgs a{zq, labels, weight, make_geo(C, 0, h, w, H, W, 0), invT, flags & 3, th, 0, 0, (flags & MAS_LCE_SIGNED) ? 1 : 0};
-    if (int e = dispatch_ce(a, N, nullptr, nullptr, reinterpret_cast<mas_u64*>(acc), false, st)) return e;
-    return loss ? mas_label_ce_value(acc, flags, loss, stream) : 0;
+    return ce_forward(label_ce(zq, h, w, labels, weight, C, H, W, invT, flags, th), N, acc, flags, loss, stream);
 }
 
 extern "C" int mas_label_ce_bwd_lowres(const float* zq, int h, int w, const uint8_t* labels, const float* weight, const uint64_t* acc,
@@ -685,62 +609,7 @@ extern "C" int mas_label_ce_bwd_lowres(const float* zq, int h, int w, const uint
                                        float* dzq, void* stream) {
     if (!acc || !grad || !dzq_fix) return MAS_ERR_NULL;
     if (int e = check_ce(zq, labels, weight, N, C, h, w, H, W, flags)) return e;
-    if ((uintptr_t)dzq_fix % 8 != 0) return MAS_ERR_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t nq = (size_t)N * C * h * w;
-    const hipError_t me = hipMemsetAsync(dzq_fix, 0, nq * sizeof(int64_t), st);
-    if (me != hipSuccess) return (int)me;
-    const CeArgs a{zq, labels, weight, make_geo(C, 0, h, w, H, W, 0), invT, flags & 3, th, 0, 0, (flags & MAS_LCE_SIGNED) ? 1 : 0};
-    if (int e = dispatch_ce(a, N, reinterpret_cast<const mas_u64*>(acc), grad, reinterpret_cast<mas_u64*>(dzq_fix), true, st)) return e;
-    return dzq ? mas_fix_to_float(dzq_fix, (int64_t)nq, MAS_GRAD_FRAC_BITS, dzq, stream) : 0;
-}
-
-namespace {
-int check_soft(const float* zq, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits, const float* softw, const int* live,
-               int N, int C, int h, int w, int H, int W, int S) {
-    if (!zq || !spx || !mask || !bits || !softw || !live) return MAS_ERR_NULL;
-    if (S <= 0) return MAS_ERR_SHAPE;
-    if (int e = check_geometry(N, C, h, w, H, W)) return e;
-    if (!id_dtype_ok(spx_dtype)) return MAS_ERR_DTYPE;
-    return 0;
-}
-}  // namespace
-
-extern "C" int mas_online_soft_weights(const float* zq_p, const float* featq, int Ch, int h, int w, const void* spx, int spx_dtype,
-                                       const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, float invT, float invtau,
-                                       void* work, size_t work_bytes, float* softw, int32_t* live, void* stream) {
-    if (!zq_p || !featq || !spx || !mask || !bits || !work || !softw || !live) return MAS_ERR_NULL;
-    if (S <= 0) return MAS_ERR_SHAPE;
-    if (int e = check_geometry(N, C, h, w, H, W)) return e;
-    if (Ch < 1 || Ch > MAS_OPL_MAX_FEAT || !(invtau > 0.0f)) return MAS_ERR_RANGE;
-    if (!id_dtype_ok(spx_dtype)) return MAS_ERR_DTYPE;
-    const size_t need = mas_online_plbl_work_bytes(N, S, C);
-    if (work_bytes < need) return MAS_ERR_WORKSPACE;
-    if ((uintptr_t)work % 8 != 0 || (uintptr_t)live % 4 != 0) return MAS_ERR_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t me = hipMemsetAsync(work, 0, need, st);
-    if (me != hipSuccess) return (int)me;
-    me = hipMemsetAsync(live, 0, (size_t)N * sizeof(int32_t), st);
-    if (me != hipSuccess) return (int)me;
-    mas_u64* acc = static_cast<mas_u64*>(work);
-    mas_u64* gmax = acc + 8;
-    if (int e = mas_partial_loss_fwd_lowres(zq_p, h, w, spx, spx_dtype, mask, bits, N, C, H, W, S, invT,
-                                            MAS_LOSS_GROUP | MAS_LOSS_GROUP_ONLY_MULTI, reinterpret_cast<uint64_t*>(gmax),
-                                            reinterpret_cast<uint64_t*>(acc), stream))
-        return e;
-    const Geo g = make_geo(C, Ch, h, w, H, W, S);
-    const long long total = (long long)N * H * W;
-    const dim3 grid((unsigned)((total + kThreads - 1) / kThreads)), block(kThreads);
-#define MAS_OPL_SOFT(IDT)                                                                                                               \
-    hipLaunchKernelGGL((k_online_soft<IDT>), grid, block, 0, st, featq, static_cast<const IDT*>(spx), mask, bits, gmax, g, total, invtau, \
-                       softw, live)
-    switch (spx_dtype) {
-        case MAS_ID_I64: MAS_OPL_SOFT(long long); break;
-        case MAS_ID_I32: MAS_OPL_SOFT(int); break;
-        default: MAS_OPL_SOFT(unsigned short); break;
-    }
-#undef MAS_OPL_SOFT
-    return mas_launch_status();
+    return ce_backward(label_ce(zq, h, w, labels, weight, C, H, W, invT, flags, th), N, acc, grad, dzq_fix, dzq, stream);
 }
 
 extern "C" int mas_soft_ce_fwd_lowres(const float* zq, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits,
@@ -748,13 +617,7 @@ extern "C" int mas_soft_ce_fwd_lowres(const float* zq, int h, int w, const void*
                                       float* loss, void* stream) {
     if (!acc) return MAS_ERR_NULL;
     if (int e = check_soft(zq, spx, spx_dtype, mask, bits, softw, live, N, C, h, w, H, W, S)) return e;
-    if ((uintptr_t)acc % 8 != 0) return MAS_ERR_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const hipError_t me = hipMemsetAsync(acc, 0, 2 * sizeof(uint64_t), st);
-    if (me != hipSuccess) return (int)me;
-    const SoftArgs a{zq, spx, mask, bits, softw, live, make_geo(C, 0, h, w, H, W, S), invT, spx_dtype, 0, 0};
-    if (int e = dispatch_soft_ce(a, N, nullptr, nullptr, reinterpret_cast<mas_u64*>(acc), false, st)) return e;
-    return loss ? mas_label_ce_value(acc, 0, loss, stream) : 0;
+    return ce_forward(SoftCe{zq, spx, mask, bits, softw, live, make_geo(C, 0, h, w, H, W, S), invT, spx_dtype, 0, 0}, N, acc, 0, loss, stream);
 }
 
 extern "C" int mas_soft_ce_bwd_lowres(const float* zq, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits,
@@ -762,14 +625,8 @@ extern "C" int mas_soft_ce_bwd_lowres(const float* zq, int h, int w, const void*
                                       int W, int S, float invT, int64_t* dzq_fix, float* dzq, void* stream) {
     if (!acc || !grad || !dzq_fix) return MAS_ERR_NULL;
     if (int e = check_soft(zq, spx, spx_dtype, mask, bits, softw, live, N, C, h, w, H, W, S)) return e;
-    if ((uintptr_t)dzq_fix % 8 != 0) return MAS_ERR_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t nq = (size_t)N * C * h * w;
-    const hipError_t me = hipMemsetAsync(dzq_fix, 0, nq * sizeof(int64_t), st);
-    if (me != hipSuccess) return (int)me;
-    const SoftArgs a{zq, spx, mask, bits, softw, live, make_geo(C, 0, h, w, H, W, S), invT, spx_dtype, 0, 0};
-    if (int e = dispatch_soft_ce(a, N, reinterpret_cast<const mas_u64*>(acc), grad, reinterpret_cast<mas_u64*>(dzq_fix), true, st)) return e;
-    return dzq ? mas_fix_to_float(dzq_fix, (int64_t)nq, MAS_GRAD_FRAC_BITS, dzq, stream) : 0;
+    return ce_backward(SoftCe{zq, spx, mask, bits, softw, live, make_geo(C, 0, h, w, H, W, S), invT, spx_dtype, 0, 0}, N, acc, grad, dzq_fix,
+                       dzq, stream);
 }
 
 // ---- the CPU-side statement: host pointers, plain loops through online_plbl.h.  No device is touched. ---------------------------------
@@ -827,6 +684,93 @@ bool host_sim(const uint64_t* gm, uint32_t Y, int c, const float* fb, int Ch, si
     *sim = s;
     *is_proto = pp == pix;
     return true;
+}
+
+// The host's policies: what LabelCe and SoftCe say, said again on host pointers.  takes(n, i): pixel i of [N,H,W], in picture n, is one
+// the loss looks at; pixel(n, i, p, s, term): its state and term from its probabilities p, true when it is counted.
+struct HostLabelCe {
+    const uint8_t* labels; const float* weight; int C, mode; float th; int sgn;
+    struct Px { int lab; float wgt; };
+
+    bool takes(int, size_t i) const { return labels[i] < C; }
+    bool pixel(int, size_t i, const float (&p)[MAS_MAX_CLASSES], Px& s, float& term) const {
+        s.lab = labels[i];
+        s.wgt = mas_opl_mode_weight(mode, mode == MAS_LCE_UNWEIGHTED ? 1.0f : weight[i], th);
+        int counted;
+        term = mas_opl_term(mode, s.wgt, mas_opl_ce(p[s.lab]), &counted);
+        return counted != 0;
+    }
+    uint64_t fix(float term) const { return mas_opl_fix_term(term, sgn); }
+    float k(const Px& s, float scale) const { return scale * s.wgt; }
+    float dir(const Px& s, int c, float pc) const { return pc - ((c == s.lab) ? 1.0f : 0.0f); }
+};
+
+struct HostSoftCe {
+    const void* spx; int spx_dtype; const uint8_t* mask; const uint32_t* bits; const float* softw; const int32_t* live;
+    int C, S; size_t HW;
+    struct Px { uint32_t Yc; int multi; const float* sw; float A; };
+
+    bool takes(int n, size_t i) const {
+        if (!live[n] || !mask[i]) return false;
+        const long long id = (int)host_id(spx, spx_dtype, i);
+        return id >= 0 && id < S;
+    }
+    bool pixel(int n, size_t i, const float (&p)[MAS_MAX_CLASSES], Px& s, float& term) const {
+        s.Yc = mas_opl_cands(bits[(size_t)n * S + (size_t)(int)host_id(spx, spx_dtype, i)], C, &s.multi);
+        s.sw = softw + (size_t)n * C * HW + (i - (size_t)n * HW);
+        term = mas_opl_soft_term<MAS_MAX_CLASSES>(p, C, s.Yc, s.multi, s.sw, HW, &s.A);
+        return true;
+    }
+    uint64_t fix(float term) const { return mas_fix(term, MAS_LOSS_FRAC_BITS); }
+    float k(const Px&, float scale) const { return scale; }
+    float dir(const Px& s, int c, float pc) const {
+        const int in_y = (int)((s.Yc >> c) & 1u);
+        return mas_opl_soft_dir(pc, s.A, in_y, (in_y && s.multi) ? s.sw[(size_t)c * HW] : 1.0f);
+    }
+};
+
+// pass 0 counts and sums the terms of the counted pixels; pass 1, with dzq_fix, scatters their gradient through the four taps
+template <typename P>
+void host_ce(const P& a, const float* zq, const Geo& g, int N, float invT, int value_flags, const float* grad, uint64_t* acc, float* loss,
+             int64_t* dzq_fix) {
+    const size_t HW = (size_t)g.H * g.W, hw = (size_t)g.h * g.w;
+    acc[0] = acc[1] = 0;
+    for (int pass = 0; pass < (dzq_fix ? 2 : 1); ++pass) {
+        float scale = 0.0f;
+        if (pass == 1) {
+            scale = (grad[0] / (float)acc[1]) * invT;
+            for (size_t i = 0; i < (size_t)N * g.C * hw; ++i) dzq_fix[i] = 0;
+        }
+        for (int n = 0; n < N; ++n) {
+            for (size_t pix = 0; pix < HW; ++pix) {
+                const size_t gi = (size_t)n * HW + pix;
+                if (!a.takes(n, gi)) continue;
+                const OplTap t = mas_opl_tap(g.sh, g.sw, (int)(pix / g.W), (int)(pix % g.W), g.h, g.w);
+                float p[MAS_MAX_CLASSES];
+                mas_opl_logits<MAS_MAX_CLASSES>(zq + (size_t)n * g.C * hw, hw, t, g.C, p);
+                mas_opl_softmax<MAS_MAX_CLASSES>(p, g.C, invT);
+                typename P::Px s;
+                float term;
+                if (!a.pixel(n, gi, p, s, term)) continue;
+                if (pass == 0) {
+                    acc[0] += a.fix(term);
+                    acc[1] += 1;
+                    continue;
+                }
+                const float k = a.k(s, scale);
+                const float w00 = t.l0h * t.l0w, w01 = t.l0h * t.l1w, w10 = t.l1h * t.l0w, w11 = t.l1h * t.l1w;
+                for (int c = 0; c < g.C; ++c) {
+                    int64_t* q = dzq_fix + ((size_t)n * g.C + c) * hw;
+                    const float d = k * a.dir(s, c, p[c]);
+                    q[t.o00] += mas_opl_grad_fix(d * w00);
+                    q[t.o01] += mas_opl_grad_fix(d * w01);
+                    q[t.o10] += mas_opl_grad_fix(d * w10);
+                    q[t.o11] += mas_opl_grad_fix(d * w11);
+                }
+            }
+        }
+        if (pass == 0 && loss) loss[0] = mas_opl_value(acc[0], acc[1], value_flags);
+    }
 }
 }  // namespace
 
@@ -886,46 +830,8 @@ extern "C" int mas_online_plbl_reference(const float* zq_p, const float* featq, 
     if (!acc) return MAS_ERR_NULL;
     if (int e = check_ce(zq, labels, weight, N, C, h, w, H, W, ce_flags)) return e;
     if (dzq_fix && !grad) return MAS_ERR_NULL;
-    const int mode = ce_flags & 3;
-    acc[0] = acc[1] = 0;
-    for (int pass = 0; pass < (dzq_fix ? 2 : 1); ++pass) {
-        float scale = 0.0f;
-        if (pass == 1) {
-            scale = (grad[0] / (float)acc[1]) * invT_ce;
-            for (size_t i = 0; i < (size_t)N * C * hw; ++i) dzq_fix[i] = 0;
-        }
-        for (int n = 0; n < N; ++n) {
-            for (size_t pix = 0; pix < HW; ++pix) {
-                const size_t gi = (size_t)n * HW + pix;
-                const int lab = labels[gi];
-                if (lab >= C) continue;
-                const OplTap t = mas_opl_tap(g.sh, g.sw, (int)(pix / W), (int)(pix % W), h, w);
-                float p[MAS_MAX_CLASSES];
-                mas_opl_logits<MAS_MAX_CLASSES>(zq + (size_t)n * C * hw, hw, t, C, p);
-                mas_opl_softmax<MAS_MAX_CLASSES>(p, C, invT_ce);
-                const float wgt = mas_opl_mode_weight(mode, mode == MAS_LCE_UNWEIGHTED ? 1.0f : weight[gi], th);
-                int counted;
-                const float term = mas_opl_term(mode, wgt, mas_opl_ce(p[lab]), &counted);
-                if (!counted) continue;
-                if (pass == 0) {
-                    acc[0] += mas_opl_fix_term(term, (ce_flags & MAS_LCE_SIGNED) ? 1 : 0);
-                    acc[1] += 1;
-                    continue;
-                }
-                const float k = scale * wgt;
-                const float w00 = t.l0h * t.l0w, w01 = t.l0h * t.l1w, w10 = t.l1h * t.l0w, w11 = t.l1h * t.l1w;
-                for (int c = 0; c < C; ++c) {
-                    int64_t* q = dzq_fix + ((size_t)n * C + c) * hw;
-                    const float d = k * (p[c] - ((c == lab) ? 1.0f : 0.0f));
-                    q[t.o00] += mas_opl_grad_fix(d * w00);
-                    q[t.o01] += mas_opl_grad_fix(d * w01);
-                    q[t.o10] += mas_opl_grad_fix(d * w10);
-                    q[t.o11] += mas_opl_grad_fix(d * w11);
-                }
-            }
-        }
-        if (pass == 0 && loss) loss[0] = mas_opl_value(acc[0], acc[1], ce_flags);
-    }
+    host_ce(HostLabelCe{labels, weight, C, ce_flags & 3, th, (ce_flags & MAS_LCE_SIGNED) ? 1 : 0}, zq, g, N, invT_ce, ce_flags, grad, acc, loss,
+            dzq_fix);
     return 0;
 }
 
@@ -972,48 +878,6 @@ extern "C" int mas_simw_plbl_reference(const float* zq_p, const float* featq, in
     if (!zq) return 0;
     if (!acc) return MAS_ERR_NULL;
     if (dzq_fix && !grad) return MAS_ERR_NULL;
-    acc[0] = acc[1] = 0;
-    for (int pass = 0; pass < (dzq_fix ? 2 : 1); ++pass) {
-        float k = 0.0f;
-        if (pass == 1) {
-            k = (grad[0] / (float)acc[1]) * invT_ce;
-            for (size_t i = 0; i < (size_t)N * C * hw; ++i) dzq_fix[i] = 0;
-        }
-        for (int n = 0; n < N; ++n) {
-            if (!live[n]) continue;
-            for (size_t pix = 0; pix < HW; ++pix) {
-                const size_t gi = (size_t)n * HW + pix;
-                if (!mask[gi]) continue;
-                const long long id = (int)host_id(spx, spx_dtype, gi);
-                if (id < 0 || id >= S) continue;
-                int multi;
-                const uint32_t Yc = mas_opl_cands(bits[(size_t)n * S + (size_t)id], C, &multi);
-                const float* sw = softw + (size_t)n * C * HW + pix;
-                const OplTap t = mas_opl_tap(g.sh, g.sw, (int)(pix / W), (int)(pix % W), h, w);
-                float p[MAS_MAX_CLASSES];
-                mas_opl_logits<MAS_MAX_CLASSES>(zq + (size_t)n * C * hw, hw, t, C, p);
-                mas_opl_softmax<MAS_MAX_CLASSES>(p, C, invT_ce);
-                float A;
-                const float term = mas_opl_soft_term<MAS_MAX_CLASSES>(p, C, Yc, multi, sw, HW, &A);
-                if (pass == 0) {
-                    acc[0] += mas_fix(term, MAS_LOSS_FRAC_BITS);
-                    acc[1] += 1;
-                    continue;
-                }
-                const float w00 = t.l0h * t.l0w, w01 = t.l0h * t.l1w, w10 = t.l1h * t.l0w, w11 = t.l1h * t.l1w;
-                for (int c = 0; c < C; ++c) {
-                    int64_t* q = dzq_fix + ((size_t)n * C + c) * hw;
-                    const int in_y = (int)((Yc >> c) & 1u);
-                    const float wj = (in_y && multi) ? sw[(size_t)c * HW] : 1.0f;
-                    const float d = k * mas_opl_soft_dir(p[c], A, in_y, wj);
-                    q[t.o00] += mas_opl_grad_fix(d * w00);
-                    q[t.o01] += mas_opl_grad_fix(d * w01);
-                    q[t.o10] += mas_opl_grad_fix(d * w10);
-                    q[t.o11] += mas_opl_grad_fix(d * w11);
-                }
-            }
-        }
-        if (pass == 0 && loss) loss[0] = mas_opl_value(acc[0], acc[1], 0);
-    }
+    host_ce(HostSoftCe{spx, spx_dtype, mask, bits, softw, live, C, S, HW}, zq, g, N, invT_ce, 0, grad, acc, loss, dzq_fix);
     return 0;
 }

@@ -377,6 +377,21 @@ def _weight_flags(weight_wo_proto, weight_sim):
     return (_lib.OPL_WEIGHT_WO_PROTO if weight_wo_proto else 0) | (_lib.OPL_WEIGHT_SIM if weight_sim else 0)
 
 
+def _plbl_args(zq_p, featq, size, spx, mask, targets, bits):
+    """What both online per-pixel entry points take: the checked arguments up to S in call order, the work buffer and its size, the
+    (N, C, H, W) of the outputs, ``bits``, and the tensors behind the pointers that the caller holds until it has made the call."""
+    _need(zq_p, "inputs_plbl", torch.float32)
+    _need(featq, "feats_plbl", torch.float32)
+    _need(spx, "superpixels")
+    mask = _mask_u8(mask)
+    bits = _need(_plbl_bits(targets, bits), "bits", torch.int32)
+    N, C, h, w, H, W, Ch, S = _plbl_shapes(zq_p, featq, size, spx, mask, bits)
+    nbytes = int(_lib.load().mas_online_plbl_work_bytes(N, S, C))
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=zq_p.device)  # (zeroed inside the call)
+    head = (zq_p.data_ptr(), featq.data_ptr(), Ch, h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), N, C, H, W, S)
+    return head, (work.data_ptr(), work.numel() * 8), (N, C, H, W), bits, (mask, work)
+
+
 def online_pseudo_labels(zq_p, featq, size, spx, mask, targets=None, bits=None, invT=1.0, weight_wo_proto=False, weight_sim=False):
     """The reference's ``generate_plbl`` (``trainer/active_onlinewplbl_multi_predignore.py:20-125``) for the whole batch in ONE library
     call and without a host round trip: ``zq_p`` [N,C,h,w] quarter-resolution logits of the eval-mode forward, ``featq`` [N,Ch,h,w]
@@ -384,23 +399,13 @@ def online_pseudo_labels(zq_p, featq, size, spx, mask, targets=None, bits=None, 
     ``targets`` u8 [N,S,cols] or ready ``bits`` int32 [N,S].  Returns (labels u8 [N,H,W], 255 = none; weight f32 [N,H,W], 0 = none).
     ``weight_sim``: the weight is the pixel's inner product with the chosen prototype (``LocalsimWProtoCE``), which may be negative,
     instead of the softmax probability of the label; the library refuses it together with ``weight_wo_proto``."""
-    _need(zq_p, "inputs_plbl", torch.float32)
-    _need(featq, "feats_plbl", torch.float32)
-    _need(spx, "superpixels")
-    mask = _mask_u8(mask)
-    bits = _need(_plbl_bits(targets, bits), "bits", torch.int32)
-    N, C, h, w, H, W, Ch, S = _plbl_shapes(zq_p, featq, size, spx, mask, bits)
+    head, work, (N, C, H, W), bits, _keep = _plbl_args(zq_p, featq, size, spx, mask, targets, bits)
     dev = zq_p.device
-    lib = _lib.load()
-    nbytes = int(lib.mas_online_plbl_work_bytes(N, S, C))
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)           # (zeroed inside the call)
     labels = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
     weight = torch.empty((N, H, W), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.mas_online_plbl_labels(zq_p.data_ptr(), featq.data_ptr(), Ch, h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(),
-                                              bits.data_ptr(), N, C, H, W, S, invT, _weight_flags(weight_wo_proto, weight_sim),
-                                              work.data_ptr(), work.numel() * 8, labels.data_ptr(), weight.data_ptr(), _stream(zq_p)),
-                   "mas_online_plbl_labels")
+        _lib.check(_lib.load().mas_online_plbl_labels(*head, invT, _weight_flags(weight_wo_proto, weight_sim), *work, labels.data_ptr(),
+                                                      weight.data_ptr(), _stream(zq_p)), "mas_online_plbl_labels")
     return labels, weight
 
 
@@ -415,6 +420,30 @@ def _label_ce_check(zq, size, labels, weight, flags):
     return N, C, h, w, H, W
 
 
+def _ce_fwd(zq, reduce_acc, value_flags, entry, head):
+    """The forward half both cross entropies share: ``entry(*head, acc, loss, stream)`` fills acc, and loss unless ``reduce_acc`` runs
+    first, between the scan and the division.  Returns (loss f32 [1], acc i64 [2])."""
+    acc = torch.empty(2, dtype=torch.int64, device=zq.device)                     # (zeroed inside the call)
+    loss = torch.empty(1, dtype=torch.float32, device=zq.device)
+    lib = _lib.load()
+    with torch.cuda.device(zq.device):
+        st = _stream(zq)
+        _lib.check(getattr(lib, entry)(*head, acc.data_ptr(), None if reduce_acc is not None else loss.data_ptr(), st), entry)
+        if reduce_acc is not None:
+            reduce_acc(acc)
+            _lib.check(lib.mas_label_ce_value(acc.data_ptr(), value_flags, loss.data_ptr(), st), "mas_label_ce_value")
+    return loss, acc
+
+
+def _ce_bwd(zq, want_fix, entry, head):
+    """The backward half: ``entry(*head, fix, dzq, stream)`` fills the int64 sums and dzq.  Returns dzq, or (dzq, fix)."""
+    fix = torch.empty(zq.shape, dtype=torch.int64, device=zq.device)              # (zeroed inside the call)
+    dzq = torch.empty_like(zq)
+    with torch.cuda.device(zq.device):
+        _lib.check(getattr(_lib.load(), entry)(*head, fix.data_ptr(), dzq.data_ptr(), _stream(zq)), entry)
+    return (dzq, fix) if want_fix else dzq
+
+
 def label_ce_fwd_lowres(zq, size, labels, weight, invT, flags, th=0.0, reduce_acc=None):
     """Forward half of ``label_ce_lowres``: (loss f32 [1], acc i64 [2] = fixed-point sum and count).  ``reduce_acc(acc)`` (data
     parallel) runs between the scan and the division, so the mean is over the global batch."""
@@ -423,31 +452,16 @@ def label_ce_fwd_lowres(zq, size, labels, weight, invT, flags, th=0.0, reduce_ac
     if weight is not None:
         _need(weight, "weight", torch.float32)
     N, C, h, w, H, W = _label_ce_check(zq, size, labels, weight, flags)
-    acc = torch.empty(2, dtype=torch.int64, device=zq.device)                     # (zeroed inside the call)
-    loss = torch.empty(1, dtype=torch.float32, device=zq.device)
-    lib = _lib.load()
-    with torch.cuda.device(zq.device):
-        st = _stream(zq)
-        _lib.check(lib.mas_label_ce_fwd_lowres(zq.data_ptr(), h, w, labels.data_ptr(), _opt(weight), N, C, H, W, invT, flags, float(th),
-                                               acc.data_ptr(), None if reduce_acc is not None else loss.data_ptr(), st),
-                   "mas_label_ce_fwd_lowres")
-        if reduce_acc is not None:
-            reduce_acc(acc)
-            _lib.check(lib.mas_label_ce_value(acc.data_ptr(), flags, loss.data_ptr(), st), "mas_label_ce_value")
-    return loss, acc
+    return _ce_fwd(zq, reduce_acc, flags, "mas_label_ce_fwd_lowres",
+                   (zq.data_ptr(), h, w, labels.data_ptr(), _opt(weight), N, C, H, W, invT, flags, float(th)))
 
 
 def label_ce_bwd_lowres(zq, size, labels, weight, acc, grad, invT, flags, th=0.0, want_fix=False):
     """Backward half: dzq [N,C,h,w] f32 for the upstream gradient ``grad`` f32 [1] (and the int64 sums it was rounded from)."""
     _need(grad, "grad", torch.float32)
     N, C, h, w, H, W = _label_ce_check(zq, size, labels, weight, flags)
-    fix = torch.empty((N, C, h, w), dtype=torch.int64, device=zq.device)          # (zeroed inside the call)
-    dzq = torch.empty_like(zq)
-    with torch.cuda.device(zq.device):
-        _lib.check(_lib.load().mas_label_ce_bwd_lowres(zq.data_ptr(), h, w, labels.data_ptr(), _opt(weight), acc.data_ptr(), grad.data_ptr(),
-                                                       N, C, H, W, invT, flags, float(th), fix.data_ptr(), dzq.data_ptr(), _stream(zq)),
-                   "mas_label_ce_bwd_lowres")
-    return (dzq, fix) if want_fix else dzq
+    return _ce_bwd(zq, want_fix, "mas_label_ce_bwd_lowres", (zq.data_ptr(), h, w, labels.data_ptr(), _opt(weight), acc.data_ptr(),
+                                                             grad.data_ptr(), N, C, H, W, invT, flags, float(th)))
 
 
 class _LabelCELowRes(torch.autograd.Function):
@@ -529,22 +543,13 @@ def online_soft_weights(zq_p, featq, size, spx, mask, targets=None, bits=None, i
     range, multi-hot superpixel) gets, over its candidate classes, the softmax of its inner products with the classes' local prototypes
     at ``inv_tau`` = ``inv_temperature(simw_temp)``.  Returns (softw f32 [N,C,H,W], allocated uninitialised: only the candidate planes
     of valid pixels are written or read; live int32 [N]: the pictures with a valid pixel; bits int32 [N,S])."""
-    _need(zq_p, "inputs_plbl", torch.float32)
-    _need(featq, "feats_plbl", torch.float32)
-    _need(spx, "superpixels")
-    mask = _mask_u8(mask)
-    bits = _need(_plbl_bits(targets, bits), "bits", torch.int32)
-    N, C, h, w, H, W, Ch, S = _plbl_shapes(zq_p, featq, size, spx, mask, bits)
+    head, work, (N, C, H, W), bits, _keep = _plbl_args(zq_p, featq, size, spx, mask, targets, bits)
     dev = zq_p.device
-    lib = _lib.load()
-    nbytes = int(lib.mas_online_plbl_work_bytes(N, S, C))
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)           # (zeroed inside the call)
     softw = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
     live = torch.empty(N, dtype=torch.int32, device=dev)                           # (zeroed inside the call)
     with torch.cuda.device(dev):
-        _lib.check(lib.mas_online_soft_weights(zq_p.data_ptr(), featq.data_ptr(), Ch, h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(),
-                                               bits.data_ptr(), N, C, H, W, S, invT, inv_tau, work.data_ptr(), work.numel() * 8,
-                                               softw.data_ptr(), live.data_ptr(), _stream(zq_p)), "mas_online_soft_weights")
+        _lib.check(_lib.load().mas_online_soft_weights(*head, invT, inv_tau, *work, softw.data_ptr(), live.data_ptr(), _stream(zq_p)),
+                   "mas_online_soft_weights")
     return softw, live, bits
 
 
@@ -569,31 +574,18 @@ def soft_ce_fwd_lowres(zq, size, spx, mask, bits, softw, live, invT, reduce_acc=
     _need(softw, "softw", torch.float32)
     _need(live, "live", torch.int32)
     N, C, h, w, H, W, S = _soft_ce_check(zq, size, spx, mask, bits, softw, live)
-    acc = torch.empty(2, dtype=torch.int64, device=zq.device)                     # (zeroed inside the call)
-    loss = torch.empty(1, dtype=torch.float32, device=zq.device)
-    lib = _lib.load()
-    with torch.cuda.device(zq.device):
-        st = _stream(zq)
-        _lib.check(lib.mas_soft_ce_fwd_lowres(zq.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
-                                              softw.data_ptr(), live.data_ptr(), N, C, H, W, S, invT, acc.data_ptr(),
-                                              None if reduce_acc is not None else loss.data_ptr(), st), "mas_soft_ce_fwd_lowres")
-        if reduce_acc is not None:
-            reduce_acc(acc)
-            _lib.check(lib.mas_label_ce_value(acc.data_ptr(), 0, loss.data_ptr(), st), "mas_label_ce_value")
-    return loss, acc
+    return _ce_fwd(zq, reduce_acc, 0, "mas_soft_ce_fwd_lowres",
+                   (zq.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), softw.data_ptr(), live.data_ptr(),
+                    N, C, H, W, S, invT))
 
 
 def soft_ce_bwd_lowres(zq, size, spx, mask, bits, softw, live, acc, grad, invT, want_fix=False):
     """Backward half: dzq [N,C,h,w] f32 for the upstream gradient ``grad`` f32 [1] (and the int64 sums it was rounded from)."""
     _need(grad, "grad", torch.float32)
     N, C, h, w, H, W, S = _soft_ce_check(zq, size, spx, mask, bits, softw, live)
-    fix = torch.empty((N, C, h, w), dtype=torch.int64, device=zq.device)          # (zeroed inside the call)
-    dzq = torch.empty_like(zq)
-    with torch.cuda.device(zq.device):
-        _lib.check(_lib.load().mas_soft_ce_bwd_lowres(zq.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
-                                                      softw.data_ptr(), live.data_ptr(), acc.data_ptr(), grad.data_ptr(), N, C, H, W, S,
-                                                      invT, fix.data_ptr(), dzq.data_ptr(), _stream(zq)), "mas_soft_ce_bwd_lowres")
-    return (dzq, fix) if want_fix else dzq
+    return _ce_bwd(zq, want_fix, "mas_soft_ce_bwd_lowres",
+                   (zq.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), softw.data_ptr(), live.data_ptr(),
+                    acc.data_ptr(), grad.data_ptr(), N, C, H, W, S, invT))
 
 
 class _SoftCELowRes(torch.autograd.Function):

@@ -89,6 +89,57 @@ def test_kernels_equal_the_host_reference_on_other_paths(c, ch, h, w, s):
     assert _bit_for_bit(ops, t, (h, w), wo_proto=(True,)) > 0
 
 
+def uint16_edge_case():
+    """the edge case with the ids as uint16 on the host already, so the host loop and the kernels both read them as uint16; its ids
+    >= S stay out of range"""
+    e = R.edge_case()
+    t = _tensors(e)
+    t['spx'] = t['spx'].to(torch.uint16)
+    assert torch.equal(t['spx'].to(torch.int64), torch.from_numpy(e['spx']))
+    return e, t
+
+
+def test_kernels_equal_the_host_reference_with_uint16_ids():
+    """the third instantiation of the per-pixel kernel, never run by the other cases"""
+    ops = _gpu()
+    e, t = uint16_edge_case()
+    invT = ops.inv_temperature(R.T)
+    wide = ops.online_plbl_reference(t['zq_p'], t['featq'], e['size'], torch.from_numpy(e['spx']), t['msk'], targets=t['tgt'], invT=invT)
+    narrow = ops.online_plbl_reference(t['zq_p'], t['featq'], e['size'], t['spx'], t['msk'], targets=t['tgt'], invT=invT)
+    assert torch.equal(wide['labels'], narrow['labels']) and torch.equal(wide['gmax'], narrow['gmax'])
+    assert _bit_for_bit(ops, t, e['size'], id_types=(torch.uint16,)) > 500
+    labels, _ = ops.online_pseudo_labels(t['zq_p'].cuda(), t['featq'].cuda(), e['size'], t['spx'].cuda(), t['msk'].cuda(),
+                                         targets=t['tgt'].cuda(), invT=invT)
+    assert np.all(labels.cpu().numpy()[3][e['spx'][3] >= e['S']] == 255)
+
+
+def off_ratio_case():
+    """An exact class count (the build with the LDS image in the backward) away from the x4 footprint the image is sized for: C = 20,
+    8 x 300 from 8 x 150.  150 quarter columns under 300 pixels: tile 0 (x < 256) reaches quarter columns up to 128, past the image's
+    72.  8 quarter rows under 8 pixel rows: the second tap row of a 4-row tile is row 4 of the image, one past its last.  Both kinds of
+    tap go to memory directly; quarter columns 73..125 receive gradient from nowhere else (tile 1 starts at quarter column 127)."""
+    case = R.inputs(51, 2, 20, 8, 8, 300, hq=8, wq=150, s=12, frac=0.6)
+    return _tensors(dict(zip(('zq_p', 'featq', 'zq', 'tgt', 'spx', 'msk'), case))), (8, 300)
+
+
+def took_the_direct_path(acc, fix):
+    return int(acc[1]) > 0 and bool((fix[..., 73:126] != 0).any())
+
+
+def test_kernels_equal_the_host_reference_off_the_x4_ratio():
+    ops = _gpu()
+    t, size = off_ratio_case()
+    assert _bit_for_bit(ops, t, size) > 0
+    # the same calls once more, to see on the device's own output that the taps outside the image were there
+    invT, d = ops.inv_temperature(R.T), {k: v.cuda() for k, v in t.items()}
+    labels, weight = ops.online_pseudo_labels(d['zq_p'], d['featq'], size, d['spx'], d['msk'], targets=d['tgt'], invT=invT)
+    for mode, th in MODES:
+        w = None if mode == 0 else weight
+        _, acc = ops.label_ce_fwd_lowres(d['zq'], size, labels, w, invT, mode, th)
+        _, fix = ops.label_ce_bwd_lowres(d['zq'], size, labels, w, acc, torch.tensor([16.0]).cuda(), invT, mode, th, want_fix=True)
+        assert took_the_direct_path(acc.cpu(), fix.cpu()), mode
+
+
 def test_bad_arguments_launch_nothing():
     ops = _gpu()
     from mulactseg_amd._lib import MulActSegHipError

@@ -13,6 +13,7 @@ import torch
 
 import online_plbl_restated as R
 from test_online_plbl_gpu import N_CLS, TH_, TS, TW_, _Train, _Val
+from test_online_plbl_gpu import off_ratio_case, took_the_direct_path, uint16_edge_case
 from test_simw_plbl_cpu import METHODS, _host_labels, _host_soft, golden, golden_inputs, negated_tensors, tensors
 
 pytestmark = pytest.mark.gpu
@@ -93,6 +94,30 @@ def test_kernels_equal_the_host_loops_on_other_paths(c, ch, h, w, s):
     case = dict(zip(('zq_p', 'featq', 'zq', 'tgt', 'spx', 'msk'), R.inputs(31 + c, 2, c, ch, h, w, R.quarter(h), R.quarter(w), s, frac=0.6)))
     labelled, _, counted = _bit_for_bit(ops, tensors(case), (h, w))
     assert labelled > 0 and counted >= labelled
+
+
+def test_kernels_equal_the_host_loops_with_uint16_ids():
+    """the third instantiation of both per-pixel kernels and the uint16 read of the soft CE, never run by the other cases"""
+    ops = _gpu()
+    e, t = uint16_edge_case()
+    labelled, negative, counted = _bit_for_bit(ops, t, e['size'], id_types=(torch.uint16,))
+    assert labelled > 500 and negative >= 1 and counted == 2293
+
+
+def test_kernels_equal_the_host_loops_off_the_x4_ratio():
+    """``off_ratio_case``: the signed, weighted and threshold label CE and the soft CE at both temperatures"""
+    ops = _gpu()
+    t, size = off_ratio_case()
+    labelled, _, counted = _bit_for_bit(ops, t, size)
+    assert labelled > 0 and counted >= labelled
+    # the soft CE once more, to see on the device's own output that the taps outside the image were there
+    invT, d = ops.inv_temperature(R.T), {k: v.cuda() for k, v in t.items()}
+    softw, live, bits = ops.online_soft_weights(d['zq_p'], d['featq'], size, d['spx'], d['msk'], targets=d['tgt'], invT=invT,
+                                                inv_tau=ops.inv_temperature(TAUS[0]))
+    mask = d['msk'].view(torch.uint8) if d['msk'].dtype == torch.bool else d['msk']
+    _, acc = ops.soft_ce_fwd_lowres(d['zq'], size, d['spx'], mask, bits, softw, live, invT)
+    _, fix = ops.soft_ce_bwd_lowres(d['zq'], size, d['spx'], mask, bits, softw, live, acc, torch.tensor([16.0]).cuda(), invT, want_fix=True)
+    assert took_the_direct_path(acc.cpu(), fix.cpu())
 
 
 def test_kernels_equal_the_host_loop_when_every_weight_off_the_prototypes_is_negative():
