@@ -349,3 +349,165 @@ def write_voc_tree(root, n=4, nseg=150, seed=0, trim=5, sizes=((120, 160), (150,
         json.dump(region, f)
     out['multi_hot'] = mh
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# float32 rounding bounds for the head / 1x1 / dense-small kernel tests (test_head_gpu.py, test_conv1x1_gpu.py,
+# test_kernel_bounds_cpu.py): inputs, float64 references and per-element worst-case bounds, shared by the GPU tests and
+# by the CPU proof that a correct float32 evaluation passes them and a wrong one does not
+# ---------------------------------------------------------------------------------------------------------------------------
+U32 = 2.0 ** -24                    # unit roundoff of float32: one correctly rounded operation errs by at most U32 * |result|
+COSINE_EPS = float(np.float32(1e-12))          # the clamp as the kernel receives it (a C float)
+
+
+def rounding_bound(*parts):
+    """``2^-24 * sum_i c_i * A_i``: ``A_i`` the float64 sum of the absolute values of a group of terms an element adds up, ``c_i`` the
+    length of the longest chain of float32 roundings between those terms and the stored element."""
+    return U32 * sum(float(c) * A for c, A in parts)
+
+
+def bound_ratio(got, ref, bound):
+    """|got - ref| / bound per element; where the bound is 0 (every term is 0) only an exact result passes; NaN counts as inf."""
+    err = (got.double() - ref).abs()
+    exact0 = torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, float('inf')))
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), exact0)
+    return torch.nan_to_num(ratio, nan=float('inf'), posinf=float('inf'))
+
+
+def assert_within(got, ref, bound, what):
+    """Prints the largest error / bound (the margin a run leaves) and asserts that no element exceeds its bound."""
+    ratio = bound_ratio(got.detach().cpu(), ref, bound)
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    print("error/bound %-34s max %.4f" % (what, worst))
+    assert worst <= 1.0, "%s: %d of %d elements beyond their rounding bound, worst error / bound = %g" % (
+        what, int((ratio > 1.0).sum()), ratio.numel(), worst)
+    return worst
+
+
+# ---- cosine classifier ------------------------------------------------------------------------------------------------------
+# (N, Ch, H, W, K, forward kernel, backward kernel, feat at an element offset of 1): every K on every kernel at least once
+HEAD_CASES = [
+    (2, 40, 36, 40, 19, 'fwd4<8>', 'bwd4', False), (2, 40, 36, 40, 20, 'fwd4<8>', 'bwd4', False), (2, 40, 36, 40, 21, 'fwd4<8>', 'bwd4', False),
+    (2, 36, 36, 40, 19, 'fwd4<4>', 'bwd4', False), (2, 36, 36, 40, 20, 'fwd4<4>', 'bwd4', False), (2, 36, 36, 40, 21, 'fwd4<4>', 'bwd4', False),
+    (2, 34, 36, 40, 21, 'fwd', 'bwd4', False), (2, 35, 36, 40, 19, 'fwd', 'bwd4', False),
+    (1, 33, 9, 31, 20, 'fwd', 'bwd', False), (1, 33, 9, 31, 19, 'fwd', 'bwd', False),
+    (1, 1, 2, 2, 21, 'fwd', 'bwd4', False),
+    (1, 40, 36, 40, 21, 'fwd', 'bwd', True), (1, 40, 36, 40, 20, 'fwd', 'bwd', True),
+]
+
+
+def head_paths(Ch, HW, aligned):
+    """The launchers' predicates (csrc/head.hip launch_fwd / launch_bwd) restated: which kernels a shape and alignment select."""
+    fwd = ('fwd4<8>' if Ch % 8 == 0 else 'fwd4<4>') if (HW % 4 == 0 and Ch % 4 == 0 and aligned) else 'fwd'
+    return fwd, ('bwd4' if (HW % 4 == 0 and aligned) else 'bwd')
+
+
+def head_inputs(N, Ch, H, W, K):
+    """(feat [N,Ch,H,W], phat [K,Ch] unit rows in float32, g [N,K,H,W]) with the planted pixels: a zero vector on the first pixel of
+    the first image and on the last pixel of the last one, |f| ~ 1e-20 (squares are denormal: the eps clamp) on pixel 1, and on pixel 2
+    a multiple of proxy 0 (cosine 1: a logit whose terms all have one sign); the gradient of the first pixel has the signs of the
+    proxies' channel 0, so that one feature gradient is a sum of terms of one sign as well."""
+    gen = torch.Generator().manual_seed(100000 * N + 1000 * Ch + 10 * K + H)
+    f = torch.randn((N, Ch, H, W), generator=gen)
+    phat = torch.nn.functional.normalize(torch.randn((K, Ch), generator=gen), dim=1)
+    g = torch.randn((N, K, H, W), generator=gen)
+    ff = f.view(N, Ch, H * W)
+    ff[0, :, 0] = 0.0
+    ff[N - 1, :, H * W - 1] = 0.0
+    ff[0, :, 1] = torch.randn(Ch, generator=gen).sign() * (1e-20 / Ch ** 0.5)
+    ff[0, :, 2] = 3.0 * phat[0]
+    gg = g.view(N, K, H * W)
+    gg[0, :, 0] = gg[0, :, 0].abs() * torch.where(phat[:, 0] < 0, -1.0, 1.0)       # d/df_0 on the first pixel: terms of one sign too
+    return f, phat, g
+
+
+def head_reference(f, phat, g):
+    """float64 evaluation of the kernels' formulas on float32 inputs, with the bounds.
+
+    logit_k = sum_c f_c p_kc / n,  n = max(|f|, eps);  dfeat_c = (sum_k g_k p_kc - (sum_k g_k logit_k) f_c / n) / n.
+
+    Chains of float32 roundings (k_cosine_fwd / k_cosine_bwd and their 4-pixel forms, same operations in the same order):
+      logit:  Ch fma steps (the dot product; |f|^2 is a parallel chain of the same length), sqrt, 1/n, the product  -> c = Ch + 3
+              over A = sum_c |f_c p_kc| / n.  (Adding the two parallel chains instead of taking the longer one would give 1.5 Ch + 3.)
+      dfeat:  two groups of terms.  A1 = sum_k |g_k p_kc| / n: K fma steps, the subtraction and the product by 1/n, or Ch + 3 through
+              1/n itself, whichever is longer -> c1 = max(K + 2, Ch + 3).  A2 = sum_k |g_k| (sum_c' |f_c' p_kc'| / n) |f_c| / n^2 (the
+              second sum expanded to the products the kernel adds, because the float32 logits carry their own error):
+              Ch + 3 roundings in the logit, K fma steps, s / n, times f_c, the subtraction, the product -> c2 = Ch + K + 7.
+    Returns a dict of float64 tensors shaped like the kernel's outputs."""
+    N, Ch, H, W = f.shape
+    K = phat.shape[0]
+    fd, pd, gd = f.double().reshape(N, Ch, H * W), phat.double(), g.double().reshape(N, K, H * W)
+    n = fd.pow(2).sum(1).sqrt().clamp_min(COSINE_EPS)[:, None]                     # [N,1,HW]
+    logits = torch.einsum('nch,kc->nkh', fd, pd) / n
+    A_logit = torch.einsum('nch,kc->nkh', fd.abs(), pd.abs()) / n
+    s = (gd * logits).sum(1, keepdim=True)
+    df = (torch.einsum('nkh,kc->nch', gd, pd) - s * fd / n) / n
+    A1 = torch.einsum('nkh,kc->nch', gd.abs(), pd.abs()) / n
+    A2 = (gd.abs() * A_logit).sum(1, keepdim=True) * fd.abs() / (n * n)
+    return {'n': n.reshape(N, H, W), 'zero': (fd.abs().sum(1) == 0).reshape(N, H, W),
+            'logits': logits.reshape(N, K, H, W), 'logits_bound': rounding_bound((Ch + 3, A_logit)).reshape(N, K, H, W),
+            'dfeat': df.reshape(N, Ch, H, W), 'dfeat_bound': rounding_bound((max(K + 2, Ch + 3), A1), (Ch + K + 7, A2)).reshape(N, Ch, H, W),
+            # a zero feature vector as the kernel documents it: n = eps, dfeat_c = (sum_k g_k p_kc) / eps; K fma steps, 1/eps, the
+            # subtraction of an exact 0 and the product -> c = K + 3
+            'dfeat_zero': (torch.einsum('nkh,kc->nch', gd, pd) / COSINE_EPS).reshape(N, Ch, H, W),
+            'dfeat_zero_bound': rounding_bound((K + 3, torch.einsum('nkh,kc->nch', gd.abs(), pd.abs()) / COSINE_EPS)).reshape(N, Ch, H, W)}
+
+
+# ---- dense small: y = x w^T, dx = dy w, dw = dy^T x ---------------------------------------------------------------------------
+DENSE_CASES = [(4, 2048, 256), (3, 70, 13), (1, 1, 1), (5, 300, 7)]
+
+
+def dense_inputs(N, K, M):
+    """x [N,K], w [M,K], dy [N,M]; row 0 of x carries the signs of row 0 of w: y[0,0] is a sum of terms of one sign."""
+    gen = torch.Generator().manual_seed(10000 * N + 10 * K + M)
+    x, w, dy = torch.randn((N, K), generator=gen), torch.randn((M, K), generator=gen) / K ** 0.5, torch.randn((N, M), generator=gen)
+    x[0] = x[0].abs() * torch.where(w[0] < 0, -1.0, 1.0)
+    return x, w, dy
+
+
+def dense_reference(x, w, dy):
+    """float64 products and bounds.  k_dense_fwd: a lane adds every 64th product with fma (ceil(K / 64) roundings), then six butterfly
+    additions -> c = ceil(K / 64) + 6 over A = sum_k |x_k w_k|.  k_dense_bwd_x: M fma steps in order -> c = M over sum_m |dy_m w_mk|.
+    k_dense_bwd_w: N fma steps -> c = N over sum_n |dy_nm x_nk|."""
+    (N, K), M = x.shape, w.shape[0]
+    xd, wd, gd = x.double(), w.double(), dy.double()
+    return {'y': xd @ wd.t(), 'y_bound': rounding_bound(((K + 63) // 64 + 6, xd.abs() @ wd.abs().t())),
+            'dx': gd @ wd, 'dx_bound': rounding_bound((M, gd.abs() @ wd.abs())),
+            'dw': gd.t() @ xd, 'dw_bound': rounding_bound((N, gd.abs().t() @ xd.abs()))}
+
+
+# ---- 1x1 convolution with the folded BatchNorm / residual / ReLU epilogue -----------------------------------------------------------
+# (N, K, M, H, W, residual, relu, epilogue)
+CONV1X1_CASES = [(2, 8, 64, 36, 40, True, False, True), (1, 8, 32, 4, 2305, False, True, True), (1, 4, 64, 4, 2048, True, True, True),
+                 (2, 12, 32, 1, 4, False, False, True), (1, 8, 64, 36, 40, False, False, False)]
+
+
+def conv1x1_tiles(M, HW):
+    """(ptiles, mtiles) of mas_conv1x1_fwd: pixel tiles of 256 lanes x 4 pixels, output-channel tiles of 32."""
+    return (HW + 1023) // 1024, M // 32
+
+
+def conv1x1_inputs(N, K, M, H, W, res):
+    """x, the [M,K] weight, BatchNorm (weight, bias, running_mean, running_var), residual or None."""
+    gen = torch.Generator().manual_seed(1000 * K + 10 * M + N + H)
+    x = torch.randn((N, K, H, W), generator=gen)
+    w = torch.randn((M, K), generator=gen)
+    bn = (torch.rand(M, generator=gen) + 0.5, torch.randn(M, generator=gen), torch.randn(M, generator=gen), torch.rand(M, generator=gen) + 0.3)
+    return x, w, bn, (torch.randn((N, M, H, W), generator=gen) if res else None)
+
+
+def conv1x1_reference(x, w, scale, shift, res, relu):
+    """float64 relu?(scale * sum_k x_k w_mk + shift + res) on float32 inputs (scale / shift None: the bare sum) and its bound:
+    K fma steps, the product by scale, the addition of shift, the addition of the residual -> c = K + 3 (K for the bare form) over
+    A = |scale| sum_k |x_k w_mk| + |shift| + |res|.  ReLU rounds nothing and cannot grow an error."""
+    N, K, H, W = x.shape
+    xd, wd = x.double().reshape(N, K, H * W), w.double()
+    y, A, c = torch.einsum('nkh,mk->nmh', xd, wd), torch.einsum('nkh,mk->nmh', xd.abs(), wd.abs()), K
+    if scale is not None:
+        s, t = scale.double()[None, :, None], shift.double()[None, :, None]
+        y, A, c = y * s + t, A * s.abs() + t.abs(), K + 3
+        if res is not None:
+            y, A = y + res.double().reshape(N, -1, H * W), A + res.double().abs().reshape(N, -1, H * W)
+        if relu:
+            y = y.clamp_min(0.0)
+    return y.reshape(N, -1, H, W), rounding_bound((c, A)).reshape(N, -1, H, W)
