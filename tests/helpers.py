@@ -511,3 +511,298 @@ def conv1x1_reference(x, w, scale, shift, res, relu):
         if relu:
             y = y.clamp_min(0.0)
     return y.reshape(N, -1, H, W), rounding_bound((c, A)).reshape(N, -1, H, W)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# BatchNorm + ReLU + residual (csrc/bn.hip): the launcher's group / chunk arithmetic restated, inputs, and float64 references
+# with per-element bounds, split in two so that every bound follows from the kernels' order of operations:
+#   (a) the statistics against float64 of the float32 input (bn_stats_reference),
+#   (b) the apply and backward kernels against float64 evaluations of their formulas with the float32 inputs and the DEVICE's
+#       float32 statistics taken as given (bn_apply_reference, bn_backward_reference).
+# test_bn_gpu.py uses them on the device's results, test_kernel_bounds_cpu.py on a float32 restatement in the kernels' order.
+# ---------------------------------------------------------------------------------------------------------------------------
+UD = 2.0 ** -53                     # unit roundoff of double
+BN_THREADS = 256
+BN_GROUPS_PER_CHUNK = 2048          # kChunk = 8192 elements of a plane per workgroup of the reduction kernels
+BN_UNROLL = 4                       # groups k_bn_bwd_partial keeps in flight per thread
+
+# (N, C, H, W) -> what the case is in the table for (bn_paths of the shape on a 16-byte aligned tensor must say exactly this).
+# chunks: reduction workgroups per plane; a: the misalignments its planes take; second: what chunk 1 holds, per misalignment
+# ('empty', 'boundary': one group that the plane covers in part, 'full': one group inside the plane); no_full: no plane has a whole
+# group; dup: some thread of k_bn_bwd_partial takes the clamped duplicate; two_trips: some thread runs its four-group loop twice.
+BN_CASES = [
+    ((2, 5, 1, 8193), dict(chunks=2, a={0, 1, 2, 3}, second={0: 'boundary', 1: 'boundary', 2: 'boundary', 3: 'full'}, no_full=False, dup=True, two_trips=True)),
+    ((2, 5, 1, 8191), dict(chunks=2, a={0, 1, 2, 3}, second={0: 'empty', 1: 'empty', 2: 'boundary', 3: 'boundary'}, no_full=False, dup=True, two_trips=True)),
+    ((2, 3, 64, 128), dict(chunks=2, a={0}, second={0: 'empty'}, no_full=False, dup=False, two_trips=True)),
+    ((1, 2, 1, 4100), dict(chunks=1, a={0}, second={}, no_full=False, dup=True, two_trips=True)),
+    ((1, 5, 33, 37), dict(chunks=1, a={0, 1, 2, 3}, second={}, no_full=False, dup=True, two_trips=False)),
+    ((3, 5, 1, 3), dict(chunks=1, a={0, 1, 2, 3}, second={}, no_full=True, dup=False, two_trips=False)),
+    ((2, 4, 1, 2), dict(chunks=1, a={0, 2}, second={}, no_full=True, dup=False, two_trips=False)),
+    ((4, 6, 1, 1), dict(chunks=1, a={0, 1, 2, 3}, second={}, no_full=True, dup=False, two_trips=False)),
+]
+BN_OPTION_CASES = [BN_CASES[0][0], BN_CASES[4][0], BN_CASES[5][0]]       # the cases every option runs on
+# one option at a time on top of relu + residual
+BN_OPTIONS = ['affine_false', 'no_running_stats', 'residual_no_grad', 'frozen_weight', 'frozen_bias', 'no_relu', 'momentum_0.01',
+              'momentum_1.0', 'eps_1e-3', 'two_steps']
+
+
+def bn_max_groups(HW):
+    return (HW + 3) // 4 + 1
+
+
+def bn_chunks(HW):
+    return (bn_max_groups(HW) + BN_GROUPS_PER_CHUNK - 1) // BN_GROUPS_PER_CHUNK
+
+
+def bn_plane_groups(a, HW, chunks):
+    """groups_of and the chunk loop of k_bn_partial / k_bn_bwd_partial for one plane at misalignment a: per chunk
+    (lo, hi, flo, fhi): groups [lo, hi) of the plane fall into the chunk, [flo, fhi) of them lie whole inside the plane."""
+    n = (a + HW + 3) >> 2
+    first_full, end_full = (a + 3) >> 2, (a + HW) >> 2
+    out = []
+    for k in range(chunks):
+        lo = k * BN_GROUPS_PER_CHUNK
+        hi = max(lo, min(n, lo + BN_GROUPS_PER_CHUNK))
+        flo, fhi = max(lo, first_full), min(hi, end_full)
+        out.append((lo, hi, flo, max(flo, fhi)))
+    return n, out
+
+
+def bn_paths(N, C, HW, offset=0):
+    """The predicates of BN_CASES for a contiguous [N,C,HW] tensor whose first element lies `offset` elements past a 16-byte boundary."""
+    chunks = bn_chunks(HW)
+    got = dict(chunks=chunks, a=set(), second={}, no_full=True, dup=False, two_trips=False, per_thread=0)
+    for p in range(N * C):
+        a = (offset + p * HW) & 3
+        got['a'].add(a)
+        n, per_chunk = bn_plane_groups(a, HW, chunks)
+        assert n <= bn_max_groups(HW)                                           # (the grid and the mask row cover every group)
+        for k, (lo, hi, flo, fhi) in enumerate(per_chunk):
+            full = fhi - flo
+            got['no_full'] &= full == 0
+            got['dup'] |= full % (BN_UNROLL * BN_THREADS) != 0
+            got['two_trips'] |= full > BN_UNROLL * BN_THREADS
+            got['per_thread'] = max(got['per_thread'], (hi - lo + BN_THREADS - 1) // BN_THREADS)
+            if k == 1:
+                what = 'empty' if hi == lo else ('full' if full == 1 else 'boundary')
+                assert hi - lo <= 1 and got['second'].get(a, what) == what
+                got['second'][a] = what
+    return got
+
+
+def bn_inputs(N, C, H, W, seed=0, const=None):
+    """x (mean 0.5, std 2; or the constant `const`), residual, upstream gradient, gamma, beta, running mean, running variance."""
+    gen = torch.Generator().manual_seed(100003 * N + 1009 * C + 31 * H + W + 7919 * seed)
+    shape = (N, C, H, W)
+    x = torch.randn(shape, generator=gen) * 2 + 0.5 if const is None else torch.full(shape, float(const))
+    return dict(x=x, res=torch.randn(shape, generator=gen), dy=torch.randn(shape, generator=gen), gamma=torch.rand(C, generator=gen) + 0.5,
+                beta=torch.randn(C, generator=gen) * 0.3, rm=torch.randn(C, generator=gen) * 0.1, rv=torch.rand(C, generator=gen) + 0.5)
+
+
+def bn_conditioning_input():
+    """[2,4,1,1221]: unit-variance channels with mean / std of 0, 1, 8 and 64."""
+    gen = torch.Generator().manual_seed(1221)
+    return torch.randn((2, 4, 1, 1221), generator=gen) + torch.tensor([0.0, 1.0, 8.0, 64.0]).view(1, 4, 1, 1)
+
+
+def f32_as_float(v):
+    """The double a C float parameter holds."""
+    return float(np.float32(v))
+
+
+def bn_stats_reference(x, eps, momentum=None, rm0=None, rv0=None, c_s=10, c_q=11, c_d=None):
+    """(a) mean, invstd and the updated running statistics of k_bn_partial + k_bn_stats in float64, with bounds.
+
+    The kernel: S = sum x, Q = sum x^2 per channel, m = S / n, var = max(Q / n - m^2, 0), invstd = 1 / sqrt(var + eps), all in double
+    from the per-thread float32 sums on.  A thread of k_bn_partial adds at most 8 groups per chunk (2048 groups, 256 threads), each
+    pre-summed in two levels, (x0 + x1) + (x2 + x3): 2 + 8 roundings on any element's way into S, c_s = 10 over mean|x|; one more for
+    the square on the way into Q, c_q = 11 over mean(x^2).  The double part (six shuffle steps, three adds over the waves, the
+    partials in index order: c_d = per_channel + 9 roundings of 2^-53) is carried as well.
+      mean:    dS + u |m|                                   (the cast)
+      var:     dvar = dQ + 2 |m| dS + dS^2                   (+ four double roundings of Q / n - m^2)
+      invstd:  the device's variance lies in [max(var - dvar, 0), var + dvar] and 1 / sqrt(. + eps) falls monotonically, so the error is at
+               most 1 / sqrt(max(var - dvar, 0) + eps) - invstd -- the factor dvar / (2 (var + eps)) with its whole remainder -- plus
+               the cast of a value no larger than that.
+      running: (1 - mom) r + mom m and (1 - mom) r + mom var n / (n - 1) in double: mom dS, mom n / (n - 1) dvar, plus the cast.
+    The bound on invstd is what the one-pass form can lose: dvar / var grows with (mean / std)^2 (test_bn_gpu.py: conditioning).
+    Other callers: c_s = c_q = 0 for partials that are exact (k_bn_stats_wide), c_d the double chain of that kernel."""
+    N, C = x.shape[:2]
+    xd = x.double().transpose(0, 1).reshape(C, -1)
+    n = xd.shape[1]
+    if c_d is None:
+        c_d = N * bn_chunks(n // N) + 9
+    m, A1, q = xd.mean(1), xd.abs().mean(1), (xd * xd).mean(1)
+    var = (xd - m[:, None]).pow(2).mean(1)
+    dS = (c_s * U32 + c_d * UD) * A1
+    dQ = (c_q * U32 + c_d * UD) * q
+    dvar = dQ + 2 * m.abs() * dS + dS * dS + 4 * UD * (q + m * m)
+    e = f32_as_float(eps)
+    invstd = (var + e).rsqrt()
+    worst = ((var - dvar).clamp_min(0.0) + e).rsqrt()
+    out = dict(mean=m, mean_bound=dS + U32 * m.abs(), var=var, dvar=dvar, invstd=invstd, invstd_bound=(worst - invstd) + (U32 + 3 * UD) * worst)
+    if momentum is not None:
+        mom = f32_as_float(momentum)
+        unb = n / (n - 1.0) if n > 1 else 1.0
+        rm = (1.0 - mom) * rm0.double() + mom * m
+        rv = (1.0 - mom) * rv0.double() + mom * var * unb
+        out.update(rm=rm, rm_bound=mom * dS + U32 * rm.abs() + 4 * UD * (rm0.double().abs() + m.abs()),
+                   rv=rv, rv_bound=mom * unb * dvar + U32 * rv.abs() + 4 * UD * (rv0.double().abs() + var * unb))
+    return out
+
+
+def _per_channel(t, C, default):
+    return torch.full((1, C, 1, 1), default, dtype=torch.float64) if t is None else t.detach().double().cpu().view(1, C, 1, 1)
+
+
+def bn_apply_reference(x, gamma, beta, res, stat1, stat2, relu, eps=None):
+    """(b) k_bn_apply: y = relu?(((x - mu) * is) * gamma + beta + res) in float64 on float32 operands.  Training (eps None): stat1 / stat2
+    are the device's float32 mean / invstd.  Five roundings (the subtraction, two products, two additions) over
+    A = |xhat gamma| + |beta| + |res|.  Inference: stat2 is the running variance, is = 1 / sqrtf(var + eps): three more roundings (the
+    addition, the square root, the division) on the first term.  ReLU rounds nothing and cannot grow an error.  -> (y, bound)"""
+    C = x.shape[1]
+    mu, gm, b = _per_channel(stat1, C, 0.0), _per_channel(gamma, C, 1.0), _per_channel(beta, C, 0.0)
+    if eps is None:
+        inv, extra = _per_channel(stat2, C, 0.0), 0
+    else:
+        inv, extra = (_per_channel(stat2, C, 0.0) + f32_as_float(eps)).rsqrt(), 3
+    t = (x.double() - mu) * inv * gm
+    r = torch.zeros_like(t) if res is None else res.double()
+    y = t + b + r
+    bound = U32 * (5 * (t.abs() + b.abs() + r.abs()) + extra * t.abs())
+    return (y.clamp_min(0.0) if relu else y), bound
+
+
+def bn_backward_reference(x, dy, y_dev, gamma, mean, invstd, relu, per_thread=8, per_channel=None):
+    """(b) k_bn_bwd_partial + k_bn_bwd_stats + k_bn_bwd_apply in float64 on float32 operands, the device's float32 mean / invstd / y:
+      g = dy [y > 0] (exact),  xhat = (x - mu) is,  dbeta = sum g,  dgamma = sum g xhat,
+      dx = k (g - mean g - xhat mean(g xhat)),  k = gamma is,  dres = g.
+    A thread adds the four elements of at most `per_thread` = 8 groups one after the other in float32: 32 additions; g xhat takes three
+    roundings first; the rest is double (c_d roundings of 2^-53) and one cast:  dbeta: 33 over sum|g|,  dgamma: 36 over sum|g xhat|.
+    dx: the two subtractions, the product by k and k's own rounding on every term, the subtraction and two products of xhat mean(g xhat)
+    on the last: 6 over |k| (|g| + |mean g| + |xhat mean(g xhat)|); the float32 coefficients mean g and mean(g xhat) carry the errors of
+    the sums divided by the count (their cast is the one counted in the sums' bounds): |k| (d_mg + |xhat| d_mgx) more.
+    -> dict(dres, dbeta, dbeta_bound, dgamma, dgamma_bound, dx, dx_bound)"""
+    N, C, H, W = x.shape
+    n = N * H * W
+    if per_channel is None:
+        per_channel = N * bn_chunks(H * W)
+    c_d = per_channel + 9
+    mu, inv, gm = _per_channel(mean, C, 0.0), _per_channel(invstd, C, 0.0), _per_channel(gamma, C, 1.0)
+    g32 = torch.where(y_dev.detach().cpu() > 0, dy, torch.zeros_like(dy)) if relu else dy
+    g = g32.double()
+    xhat = (x.double() - mu) * inv
+    red = lambda t: t.sum((0, 2, 3))
+    dbeta, dgamma = red(g), red(g * xhat)
+    dbeta_bound = ((4 * per_thread + 1) * U32 + c_d * UD) * red(g.abs())
+    dgamma_bound = ((4 * per_thread + 4) * U32 + c_d * UD) * red((g * xhat).abs())
+    v = lambda t: t.view(1, C, 1, 1)
+    mg, mgx, k = v(dbeta) / n, v(dgamma) / n, gm * inv
+    dx = k * (g - mg - xhat * mgx)
+    dx_bound = k.abs() * (6 * U32 * (g.abs() + mg.abs() + (xhat * mgx).abs()) + v(dbeta_bound) / n + xhat.abs() * v(dgamma_bound) / n)
+    return dict(dres=g32, dbeta=dbeta, dbeta_bound=dbeta_bound, dgamma=dgamma, dgamma_bound=dgamma_bound, dx=dx, dx_bound=dx_bound)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# bilinear upsampling (csrc/upsample.hip): make_tap restated in torch float32 operation by operation (nothing is contracted: the
+# same bits as the kernel's), the weights built from those taps, combined in float64
+# ---------------------------------------------------------------------------------------------------------------------------
+UPSAMPLE_MAX_TAPS = 16
+# (N, C, Hi, Wi, Ho, Wo) -> the kernel forms the case selects on 16-byte aligned tensors (upsample_paths must say exactly this).
+# fast4: k_upsample_bwd<true>; fast_cols: input columns that take its three-load form (the interior ones: 0 and Wi - 1 stay on the
+# tested loop); fwd_cols / bwd_cols: block columns of the forward (1024 outputs) and of the backward (64 inputs);
+# bwd_partial: the last backward block column is partial; vec_store: the forward stores float4; cols: the largest number of candidate
+# output columns of an input column (the tap limit Wo = 6 Wi fills all 16, the fractional 17 / 3 reaches 15; None: not what the case
+# is for); single: every tap has i1 == i0 (one input pixel)
+UPSAMPLE_CASES = [
+    ((1, 2, 2, 260, 8, 1040), dict(fast4=True, fast_cols=258, fwd_cols=2, bwd_cols=5, bwd_partial=True, vec_store=True, cols=12, single=False)),
+    ((1, 2, 3, 5, 12, 20), dict(fast4=True, fast_cols=3, fwd_cols=1, bwd_cols=1, bwd_partial=True, vec_store=True, cols=12, single=False)),
+    ((1, 1, 5, 13, 17, 49), dict(fast4=False, fast_cols=0, fwd_cols=1, bwd_cols=1, bwd_partial=True, vec_store=False, cols=None, single=False)),
+    ((1, 2, 4, 3, 4, 18), dict(fast4=False, fast_cols=0, fwd_cols=1, bwd_cols=1, bwd_partial=True, vec_store=False, cols=16, single=False)),
+    ((1, 2, 4, 3, 5, 17), dict(fast4=False, fast_cols=0, fwd_cols=1, bwd_cols=1, bwd_partial=True, vec_store=False, cols=15, single=False)),
+    ((1, 1, 1, 1, 3, 5), dict(fast4=False, fast_cols=0, fwd_cols=1, bwd_cols=1, bwd_partial=True, vec_store=False, cols=None, single=True)),
+    ((2, 3, 7, 5, 7, 5), dict(fast4=False, fast_cols=0, fwd_cols=1, bwd_cols=1, bwd_partial=True, vec_store=False, cols=None, single=False)),
+]
+
+
+def upsample_taps(n_in, n_out):
+    """make_tap(scale, o, n_in) for o = 0 .. n_out - 1 -> (i0, i1 int64, l0, l1 float32), scale = (float)n_in / (float)n_out."""
+    scale = torch.tensor(float(n_in), dtype=torch.float32) / torch.tensor(float(n_out), dtype=torch.float32)
+    s = scale * (torch.arange(n_out, dtype=torch.float32) + 0.5) - 0.5
+    s = torch.where(s < 0, torch.zeros_like(s), s)
+    i0 = s.to(torch.int64)
+    i1 = i0 + (i0 < n_in - 1).to(torch.int64)
+    l1 = s - i0.to(torch.float32)
+    return i0, i1, 1.0 - l1, l1
+
+
+def upsample_weights(n_in, n_out, dtype):
+    """[n_out, n_in]: row o holds l0 at i0 and l1 at i1, added where the two coincide -- in float64 (the forward adds the two products) or
+    in float32 (the backward adds the two weights in float32 before it uses them)."""
+    i0, i1, l0, l1 = upsample_taps(n_in, n_out)
+    w = torch.zeros((n_out, n_in), dtype=dtype)
+    o = torch.arange(n_out)
+    w[o, i0] += l0.to(dtype)
+    w[o, i1] += l1.to(dtype)
+    return w
+
+
+def upsample_out_range(n_in, n_out):
+    """out_range of k_upsample_bwd for every input index, in float32 as the kernel -> (lo, hi) int64 [n_in]."""
+    scale = torch.tensor(float(n_in), dtype=torch.float32) / torch.tensor(float(n_out), dtype=torch.float32)
+    inv = 1.0 / scale
+    i = torch.arange(n_in, dtype=torch.float32)
+    lo = torch.floor((i - 0.5) * inv - 0.5).to(torch.int64) - 1
+    hi = torch.ceil((i + 1.5) * inv - 0.5).to(torch.int64) + 1
+    return lo.clamp_min(0), hi.clamp_max(n_out - 1)
+
+
+def upsample_paths(Hi, Wi, Ho, Wo, gy_aligned=True):
+    """The launchers' and kernels' predicates restated.  Also asserts what the backward needs to be right at all: every output column
+    that carries weight for an input column is among its (at most 16) candidates, and every such row is in its row range."""
+    wx, wy = upsample_weights(Wi, Wo, torch.float32), upsample_weights(Hi, Ho, torch.float32)
+    xlo, xhi = upsample_out_range(Wi, Wo)
+    ylo, yhi = upsample_out_range(Hi, Ho)
+    ox, oy = torch.arange(Wo)[:, None], torch.arange(Ho)[:, None]
+    assert bool(((wx == 0) | ((ox >= xlo[None]) & (ox <= torch.minimum(xhi, xlo + UPSAMPLE_MAX_TAPS - 1)[None]))).all())
+    assert bool(((wy == 0) | ((oy >= ylo[None]) & (oy <= yhi[None]))).all())
+    i0, i1, _, _ = upsample_taps(Wi, Wo)
+    j0, j1, _, _ = upsample_taps(Hi, Ho)
+    cols = (torch.minimum(xhi, xlo + UPSAMPLE_MAX_TAPS - 1) - xlo + 1)
+    fast4 = Wo == 4 * Wi and gy_aligned
+    ix = torch.arange(Wi)
+    fast = (ix >= 1) & (ix + 2 <= Wi) & (xlo == 4 * ix - 4)
+    if fast4:       # what the three loads stand for: exactly the candidates 2 .. 9 carry weight
+        k = torch.arange(UPSAMPLE_MAX_TAPS)[:, None]
+        w = torch.where(xlo[None] + k <= xhi[None], wx[(xlo[None] + k).clamp_max(Wo - 1), ix[None]], torch.zeros(()))
+        assert bool((((w != 0) == ((k >= 2) & (k <= 9))) | ~fast[None]).all())
+    return dict(fast4=fast4, fast_cols=int(fast.sum()) if fast4 else 0, fwd_cols=(Wo + 1023) // 1024, bwd_cols=(Wi + 63) // 64, bwd_partial=Wi % 64 != 0,
+                vec_store=Wo % 4 == 0, cols=int(cols.max()), single=bool((i0 == i1).all() and (j0 == j1).all()),
+                col_count=cols, row_count=(wy != 0).sum(0))
+
+
+def upsample_reference(x, Ho, Wo):
+    """y = Wy x Wx^T in float64 from the float32 taps; k_upsample_fwd computes l0h (l0w v00 + l1w v01) + l1h (l0w v10 + l1w v11) with
+    every operation rounded: a product, the inner addition, the product by the row weight, the outer addition -> c = 4 over
+    A = sum w |v|."""
+    Hi, Wi = x.shape[2:]
+    wy, wx = upsample_weights(Hi, Ho, torch.float64), upsample_weights(Wi, Wo, torch.float64)
+    f = lambda t: torch.einsum('oh,nchw,pw->ncop', wy, t, wx)
+    return f(x.double()), rounding_bound((4, f(x.double().abs())))
+
+
+def upsample_backward_reference(g, Hi, Wi):
+    """gx = Wy^T g Wx in float64 from the float32 weights of k_upsample_bwd (the forward's, transposed; where a tap's two indices
+    coincide the kernel adds l0 + l1 in float32, as upsample_weights does).  An input pixel adds, with fma, one term per candidate column
+    into a row sum (zero weights skipped or, on the x4 form, absent) and one row sum per contributing row: c = candidate columns +
+    contributing rows over A = sum w |g|."""
+    Ho, Wo = g.shape[2:]
+    wy, wx = upsample_weights(Hi, Ho, torch.float32).double(), upsample_weights(Wi, Wo, torch.float32).double()
+    p = upsample_paths(Hi, Wi, Ho, Wo)
+    c = (p['row_count'][:, None] + p['col_count'][None, :]).double()
+    f = lambda t: torch.einsum('oh,ncop,pw->nchw', wy, t, wx)
+    return f(g.double()), U32 * c[None, None] * f(g.double().abs())
+
+
+def upsample_inputs(N, C, Hi, Wi, Ho, Wo):
+    gen = torch.Generator().manual_seed(100003 * Hi + 1009 * Wi + 31 * Ho + Wo)
+    return torch.randn((N, C, Hi, Wi), generator=gen), torch.randn((N, C, Ho, Wo), generator=gen)

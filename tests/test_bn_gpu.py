@@ -1,11 +1,21 @@
 """csrc/bn.hip (BatchNorm2d + ReLU + residual add, fused) against torch.nn.BatchNorm2d on the CPU in float64:
-forward, running statistics, all gradients, inference mode, determinism; model-level parity and a training step."""
+forward, running statistics, all gradients, inference mode, determinism; model-level parity and a training step.
+
+Second half: every kernel of the file element by element within derived float32 bounds (tests/helpers.py, proved on the CPU by
+tests/test_kernel_bounds_cpu.py), in two steps -- (a) the device's own mean / invstd / running statistics against float64 of the
+float32 input, (b) y, dx, dres, dgamma, dbeta against float64 evaluations of the kernels' formulas that take the device's float32
+statistics as given -- on a table of shapes that reaches every chunk, boundary-group and loop form of the launchers, each case
+asserting the restated launcher arithmetic it is in the table for."""
 import copy
+import functools
+import math
 
 import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+import helpers as hp
 
 pytestmark = pytest.mark.gpu
 
@@ -160,7 +170,10 @@ def test_last_block_statistics_equal_the_separate_launch_bit_for_bit():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     from mulactseg_amd import ops
-    for (N, C, H, W, res) in ((4, 64, 48, 48, False), (2, 256, 49, 49, True), (4, 128, 97, 33, True), (1, 20, 5, 7, False), (4, 2048, 12, 12, False)):
+    for (N, C, H, W, res) in ((4, 64, 48, 48, False), (2, 256, 49, 49, True), (4, 128, 97, 33, True), (1, 20, 5, 7, False), (4, 2048, 12, 12, False),
+                            # a chunk with one boundary group / one whole group, an empty chunk on every plane (it counts towards per_channel),
+                            # planes without a whole group (helpers.BN_CASES 1, 3, 6)
+                            (2, 5, 1, 8193, True), (2, 3, 64, 128, True), (3, 5, 1, 3, True)):
         torch.manual_seed(N * C + H)
         x = torch.randn(N, C, H, W, device='cuda') * 2.0 + 0.3
         r = torch.randn(N, C, H, W, device='cuda') if res else None
@@ -190,3 +203,292 @@ def test_last_block_statistics_equal_the_separate_launch_bit_for_bit():
         assert int(outs["on"][6]) == 1
     key = (torch.device('cuda', torch.cuda.current_device()), torch.cuda.current_stream().cuda_stream)
     assert int(ops._BN_COUNTERS[key].abs().sum()) == 0
+
+
+# ---- every kernel of bn.hip, element by element, within derived bounds ---------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _bn_case(shape, seed=0, const=None):
+    """Inputs of one shape: made once, shared by the tests, never written to."""
+    return hp.bn_inputs(*shape, seed=seed, const=const)
+
+
+def _offset_view(t):
+    """A contiguous copy of ``t`` one element into a larger buffer: its address is 4 modulo 16."""
+    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device='cuda')
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v
+
+
+def _module(t, affine=True, track=True, momentum=0.1, eps=1e-5, freeze=()):
+    C = t['gamma'].numel()
+    bn = nn.BatchNorm2d(C, eps=eps, momentum=momentum, affine=affine, track_running_stats=track)
+    with torch.no_grad():
+        if affine:
+            bn.weight.copy_(t['gamma']); bn.bias.copy_(t['beta'])
+        if track:
+            bn.running_mean.copy_(t['rm']); bn.running_var.copy_(t['rv'])
+    for name in freeze:
+        getattr(bn, name).requires_grad_(False)
+    return bn.cuda().train()
+
+
+def _run_bn(bn, t, relu=True, res_grad=True, dy=None, partials=None):
+    """One forward / backward of ops.bn_act on aligned device copies of t (dy: a device tensor to use as the upstream gradient).
+    -> the outputs, the statistics the forward saved for the backward, and the running statistics before and after."""
+    from mulactseg_amd import ops
+    xd, rd = t['x'].cuda().requires_grad_(True), t['res'].cuda().requires_grad_(res_grad)
+    dyd = t['dy'].cuda() if dy is None else dy
+    before = (bn.running_mean.clone().cpu(), bn.running_var.clone().cpu()) if bn.track_running_stats else (None, None)
+    assert ops.bn_act_supported(bn, xd, rd)
+    y = ops.bn_act(bn, xd, relu, rd, partials=partials)
+    saved = y.grad_fn.saved_tensors
+    assert all(v.data_ptr() % 16 == 0 for v in (xd, rd, y))                    # the forward takes the float4 form
+    y.backward(dyd)
+    assert xd.grad.data_ptr() % 16 == 0
+    return dict(x=xd.detach(), y=y.detach(), mean=saved[3].clone(), invstd=saved[4].clone(), mask=saved[5], dx=xd.grad, dres=rd.grad,
+                dgamma=None if bn.weight is None else bn.weight.grad, dbeta=None if bn.bias is None else bn.bias.grad, rm0=before[0], rv0=before[1],
+                rm=bn.running_mean.clone() if bn.track_running_stats else None, rv=bn.running_var.clone() if bn.track_running_stats else None,
+                nbt=int(bn.num_batches_tracked) if bn.track_running_stats else None)
+
+
+def _check_stats(t, out, bn, what, **chain):
+    """(a) the device's statistics against float64 of the float32 input."""
+    ref = hp.bn_stats_reference(t['x'], bn.eps, bn.momentum, out['rm0'], out['rv0'], **chain) if bn.track_running_stats else \
+        hp.bn_stats_reference(t['x'], bn.eps, **chain)
+    hp.assert_within(out['mean'], ref['mean'], ref['mean_bound'], "bn mean " + what)
+    hp.assert_within(out['invstd'], ref['invstd'], ref['invstd_bound'], "bn invstd " + what)
+    if bn.track_running_stats:
+        hp.assert_within(out['rm'], ref['rm'], ref['rm_bound'], "bn running_mean " + what)
+        hp.assert_within(out['rv'], ref['rv'], ref['rv_bound'], "bn running_var " + what)
+    return ref
+
+
+def _check_apply_and_backward(t, out, bn, what, relu=True, res_grad=True):
+    """(b) y, dres (exact), dbeta, dgamma, dx against the kernels' formulas on the device's float32 statistics."""
+    gamma, beta = (t['gamma'], t['beta']) if bn.affine else (None, None)
+    mean, invstd = out['mean'].cpu(), out['invstd'].cpu()
+    y = out['y'].cpu()
+    yr, yb = hp.bn_apply_reference(t['x'], gamma, beta, t['res'], mean, invstd, relu)
+    hp.assert_within(y, yr, yb, "bn y " + what)
+    if relu:
+        assert bool((y >= 0).all()) and not bool(torch.signbit(y).any())       # exact zeros, none of them negative
+        assert out['mask'] is not None
+    ref = hp.bn_backward_reference(t['x'], t['dy'], y, gamma, mean, invstd, relu)
+    if res_grad:
+        assert torch.equal(out['dres'].cpu(), ref['dres']), "dres is not dy * [y > 0] bit for bit"
+    else:
+        assert out['dres'] is None
+    hp.assert_within(out['dx'], ref['dx'], ref['dx_bound'], "bn dx " + what)
+    for name, p in (('dgamma', 'weight'), ('dbeta', 'bias')):
+        if bn.affine and getattr(bn, p).requires_grad:
+            hp.assert_within(out[name], ref[name], ref[name + '_bound'], "bn %s %s" % (name, what))
+        else:
+            assert out[name] is None
+    return ref
+
+
+def _paths_on_device(shape, out):
+    N, C, H, W = shape
+    return hp.bn_paths(N, C, H * W, offset=(out['x'].data_ptr() // 4) % 4)
+
+
+@pytest.mark.parametrize("shape,expect", hp.BN_CASES)
+def test_every_chunk_and_group_form(shape, expect):
+    """relu + residual on the case table: chunk edges (a second chunk that is empty, holds one boundary group, holds one whole
+    group), every misalignment, two trips through the four-group loop of k_bn_bwd_partial, its clamped duplicate, planes without a whole
+    group, one-element planes.  The same bits twice."""
+    _gpu()
+    t = _bn_case(shape)
+    bn = _module(t)
+    out = _run_bn(bn, t)
+    got = _paths_on_device(shape, out)
+    assert got.pop('per_thread') <= 8 and got == expect
+    what = "%dx%dx%dx%d" % shape
+    _check_stats(t, out, bn, what)
+    _check_apply_and_backward(t, out, bn, what)
+    assert out['nbt'] == 1
+    again = _run_bn(_module(t), t)
+    for name in ('y', 'mean', 'invstd', 'dx', 'dres', 'dgamma', 'dbeta', 'rm', 'rv'):
+        assert torch.equal(out[name], again[name]), name
+
+
+@pytest.mark.parametrize("option", hp.BN_OPTIONS)
+@pytest.mark.parametrize("shape", hp.BN_OPTION_CASES)
+def test_options_one_at_a_time(shape, option):
+    """Null gamma / beta, null running pointers, dres / dgamma / dbeta not asked for, no ReLU under a residual, other momenta and eps, a
+    second step on the same module -- each on a two-chunk case, on odd planes and on planes without a whole group."""
+    _gpu()
+    t = _bn_case(shape)
+    kw, relu, res_grad = {}, True, True
+    if option == 'affine_false':
+        kw['affine'] = False
+    elif option == 'no_running_stats':
+        kw['track'] = False
+    elif option == 'residual_no_grad':
+        res_grad = False
+    elif option == 'frozen_weight':
+        kw['freeze'] = ('weight',)
+    elif option == 'frozen_bias':
+        kw['freeze'] = ('bias',)
+    elif option == 'no_relu':
+        relu = False
+    elif option.startswith('momentum_'):
+        kw['momentum'] = float(option.split('_')[1])
+    elif option == 'eps_1e-3':
+        kw['eps'] = 1e-3
+    bn = _module(t, **kw)
+    what = "%dx%dx%dx%d %s" % (shape + (option,))
+    out = _run_bn(bn, t, relu=relu, res_grad=res_grad)
+    _check_stats(t, out, bn, what)
+    _check_apply_and_backward(t, out, bn, what, relu=relu, res_grad=res_grad)
+    if option == 'no_relu':
+        assert out['mask'] is None and bool((out['y'] < 0).any())
+    if option == 'no_running_stats':
+        assert bn.running_mean is None and out['nbt'] is None
+    else:
+        assert out['nbt'] == 1
+    if option == 'two_steps':
+        # the second step starts from the running statistics the first one left on the device (taken as given) and counts to 2
+        t2 = dict(_bn_case(shape, seed=1), gamma=t['gamma'], beta=t['beta'])          # (the module keeps its parameters)
+        bn.zero_grad(set_to_none=True)
+        out2 = _run_bn(bn, t2)
+        assert torch.equal(out2['rm0'], out['rm'].cpu()) and torch.equal(out2['rv0'], out['rv'].cpu())
+        assert not torch.equal(out2['rm'], out['rm']) and not torch.equal(out2['rv'], out['rv'])
+        _check_stats(t2, out2, bn, what + " step 2")
+        _check_apply_and_backward(t2, out2, bn, what + " step 2")
+        assert out2['nbt'] == 2
+
+
+@pytest.mark.parametrize("shape", hp.BN_OPTION_CASES)
+def test_forward_vectorised_backward_not(shape):
+    """The upstream gradient is a contiguous view one element off a 16-byte boundary: k_bn_apply ran on float4 groups, k_bn_bwd_partial /
+    k_bn_bwd_apply fall back to the element path (not congruent with x).  Within the bounds of (b), which do not depend on the
+    partition of the sums; dres, which has no sum in it, equals the aligned run bit for bit."""
+    _gpu()
+    t = _bn_case(shape)
+    bn = _module(t)
+    dy = _offset_view(t['dy'].cuda())
+    out = _run_bn(bn, t, dy=dy)
+    assert (out['x'].data_ptr() ^ dy.data_ptr()) & 15 != 0                        # congruent(x, dy) of the launcher is false
+    _check_apply_and_backward(t, out, bn, "%dx%dx%dx%d dy at +1" % shape)
+    aligned = _run_bn(_module(t), t)
+    assert torch.equal(out['y'], aligned['y']) and torch.equal(out['dres'], aligned['dres'])
+
+
+def _bwd_direct(t, fwd, y, shape):
+    """mas_bn_act_train_bwd through the C ABI with relu_mask = NULL: the gate is read from y."""
+    from mulactseg_amd import _lib, ops
+    N, C, H, W = shape
+    lib = _lib.load()
+    xd, dyd, gm = fwd['x'], t['dy'].cuda(), t['gamma'].cuda()
+    ws = torch.empty(int(lib.mas_bn_workspace_bytes(N, C, H * W)), dtype=torch.uint8, device='cuda')
+    dx, dres = torch.full_like(xd, float('nan')), torch.full_like(xd, float('nan'))
+    dg, db = torch.full((C,), float('nan'), device='cuda'), torch.full((C,), float('nan'), device='cuda')
+    assert all(v.data_ptr() % 16 == 0 for v in (xd, dyd, dx, dres))
+    _lib.check(lib.mas_bn_act_train_bwd(dyd.data_ptr(), xd.data_ptr(), y.data_ptr(), None, gm.data_ptr(), fwd['mean'].data_ptr(),
+                                        fwd['invstd'].data_ptr(), N, C, H * W, 1, ws.data_ptr(), dx.data_ptr(), dres.data_ptr(), dg.data_ptr(),
+                                        db.data_ptr(), None, ops._stream(xd)), "mas_bn_act_train_bwd")
+    torch.cuda.synchronize()
+    return dict(dx=dx, dres=dres, dgamma=dg, dbeta=db)
+
+
+@pytest.mark.parametrize("shape,expect", [hp.BN_CASES[0], hp.BN_CASES[5]])
+def test_backward_gated_by_y_equals_the_mask_gated_backward(shape, expect):
+    """The ReLU gate read from y (relu_mask = NULL: part of the C ABI, never taken by ops.py) against the gate read from the mask: the
+    same gate, so every output has the same bits as the mask-gated launch OF THE SAME FORM.  y congruent with x: the float4 form, against
+    the aligned autograd run.  y one element off: the element form, against the mask-gated element form (upstream gradient one element
+    off).  The two forms hand the groups to the threads differently when a plane is misaligned (from flo / from lo), so their sums
+    may differ in the last bit -- except where no plane has a whole group, where they are one partition; dres, which has no sum in
+    it, agrees across the forms everywhere."""
+    _gpu()
+    t = _bn_case(shape)
+    vec = _run_bn(_module(t), t)
+    elem = _run_bn(_module(t), t, dy=_offset_view(t['dy'].cuda()))
+    assert vec['mask'] is not None
+    by_y = _bwd_direct(t, vec, vec['y'], shape)
+    y_off = _offset_view(vec['y'])
+    assert (vec['x'].data_ptr() ^ y_off.data_ptr()) & 15 != 0
+    by_y_elem = _bwd_direct(t, vec, y_off, shape)
+    for name in ('dx', 'dres', 'dgamma', 'dbeta'):
+        assert torch.equal(by_y[name], vec[name]), "float4 form, %s" % name
+        assert torch.equal(by_y_elem[name], elem[name]), "element form, %s" % name
+        if expect['no_full']:
+            assert torch.equal(by_y_elem[name], vec[name]), "both forms, %s" % name
+    assert torch.equal(by_y_elem['dres'], vec['dres'])
+
+
+@pytest.mark.parametrize("per_channel", [1, 255, 256, 257, 1000])
+def test_statistics_from_exact_partials(per_channel):
+    """k_bn_stats_wide: bn_act(partials=) with float64 partial sums of disjoint pixel sets (pixel j of a channel in set j % per_channel;
+    sets beyond the 640 pixels are empty), around the 256-way stride.  The partials are exact to double rounding, so the statistics err
+    only by their final casts: the bounds of (a) with no float32 chain."""
+    _gpu()
+    shape = (2, 3, 16, 20)
+    N, C, H, W = shape
+    t = _bn_case(shape)
+    xc = t['x'].double().transpose(0, 1).reshape(C, -1)
+    n = xc.shape[1]
+    sets = torch.arange(n) % per_channel
+    P = torch.zeros((C, per_channel, 2), dtype=torch.float64)
+    P[:, :, 0].index_add_(1, sets, xc)
+    P[:, :, 1].index_add_(1, sets, xc * xc)
+    bn = _module(t)
+    out = _run_bn(bn, t, partials=P.cuda())
+    what = "partials=%d" % per_channel
+    # double roundings: up to ceil(n / per_channel) additions inside a partial, ceil(per_channel / 256) per thread, six shuffles, three waves
+    chain = dict(c_s=0, c_q=0, c_d=(n + per_channel - 1) // per_channel + (per_channel + 255) // 256 + 9)
+    _check_stats(t, out, bn, what, **chain)
+    _check_apply_and_backward(t, out, bn, what)
+    assert out['nbt'] == 1
+
+
+@pytest.mark.parametrize("shape", [hp.BN_CASES[4][0], hp.BN_CASES[5][0]])
+def test_constant_planes(shape):
+    """x == 0.5 everywhere: every float32 partial sum is exact, so mean == 0.5, var == 0 and invstd == 1 / sqrt(eps) exactly;
+    xhat == 0, so y == relu(beta + res) with one rounding, dgamma == 0, and dx = k (g - mean g) within the bound of (b)."""
+    _gpu()
+    t = _bn_case(shape, const=0.5)
+    bn = _module(t)
+    out = _run_bn(bn, t)
+    C = shape[1]
+    assert torch.equal(out['mean'].cpu(), torch.full((C,), 0.5))
+    assert torch.equal(out['invstd'].cpu(), torch.full((C,), 1.0 / math.sqrt(hp.f32_as_float(bn.eps)), dtype=torch.float64).float())
+    assert torch.equal(out['y'].cpu(), torch.relu(t['beta'].view(1, C, 1, 1) + t['res']))
+    assert torch.equal(out['dgamma'].cpu(), torch.zeros(C))
+    what = "%dx%dx%dx%d constant" % shape
+    _check_stats(t, out, bn, what)
+    _check_apply_and_backward(t, out, bn, what)
+
+
+def test_conditioning_of_the_one_pass_variance():
+    """var = Q / n - m^2 from float32 partial sums loses (mean / std)^2 roundings: four channels of unit variance with mean / std of 0,
+    1, 8 and 64, judged by the bound of (a), which grows the same way (relative bound on invstd: 4e-7, 1.4e-6, 6e-5, 4e-3).  The
+    measured relative error of invstd is printed per channel (on an MI355X: 2.8e-8, 1.4e-8, 1.0e-7, 9.8e-6).  The one-pass form is
+    good to a relative 1e-4 up to mean / std of about 64; beyond that it wants a shifted or two-pass variance."""
+    _gpu()
+    x = hp.bn_conditioning_input()
+    C = x.shape[1]
+    t = dict(_bn_case((2, C, 1, 1221)), x=x)
+    bn = _module(t)
+    out = _run_bn(bn, t)
+    ref = _check_stats(t, out, bn, "conditioning")
+    rel = ((out['invstd'].double().cpu() - ref['invstd']) / ref['invstd']).abs()
+    print("relative invstd error at mean/std 0, 1, 8, 64:", ["%.2e" % float(v) for v in rel],
+          " bound:", ["%.2e" % float(v) for v in ref['invstd_bound'] / ref['invstd']])
+    _check_apply_and_backward(t, out, bn, "conditioning")
+
+
+@pytest.mark.parametrize("shape", [hp.BN_CASES[4][0], hp.BN_CASES[5][0]])
+@pytest.mark.parametrize("relu", [True, False])
+def test_inference_within_the_apply_bound(shape, relu):
+    """k_bn_apply<FROM_VAR>: the bound of (b) with the three roundings of 1 / sqrtf(var + eps)."""
+    ops = _gpu()
+    t = _bn_case(shape)
+    bn = _module(t).eval()
+    with torch.no_grad():
+        y = ops.bn_act(bn, t['x'].cuda(), relu, t['res'].cuda())
+    yr, yb = hp.bn_apply_reference(t['x'], t['gamma'], t['beta'], t['res'], t['rm'], t['rv'], relu, eps=bn.eps)
+    hp.assert_within(y, yr, yb, "bn y inference %dx%dx%dx%d" % shape)
+    assert torch.equal(bn.running_mean.cpu(), t['rm']) and int(bn.num_batches_tracked) == 0
