@@ -60,7 +60,9 @@ extern "C" {
  * mas_photometric_reference, then mas_partial_loss_reference and the MAS_LOSS_RC / MAS_LOSS_TOPONE flag bits (a library built before
  * them treats the bits as unset), then mas_online_plbl_labels, mas_label_ce_fwd_lowres / _bwd_lowres / _value and
  * mas_online_plbl_reference, then mas_online_soft_weights, mas_soft_ce_fwd_lowres / _bwd_lowres and mas_simw_plbl_reference with the
- * MAS_OPL_WEIGHT_SIM and MAS_LCE_SIGNED flag bits (a library built before them answers MAS_ERR_RANGE to either bit): new entry
+ * MAS_OPL_WEIGHT_SIM and MAS_LCE_SIGNED flag bits (a library built before them answers MAS_ERR_RANGE to either bit), then
+ * mas_teacher_loss_fwd / _bwd / _values / _scales and mas_teacher_loss_reference with the MAS_LOSS_TOP1 / MAS_LOSS_ENT /
+ * MAS_LOSS_WITHIN flag bits (the mas_partial_loss_* entry points answer MAS_ERR_RANGE to them): new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -217,6 +219,45 @@ int mas_partial_loss_fwd_fused(const float* z, int h, int w, const void* spx, in
 int mas_partial_loss_bwd_fused(const float* z, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits,
                                const void* work, const float* grad, const float* weights, int N, int C, int H, int W, int S, float invT,
                                int flags, float* dz, int64_t* dzq_fix, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Teacher-gated candidate terms (csrc/teacher_terms.h is the arithmetic): a FOURTH loss slot beside (ce, mc, group), computed by the
+ * same two scans over selected pixels of multi-hot superpixels only.
+ *   MAS_LOSS_TOP1  self-training top-1 (trainer/active_joint_multi_predignore_top1plbl.py:19-82, TopOnePlbl): -log max_{c in Y} p_c on
+ *                  the pixels whose eval-mode teacher is confident, plbl_th < max_{c in Y} t_c; with MAS_LOSS_WITHIN the gate value
+ *                  is divided by sum_{c in Y} t_c (--within_filtering).  `zt` = the teacher's logits, laid out as z.
+ *   MAS_LOSS_ENT   candidate entropy (trainer/active_joint_multi_predignore_multient.py:16-70, MultiChoiceEnt_): the entropy of the
+ *                  softmax restricted to the candidates; zt is not read (may be NULL).
+ * One of the two, combined freely with MAS_LOSS_CE (optionally MAS_LOSS_DECOMP) and the group flags; any other bit is MAS_ERR_RANGE,
+ * and the mas_partial_loss_* entry points answer MAS_ERR_RANGE to the three bits.  invT is the inverse temperature of the ce / group
+ * terms, invT_x (> 0) the fourth slot's own.  h, w > 0: z and zt are quarter-resolution tensors [N,C,h,w], upsampled per selected
+ * pixel as by mas_partial_loss_fwd_lowres; h = w = 0: [N,C,H,W].
+ * acc: SIXTEEN caller-zeroed u64 words -- the eight of mas_partial_loss_fwd, then MAS_ACC_SUM_X, MAS_ACC_N_X.  The group term is
+ * completed by mas_group_finalize as before.  mas_teacher_loss_values: losses4 = (ce, mc, group, x), x = sum_x / (1 + n_x).
+ * mas_teacher_loss_scales: scale4[k] = grad_out4[k] / (1 + n_k).  Backward: dz [N,C,H,W] written completely (h = 0), or dzq_fix
+ * [N,C,h,w] int64 caller-zeroed, as mas_partial_loss_bwd_lowres (then mas_fix_to_float); the teacher is a constant. */
+#define MAS_LOSS_TOP1 128
+#define MAS_LOSS_ENT 256
+#define MAS_LOSS_WITHIN 512
+#define MAS_ACC_SUM_X 8
+#define MAS_ACC_N_X 9
+#define MAS_TEACHER_ACC_WORDS 16
+int mas_teacher_loss_fwd(const float* z, const float* zt, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask,
+                         const uint32_t* bits, int N, int C, int H, int W, int S, float invT, float invT_x, float plbl_th, int flags,
+                         uint64_t* gmax /* [N,S,C] */, uint64_t* acc /* [16] */, void* stream);
+int mas_teacher_loss_values(const uint64_t* acc, int flags, float* losses4 /* [4] */, void* stream);
+int mas_teacher_loss_scales(const uint64_t* acc, const float* grad_out4 /* [4] */, int flags, float* scale4 /* [4] */, void* stream);
+int mas_teacher_loss_bwd(const float* z, const float* zt, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask,
+                         const uint32_t* bits, const uint64_t* gmax, const float* scale4 /* [4] */, int N, int C, int H, int W, int S,
+                         float invT, float invT_x, float plbl_th, int flags, float* dz, int64_t* dzq_fix, void* stream);
+/* The CPU-side statement of csrc/teacher_terms.h beside csrc/partial_label.h: HOST pointers, full resolution, no device touched.
+ * Every term of the flags -- acc [16] += (the group sums included: gmax [N,S,C] caller-zeroed, filled and finalized here), losses4 (may
+ * be NULL) = mas_teacher_loss_values of acc, dz (may be NULL; needs grad_out4) = what mas_teacher_loss_scales + mas_teacher_loss_bwd
+ * write.  The kernels are tested against it bit for bit. */
+int mas_teacher_loss_reference(const float* z, const float* zt, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits,
+                               int N, int C, int H, int W, int S, float invT, float invT_x, float plbl_th, int flags,
+                               const float* grad_out4 /* [4] or NULL */, uint64_t* acc /* [16] += */, uint64_t* gmax /* or NULL */,
+                               float* losses4 /* [4] or NULL */, float* dz /* or NULL */);
 
 /* The CPU-side statement of csrc/partial_label.h: every pointer is a HOST pointer, no device is touched.  A plain loop over the selected
  * pixels for the CE-family flags (MAS_LOSS_CE, optionally with MAS_LOSS_DECOMP and one of MAS_LOSS_RC / MAS_LOSS_TOPONE; any other bit

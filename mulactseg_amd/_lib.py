@@ -17,7 +17,9 @@ LABELS_BAD_VALUE = 1
 SCORE_FRAC, PROB_FRAC, LOSS_FRAC = 40, 23, 32
 LOSS_CE, LOSS_GROUP, LOSS_GROUP_ONLY_MULTI, LOSS_DECOMP, LOSS_TCE = 1, 2, 4, 8, 16
 LOSS_RC, LOSS_TOPONE = 32, 64       # the multi-hot pixel term of the CE sums (csrc/partial_label.h); neither = the merged positive
+LOSS_TOP1, LOSS_ENT, LOSS_WITHIN = 128, 256, 512     # the fourth loss slot of the mas_teacher_loss_* entry points (csrc/teacher_terms.h)
 ACC_WORDS = 8
+TEACHER_ACC_WORDS, ACC_SUM_X, ACC_N_X = 16, 8, 9
 GRAD_FRAC = 44
 MS_MAX_SOURCES = 16
 
@@ -165,6 +167,11 @@ SIGNATURES = {
     "mas_partial_loss_work_bytes": (_c.c_size_t, [_i, _i, _i, _i]),
     "mas_partial_loss_fwd_fused": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _c.c_size_t, _vp, _vp]),
     "mas_partial_loss_reference": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "mas_teacher_loss_fwd": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp]),
+    "mas_teacher_loss_values": (_i, [_vp, _i, _vp, _vp]),
+    "mas_teacher_loss_scales": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "mas_teacher_loss_bwd": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp]),
+    "mas_teacher_loss_reference": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "mas_adamw_job_bytes": (_c.c_size_t, []),
     "mas_adamw_max_groups": (_i, []),
     "mas_adamw_job": (_c.c_uint, [_vp, _vp, _vp, _vp, _vp, _c.c_longlong, _i, _c.c_uint]),

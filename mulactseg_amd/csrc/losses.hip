@@ -14,12 +14,18 @@
 //                        (MAS_LOSS_TOPONE) formula of partial_label.h instead of the merged positive; chosen at launch, so the
 //                        merged-positive kernels carry nothing of it.
 //   mas_partial_loss_reference   the CE-family sums and dz on HOST pointers, a plain loop through partial_label.h.
+//   the TT instantiations of both scans    the same two scan bodies with a fourth loss slot: the teacher-gated top-1 term (a second logit plane,
+//                        the eval-mode teacher's, read with the same taps / at the same address) or the candidate entropy of
+//                        teacher_terms.h, beside the merged-positive and group terms.  Kernels of their own, so every
+//                        k_partial_loss_* instantiation compiles to what it was.
+//   mas_teacher_loss_reference   all four terms (the group table included) and dz on HOST pointers.
 //
 // Reference semantics: trainer/active_joint_multi_predignore_lossdecomp.py:21-72 (OnehotCEMultihotChoice),
 // trainer/active_joint_multi_predignore_mclossablation2.py:22-79 (GroupMultiLabelCE_onlymulti),
 // trainer/active_joint_multi_predignore.py:21-128, utils/loss.py:91-141,543-588 (base classes).
 #include "common.h"
 #include "partial_label.h"
+#include "teacher_terms.h"
 
 namespace {
 
@@ -31,6 +37,16 @@ constexpr int kSlots = 1 << kLogSlots;
 
 // accumulator slots of the u64 `acc` array
 enum { ACC_SUM_CE = 0, ACC_SUM_MC = 1, ACC_N_CE = 2, ACC_N_MC = 3, ACC_N_EMPTY = 4, ACC_SUM_GROUP = 5, ACC_N_GROUP = 6 };
+// the teacher-term scans use a 16-word accumulator: word 7 stays the fused forward's arrival counter, 8 / 9 are the fourth loss slot
+enum { ACC_SUM_X = 8, ACC_N_X = 9 };
+
+// what the teacher-term kernels take beside the arguments of the plain scans (teacher_terms.h); TT == MAS_TT_NONE bodies never read it
+struct TeacherIn {
+    const float* zt;        // teacher logits, laid out as z (top1; NULL for ent)
+    float invT;             // the term's own inverse temperature
+    float th;               // plbl_th
+    int within;             // within_filtering
+};
 
 __device__ __forceinline__ mas_u64 pack_max(float p, unsigned pix) {
     return ((mas_u64)mas_f2u(p) << 32) | (mas_u64)(0xffffffffu - pix);
@@ -171,17 +187,44 @@ __device__ __forceinline__ void tile_compact(const unsigned char* __restrict__ m
     }
 }
 
-template <int CT, bool EXACT, typename IdT, bool VEC, bool LOWRES, bool PLX>
+// The fourth loss slot of a selected multi-hot pixel (teacher_terms.h).  `v` holds the student's logits.  top1: the teacher's row is
+// loaded into `u` (same taps / same address as the student's), reduced to the gate, and only then overwritten with the student's
+// softmax at the term's temperature -- the teacher row is never live beside a third array.  ent: `u` = the softmax restricted to
+// M = the candidates with a non-zero logit.  Returns whether the pixel counts.
+template <int CT, bool EXACT, bool LOWRES, int TT>
+__device__ __forceinline__ bool teacher_term_probs(const float* __restrict__ ztb, const float (&v)[CT], int C, int HW, size_t pix, int py,
+                                                   int px, const LowRes& lr, unsigned Y, const TeacherIn& te, float (&u)[CT], unsigned& M) {
+    const int Cn = EXACT ? CT : C;
+    if (TT == MAS_TT_TOP1) {
+        LTap t_y, t_x;
+        load_logits<CT, EXACT, LOWRES>(ztb, C, HW, pix, py, px, lr, u, t_y, t_x);
+        M = mas_tt_all(Cn);
+        mas_tt_softmax(u, CT, Cn, M, te.invT);
+        if (!mas_tt_gate(u, CT, Cn, Y, te.within, te.th)) return false;
+    } else {
+        M = mas_tt_ent_set(v, CT, Cn, Y);
+    }
+#pragma unroll
+    for (int c = 0; c < CT; ++c) u[c] = v[c];
+    mas_tt_softmax(u, CT, Cn, M, te.invT);
+    return true;
+}
+
+// TT (MAS_TT_*): the fourth loss slot (teacher_terms.h).  MAS_TT_NONE instantiations are the scans as they were: `te` is a trailing
+// kernel argument they never read, and nothing of the slot is compiled into them.
+template <int CT, bool EXACT, typename IdT, bool VEC, bool LOWRES, bool PLX, int TT>
 __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __restrict__ z, const IdT* __restrict__ spx,
                                                                 const unsigned char* __restrict__ mask,
                                                                 const unsigned* __restrict__ bits, int C, int H, int W, int S,
                                                                 float invT, int flags, int tiles_x, int tiles_y,
-                                                                mas_u64* __restrict__ gmax, mas_u64* __restrict__ acc, const LowRes lr) {
+                                                                mas_u64* __restrict__ gmax, mas_u64* __restrict__ acc, const LowRes lr,
+                                                                const TeacherIn te) {
+    constexpr int NR = TT ? 7 : 5;              // scalar accumulators of a workgroup
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     mas_u64* t_max = reinterpret_cast<mas_u64*>(smem);                       // [kSlots * C]
     int* t_keys = reinterpret_cast<int*>(smem + sizeof(mas_u64) * kSlots * C);  // [kSlots]
-    mas_u64* s_red = reinterpret_cast<mas_u64*>(smem + sizeof(mas_u64) * kSlots * C + sizeof(int) * kSlots);  // [4][5]
-    int* qcount = reinterpret_cast<int*>(s_red + 4 * 5);
+    mas_u64* s_red = reinterpret_cast<mas_u64*>(smem + sizeof(mas_u64) * kSlots * C + sizeof(int) * kSlots);  // [4][NR]
+    int* qcount = reinterpret_cast<int*>(s_red + 4 * NR);
     unsigned short* queue = reinterpret_cast<unsigned short*>(qcount + 2);     // [kTilePx]
 
     const bool do_ce = flags & MAS_LOSS_CE;
@@ -202,6 +245,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
     const int n = bid / tiles_y;
     const int HW = H * W;
     const float* zb = z + (size_t)n * C * (LOWRES ? lr.h * lr.w : HW);
+    const float* ztb = (TT == MAS_TT_TOP1) ? te.zt + (size_t)n * C * (LOWRES ? lr.h * lr.w : HW) : nullptr;
     const IdT* sb = spx + (size_t)n * HW;
     const unsigned char* mb = mask + (size_t)n * HW;
     const unsigned* bb = bits + (size_t)n * S;
@@ -213,8 +257,8 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
     __syncthreads();
     const int nq = *qcount;
 
-    mas_u64 sum_ce = 0, sum_mc = 0;
-    unsigned n_ce = 0, n_mc = 0, n_empty = 0;
+    mas_u64 sum_ce = 0, sum_mc = 0, sum_x = 0;
+    unsigned n_ce = 0, n_mc = 0, n_empty = 0, n_x = 0;
     for (int i = threadIdx.x; i < nq; i += kThreads) {
         const unsigned off = queue[i];
         const int py = ty * kTileH + (int)(off >> 8), px = tx * kTileW + (int)(off & 255u);
@@ -227,6 +271,16 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
         const unsigned Y = tce ? (1u << id) : bb[id];
         const int nb = __popc(Y);
         if (nb == 0) { n_empty += 1; continue; }
+        if (TT != MAS_TT_NONE && nb > 1) {
+            float u[CT];
+            unsigned M;
+            if (teacher_term_probs<CT, EXACT, LOWRES, TT>(ztb, v, C, HW, pix, py, px, lr, Y, te, u, M)) {
+                const int Cn = EXACT ? CT : C;
+                const float l = (TT == MAS_TT_TOP1) ? mas_pl_loss(u, CT, Cn, Y, MAS_PL_TOPONE) : mas_tt_ent_loss(u, CT, Cn, M);
+                sum_x += mas_fix(l, MAS_LOSS_FRAC);
+                n_x += 1;
+            }
+        }
         {
             const float rinv = mas_softmax_regs<CT, EXACT>(v, C, invT);
 #pragma unroll
@@ -259,19 +313,19 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
         }
     }
 
-    // block reduction of the five scalar accumulators
-    mas_u64 r[5] = {sum_ce, sum_mc, (mas_u64)n_ce, (mas_u64)n_mc, (mas_u64)n_empty};
+    // block reduction of the five (teacher terms: seven) scalar accumulators
+    mas_u64 r[7] = {sum_ce, sum_mc, (mas_u64)n_ce, (mas_u64)n_mc, (mas_u64)n_empty, sum_x, (mas_u64)n_x};
 #pragma unroll
-    for (int i = 0; i < 5; ++i) {
+    for (int i = 0; i < NR; ++i) {
 #pragma unroll
         for (int off = MAS_WAVE / 2; off > 0; off >>= 1) r[i] += __shfl_down(r[i], off, MAS_WAVE);
-        if (lane == 0) s_red[wave * 5 + i] = r[i];
+        if (lane == 0) s_red[wave * NR + i] = r[i];
     }
     __syncthreads();
-    if (threadIdx.x < 5) {
+    if (threadIdx.x < NR) {
         mas_u64 a = 0;
-        for (int w = 0; w < kThreads / MAS_WAVE; ++w) a += s_red[w * 5 + threadIdx.x];
-        if (a) atomicAdd(&acc[threadIdx.x], a);
+        for (int w = 0; w < kThreads / MAS_WAVE; ++w) a += s_red[w * NR + threadIdx.x];
+        if (a) atomicAdd(&acc[threadIdx.x < 5 ? threadIdx.x : ACC_SUM_X + (threadIdx.x - 5)], a);
     }
     if (do_group) {
         for (int i = threadIdx.x; i < kSlots * C; i += kThreads) {
@@ -429,7 +483,9 @@ __global__ void k_loss_scales(const mas_u64* __restrict__ acc, const float* __re
 // selected pixel adds (gradient of its class-c logit) * (bilinear weight) into the four quarter-resolution elements its
 // logits were interpolated from -- integer atomics, so the sums do not depend on the order; nothing is written at full
 // resolution.
-template <int CT, bool EXACT, typename IdT, bool VEC, bool LOWRES, bool PLX>
+// TT != MAS_TT_NONE: scale[3] is the factor of the fourth loss slot; the gradient of its term is added to the pixel's d in f32 before
+// the one store (full resolution) or the four fixed-point adds (LOWRES), so there is still one write per logit.
+template <int CT, bool EXACT, typename IdT, bool VEC, bool LOWRES, bool PLX, int TT>
 __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __restrict__ z, const IdT* __restrict__ spx,
                                                                 const unsigned char* __restrict__ mask,
                                                                 const unsigned* __restrict__ bits,
@@ -437,7 +493,8 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
                                                                 const float* __restrict__ scale, int C, int H, int W, int S,
                                                                 float invT, int flags, int tiles_x, int tiles_y,
                                                                 float* __restrict__ dz, const LowRes lr, const mas_u64* __restrict__ acc,
-                                                                const float* __restrict__ grad, const float* __restrict__ gw) {
+                                                                const float* __restrict__ grad, const float* __restrict__ gw,
+                                                                const TeacherIn te) {
     __shared__ int qcount[2];
     __shared__ unsigned short queue[kTilePx];
     // LOWRES: the quarter-resolution footprint of a 4 x 256 tile (<= 4 rows x 72 columns per class for the x4 ratios of the
@@ -458,6 +515,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
     const int HW = H * W;
     const int hw_in = LOWRES ? lr.h * lr.w : HW;
     const float* zb = z + (size_t)n * C * hw_in;
+    const float* ztb = (TT == MAS_TT_TOP1) ? te.zt + (size_t)n * C * hw_in : nullptr;
     float* db = LOWRES ? nullptr : dz + (size_t)n * C * HW;
     mas_u64* qb = LOWRES ? reinterpret_cast<mas_u64*>(dz) + (size_t)n * C * hw_in : nullptr;
     const IdT* sb = spx + (size_t)n * HW;
@@ -470,6 +528,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
     if (scale) { sc3[0] = scale[0]; sc3[1] = scale[1]; sc3[2] = scale[2]; }
     else loss_scales_of(acc, grad, gw, flags, sc3);
     const float a_ce = sc3[0] * invT, a_mc = sc3[1] * invT, g6 = sc3[2] * invT;
+    const float a_x = (TT != MAS_TT_NONE) ? scale[3] * te.invT : 0.0f;
 
     // phase 1: dz = 0 over the whole tile (streaming 16-B stores) while the selected pixels are compacted
     tile_compact<CT, EXACT, VEC, !LOWRES>(mb, C, H, W, HW, tx, ty, queue, qcount, db);
@@ -502,6 +561,19 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
         float v[CT];
         LTap t_y, t_x;
         load_logits<CT, EXACT, LOWRES>(zb, C, HW, pix, py, px, lr, v, t_y, t_x);
+        // the fourth slot: u = the term's own probabilities of this pixel, (gx, ux) the per-pixel constants of its gradient
+        float u[TT != MAS_TT_NONE ? CT : 1];
+        unsigned M = 0;
+        bool xon = false;
+        mas_pl_grad_ctx gx = {};
+        float ux = 0.0f;
+        if constexpr (TT != MAS_TT_NONE) {
+            if (nb > 1) xon = teacher_term_probs<CT, EXACT, LOWRES, TT>(ztb, v, C, HW, pix, py, px, lr, Y, te, u, M);
+            if (xon) {
+                if (TT == MAS_TT_TOP1) gx = mas_pl_grad_prepare(u, CT, EXACT ? CT : C, Y, MAS_PL_TOPONE, a_x);
+                else ux = mas_tt_ent_u(u, CT, EXACT ? CT : C, M);
+            }
+        }
         {
             const float rinv = mas_softmax_regs<CT, EXACT>(v, C, invT);
 #pragma unroll
@@ -521,7 +593,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
         }
         // group loss: classes of Y whose arg-max pixel is this pixel
         unsigned A = 0;
-        float u = 0.0f;
+        float ug = 0.0f;
         float t[CT];
 #pragma unroll
         for (int c = 0; c < CT; ++c) t[c] = 0.0f;
@@ -534,7 +606,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
                     if ((unsigned)w == key && (unsigned)(w >> 32) != 0u) {
                         A |= 1u << c;
                         t[c] = -(g6 / (v[c] + 1e-8f));
-                        u = u + t[c] * v[c];
+                        ug = ug + t[c] * v[c];
                     }
                 }
             }
@@ -548,7 +620,11 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
                 if (plx) d = mas_pl_grad(gk, pl_mode, p, (int)((Y >> c) & 1u), c);
                 if (A) {
                     if ((A >> c) & 1u) d = d + t[c] * p;
-                    d = d - p * u;
+                    d = d - p * ug;
+                }
+                if constexpr (TT != MAS_TT_NONE) {
+                    if (xon) d = d + ((TT == MAS_TT_TOP1) ? mas_pl_grad(gx, MAS_PL_TOPONE, u[c], (int)((Y >> c) & 1u), c)
+                                                          : mas_tt_ent_grad(a_x, ux, u[c], (int)((M >> c) & 1u)));
                 }
                 if (LOWRES) {
                     mas_u64* q = qb + (size_t)c * hw_in;
@@ -575,8 +651,8 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
     }
 }
 
-inline size_t fwd_smem_bytes(int C) {
-    return sizeof(mas_u64) * kSlots * (size_t)C + sizeof(int) * kSlots + sizeof(mas_u64) * 4 * 5 + sizeof(int) * 2 +
+inline size_t fwd_smem_bytes(int C, bool teacher = false) {
+    return sizeof(mas_u64) * kSlots * (size_t)C + sizeof(int) * kSlots + sizeof(mas_u64) * 4 * (teacher ? 7 : 5) + sizeof(int) * 2 +
            sizeof(unsigned short) * kTilePx;
 }
 
@@ -586,9 +662,11 @@ struct LossArgs {
     mas_u64* gmax; mas_u64* acc; const float* scale; float* dz;
     int h = 0, w = 0;           // > 0: `z` is the quarter-resolution tensor [N,C,h,w] (LOWRES kernels)
     const float* grad = nullptr; const float* gw = nullptr;     // backward with scale == NULL: upstream gradient(s) and optional weights
+    TeacherIn te = {nullptr, 0.f, 0.f, 0};                      // MAS_LOSS_TOP1 / MAS_LOSS_ENT (`scale` then holds four factors)
+    bool teacher = false;       // set by the mas_teacher_loss_* entry points: `acc` has 16 words and `te` is filled in
 };
 
-template <int CT, bool EXACT, typename IdT, bool PLX>
+template <int CT, bool EXACT, typename IdT, bool PLX, int TT = MAS_TT_NONE>
 int launch_loss(const LossArgs& a, bool backward, hipStream_t st) {
     const int tiles_x = (a.W + kTileW - 1) / kTileW;
     const int tiles_y = (a.H + kTileH - 1) / kTileH;
@@ -602,11 +680,11 @@ int launch_loss(const LossArgs& a, bool backward, hipStream_t st) {
 #define MAS_LAUNCH_LOSS(VECV, LOWV)                                                                                                     \
     do {                                                                                                                                \
         if (!backward)                                                                                                                  \
-            hipLaunchKernelGGL((k_partial_loss_fwd<CT, EXACT, IdT, VECV, LOWV, PLX>), grid, block, fwd_smem_bytes(a.C), st, a.z, ids, a.mask, \
-                               a.bits, a.C, a.H, a.W, a.S, a.invT, a.flags, tiles_x, tiles_y, a.gmax, a.acc, lr);                        \
+            hipLaunchKernelGGL((k_partial_loss_fwd<CT, EXACT, IdT, VECV, LOWV, PLX, TT>), grid, block, fwd_smem_bytes(a.C, TT != 0), st, a.z, ids, \
+                               a.mask, a.bits, a.C, a.H, a.W, a.S, a.invT, a.flags, tiles_x, tiles_y, a.gmax, a.acc, lr, a.te);           \
         else                                                                                                                            \
-            hipLaunchKernelGGL((k_partial_loss_bwd<CT, EXACT, IdT, VECV, LOWV, PLX>), grid, block, 0, st, a.z, ids, a.mask, a.bits, a.gmax, \
-                               a.scale, a.C, a.H, a.W, a.S, a.invT, a.flags, tiles_x, tiles_y, a.dz, lr, a.acc, a.grad, a.gw);           \
+            hipLaunchKernelGGL((k_partial_loss_bwd<CT, EXACT, IdT, VECV, LOWV, PLX, TT>), grid, block, 0, st, a.z, ids, a.mask, a.bits, a.gmax, \
+                               a.scale, a.C, a.H, a.W, a.S, a.invT, a.flags, tiles_x, tiles_y, a.dz, lr, a.acc, a.grad, a.gw, a.te);     \
     } while (0)
     if (low) { if (vec) MAS_LAUNCH_LOSS(true, true); else MAS_LAUNCH_LOSS(false, true); }
     else { if (vec) MAS_LAUNCH_LOSS(true, false); else MAS_LAUNCH_LOSS(false, false); }
@@ -616,6 +694,17 @@ int launch_loss(const LossArgs& a, bool backward, hipStream_t st) {
 
 template <int CT, bool EXACT>
 int dispatch_loss_ids(const LossArgs& a, int spx_dtype, bool backward, hipStream_t st) {
+    if (const int tt = mas_tt_mode(a.flags)) {
+#define MAS_TEACHER_BY_TERM(IDT) (tt == MAS_TT_TOP1 ? launch_loss<CT, EXACT, IDT, false, MAS_TT_TOP1>(a, backward, st) \
+                                                    : launch_loss<CT, EXACT, IDT, false, MAS_TT_ENT>(a, backward, st))
+        switch (spx_dtype) {
+            case MAS_ID_I64: return MAS_TEACHER_BY_TERM(long long);
+            case MAS_ID_I32: return MAS_TEACHER_BY_TERM(int);
+            case MAS_ID_U16: return MAS_TEACHER_BY_TERM(unsigned short);
+            default: return MAS_ERR_DTYPE;
+        }
+#undef MAS_TEACHER_BY_TERM
+    }
     // the rc / topone multi-hot term is compiled into instantiations of its own (PLX): the merged-positive kernels stay as they were
     const bool plx = (a.flags & (MAS_LOSS_RC | MAS_LOSS_TOPONE)) != 0;
 #define MAS_LOSS_BY_MODE(IDT) (plx ? launch_loss<CT, EXACT, IDT, true>(a, backward, st) : launch_loss<CT, EXACT, IDT, false>(a, backward, st))
@@ -630,13 +719,23 @@ int dispatch_loss_ids(const LossArgs& a, int spx_dtype, bool backward, hipStream
 
 // MAS_LOSS_RC / MAS_LOSS_TOPONE name the multi-hot term of the CE sums: one of them at most, with MAS_LOSS_CE, never with MAS_LOSS_TCE
 inline bool loss_flags_ok(int flags) {
+    if (flags & (MAS_LOSS_TOP1 | MAS_LOSS_ENT | MAS_LOSS_WITHIN)) return false;     // (the mas_teacher_loss_* entry points only)
     const int m = flags & (MAS_LOSS_RC | MAS_LOSS_TOPONE);
     if (!m) return true;
     return m != (MAS_LOSS_RC | MAS_LOSS_TOPONE) && (flags & MAS_LOSS_CE) && !(flags & MAS_LOSS_TCE);
 }
 
+// MAS_LOSS_TOP1 / MAS_LOSS_ENT: one of them, beside the merged-positive (MAS_LOSS_CE, optionally MAS_LOSS_DECOMP) and group flags only;
+// MAS_LOSS_WITHIN qualifies MAS_LOSS_TOP1
+inline bool teacher_flags_ok(int flags) {
+    const int t = flags & (MAS_LOSS_TOP1 | MAS_LOSS_ENT);
+    if (!t || t == (MAS_LOSS_TOP1 | MAS_LOSS_ENT)) return false;
+    if ((flags & MAS_LOSS_WITHIN) && !(flags & MAS_LOSS_TOP1)) return false;
+    return !(flags & ~(MAS_LOSS_CE | MAS_LOSS_DECOMP | MAS_LOSS_GROUP | MAS_LOSS_GROUP_ONLY_MULTI | MAS_LOSS_TOP1 | MAS_LOSS_ENT | MAS_LOSS_WITHIN));
+}
+
 int dispatch_loss(const LossArgs& a, int spx_dtype, bool backward, hipStream_t st) {
-    if (!loss_flags_ok(a.flags)) return MAS_ERR_RANGE;
+    if (!(a.teacher ? teacher_flags_ok(a.flags) : loss_flags_ok(a.flags))) return MAS_ERR_RANGE;
     if (a.N <= 0 || a.H <= 0 || a.W <= 0 || a.S <= 0 || (long long)a.H * a.W > 0x7fffffffLL / 2) return MAS_ERR_SHAPE;
     if (a.C < 2 || a.C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
     switch (a.C) {
@@ -916,6 +1015,224 @@ extern "C" int mas_partial_loss_reference(const float* z, const void* spx, int s
             }
         }
         if (pass == 0 && losses) loss_values_of(a64, flags, nullptr, losses);
+    }
+    return 0;
+}
+
+// ---- teacher-gated candidate terms (teacher_terms.h): step-by-step entry points over the teacher-term kernels --------------------------
+// Reference: trainer/active_joint_multi_predignore_top1plbl.py:19-82 (TopOnePlbl), ..._multient.py:16-70 (MultiChoiceEnt_).
+namespace {
+inline int teacher_args_ok(const float* z, const float* zt, int h, int w, const void* spx, const uint8_t* mask, const uint32_t* bits, int H, int W,
+                           float invT_x, int flags) {
+    if (!z || !spx || !mask || !bits) return MAS_ERR_NULL;
+    if (!teacher_flags_ok(flags)) return MAS_ERR_RANGE;
+    if ((flags & MAS_LOSS_TOP1) && !zt) return MAS_ERR_NULL;
+    if (!(invT_x > 0.0f)) return MAS_ERR_RANGE;
+    if ((h > 0) != (w > 0) || h < 0 || h > H || w > W) return MAS_ERR_SHAPE;
+    return 0;
+}
+}  // namespace
+
+extern "C" int mas_teacher_loss_fwd(const float* z, const float* zt, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask,
+                                    const uint32_t* bits, int N, int C, int H, int W, int S, float invT, float invT_x, float plbl_th, int flags,
+                                    uint64_t* gmax, uint64_t* acc, void* stream) {
+    if (int e = teacher_args_ok(z, zt, h, w, spx, mask, bits, H, W, invT_x, flags)) return e;
+    if (!acc || ((flags & MAS_LOSS_GROUP) && !gmax)) return MAS_ERR_NULL;
+    LossArgs a{z, spx, mask, bits, N, C, H, W, S, invT, flags, reinterpret_cast<mas_u64*>(gmax), reinterpret_cast<mas_u64*>(acc), nullptr,
+               nullptr, h > 0 ? h : 0, h > 0 ? w : 0};
+    a.te = TeacherIn{zt, invT_x, plbl_th, (flags & MAS_LOSS_WITHIN) ? 1 : 0};
+    a.teacher = true;
+    return dispatch_loss(a, spx_dtype, false, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mas_teacher_loss_bwd(const float* z, const float* zt, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask,
+                                    const uint32_t* bits, const uint64_t* gmax, const float* scale, int N, int C, int H, int W, int S,
+                                    float invT, float invT_x, float plbl_th, int flags, float* dz, int64_t* dzq_fix, void* stream) {
+    if (int e = teacher_args_ok(z, zt, h, w, spx, mask, bits, H, W, invT_x, flags)) return e;
+    if (!scale || (h > 0 ? !dzq_fix : !dz) || ((flags & MAS_LOSS_GROUP) && !gmax)) return MAS_ERR_NULL;
+    LossArgs a{z, spx, mask, bits, N, C, H, W, S, invT, flags, const_cast<mas_u64*>(reinterpret_cast<const mas_u64*>(gmax)), nullptr, scale,
+               h > 0 ? reinterpret_cast<float*>(dzq_fix) : dz, h > 0 ? h : 0, h > 0 ? w : 0};
+    a.te = TeacherIn{zt, invT_x, plbl_th, (flags & MAS_LOSS_WITHIN) ? 1 : 0};
+    a.teacher = true;
+    return dispatch_loss(a, spx_dtype, true, static_cast<hipStream_t>(stream));
+}
+
+namespace {
+// losses4 = (ce, mc, group, x): the first three as mas_loss_values, x = the fourth slot's sum / (1 + n)
+__host__ __device__ __forceinline__ void teacher_values_of(const mas_u64* acc, int flags, float* out) {
+    loss_values_of(acc, flags & ~(MAS_LOSS_TOP1 | MAS_LOSS_ENT | MAS_LOSS_WITHIN), nullptr, out);
+    out[3] = loss_value(acc[ACC_SUM_X], acc[ACC_N_X]);
+}
+__host__ __device__ __forceinline__ void teacher_scales_of(const mas_u64* acc, const float* grad, int flags, float* scale) {
+    loss_scales_of(acc, grad, nullptr, flags & ~(MAS_LOSS_TOP1 | MAS_LOSS_ENT | MAS_LOSS_WITHIN), scale);
+    scale[3] = grad[3] / (float)(acc[ACC_N_X] + 1);
+}
+__global__ void k_teacher_loss_values(const mas_u64* __restrict__ acc, int flags, float* __restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    teacher_values_of(acc, flags, out);
+}
+__global__ void k_teacher_loss_scales(const mas_u64* __restrict__ acc, const float* __restrict__ grad, int flags, float* __restrict__ scale) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    teacher_scales_of(acc, grad, flags, scale);
+}
+}  // namespace
+
+extern "C" int mas_teacher_loss_values(const uint64_t* acc, int flags, float* losses4, void* stream) {
+    if (!acc || !losses4) return MAS_ERR_NULL;
+    if (!teacher_flags_ok(flags)) return MAS_ERR_RANGE;
+    hipLaunchKernelGGL(k_teacher_loss_values, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), reinterpret_cast<const mas_u64*>(acc), flags,
+                       losses4);
+    return mas_launch_status();
+}
+
+extern "C" int mas_teacher_loss_scales(const uint64_t* acc, const float* grad_out4, int flags, float* scale4, void* stream) {
+    if (!acc || !grad_out4 || !scale4) return MAS_ERR_NULL;
+    if (!teacher_flags_ok(flags)) return MAS_ERR_RANGE;
+    hipLaunchKernelGGL(k_teacher_loss_scales, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), reinterpret_cast<const mas_u64*>(acc),
+                       grad_out4, flags, scale4);
+    return mas_launch_status();
+}
+
+// ---- the CPU-side statement: host pointers, a plain loop over the pixels through partial_label.h and teacher_terms.h, every term the
+// teacher-term kernels compute -- the merged-positive sums, the group table with its finalize, the fourth slot -- and dz in the
+// operation order of the TT instantiations of k_partial_loss_bwd.  No device is touched.
+extern "C" int mas_teacher_loss_reference(const float* z, const float* zt, const void* spx, int spx_dtype, const uint8_t* mask,
+                                          const uint32_t* bits, int N, int C, int H, int W, int S, float invT, float invT_x, float plbl_th,
+                                          int flags, const float* grad_out4, uint64_t* acc, uint64_t* gmax, float* losses4, float* dz) {
+    if (int e = teacher_args_ok(z, zt, 0, 0, spx, mask, bits, H, W, invT_x, flags)) return e;
+    if (!acc || (dz && !grad_out4) || ((flags & MAS_LOSS_GROUP) && !gmax)) return MAS_ERR_NULL;
+    if (N <= 0 || H <= 0 || W <= 0 || S <= 0 || (long long)H * W > 0x7fffffffLL / 2) return MAS_ERR_SHAPE;
+    if (C < 2 || C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
+    if (spx_dtype != MAS_ID_I64 && spx_dtype != MAS_ID_I32 && spx_dtype != MAS_ID_U16) return MAS_ERR_DTYPE;
+    const int tt = mas_tt_mode(flags), within = (flags & MAS_LOSS_WITHIN) ? 1 : 0;
+    const bool do_ce = flags & MAS_LOSS_CE, do_group = flags & MAS_LOSS_GROUP, only_multi = flags & MAS_LOSS_GROUP_ONLY_MULTI;
+    const size_t HW = (size_t)H * W;
+    mas_u64* a64 = reinterpret_cast<mas_u64*>(acc);
+    mas_u64* g64 = reinterpret_cast<mas_u64*>(gmax);
+    for (int pass = 0; pass < (dz ? 2 : 1); ++pass) {
+        float sc4[4] = {0.f, 0.f, 0.f, 0.f};
+        if (pass == 1) {
+            teacher_scales_of(a64, grad_out4, flags, sc4);
+            for (size_t i = 0; i < (size_t)N * C * HW; ++i) dz[i] = 0.0f;
+        }
+        const float a_ce = sc4[0] * invT, a_mc = sc4[1] * invT, g6 = sc4[2] * invT, a_x = sc4[3] * invT_x;
+        for (int n = 0; n < N; ++n) {
+            for (size_t i = 0; i < HW; ++i) {
+                const size_t g = (size_t)n * HW + i;
+                if (!mask[g]) continue;
+                long long id;
+                if (spx_dtype == MAS_ID_I64) id = static_cast<const long long*>(spx)[g];
+                else if (spx_dtype == MAS_ID_I32) id = static_cast<const int*>(spx)[g];
+                else id = static_cast<const unsigned short*>(spx)[g];
+                if (id < 0 || id >= S) continue;
+                const uint32_t Y = bits[(size_t)n * S + (size_t)id];
+                const int nb = mas_pl_popcount(Y);
+                if (nb == 0) { if (pass == 0) a64[ACC_N_EMPTY] += 1; continue; }
+                float v[MAS_MAX_CLASSES], u[MAS_MAX_CLASSES];
+                for (int c = 0; c < C; ++c) v[c] = z[((size_t)n * C + c) * HW + i];
+                // the fourth slot
+                bool xon = false;
+                uint32_t M = 0;
+                if (nb > 1) {
+                    xon = true;
+                    if (tt == MAS_TT_TOP1) {
+                        for (int c = 0; c < C; ++c) u[c] = zt[((size_t)n * C + c) * HW + i];
+                        M = mas_tt_all(C);
+                        mas_tt_softmax(u, C, C, M, invT_x);
+                        xon = mas_tt_gate(u, C, C, Y, within, plbl_th) != 0;
+                    } else {
+                        M = mas_tt_ent_set(v, C, C, Y);
+                    }
+                    if (xon) {
+                        for (int c = 0; c < C; ++c) u[c] = v[c];
+                        mas_tt_softmax(u, C, C, M, invT_x);
+                    }
+                }
+                mas_pl_grad_ctx gx = {};
+                float ux = 0.0f;
+                if (xon && pass == 0) {
+                    const float l = (tt == MAS_TT_TOP1) ? mas_pl_loss(u, C, C, Y, MAS_PL_TOPONE) : mas_tt_ent_loss(u, C, C, M);
+                    a64[ACC_SUM_X] += mas_fix(l, MAS_LOSS_FRAC);
+                    a64[ACC_N_X] += 1;
+                } else if (xon) {
+                    if (tt == MAS_TT_TOP1) gx = mas_pl_grad_prepare(u, C, C, Y, MAS_PL_TOPONE, a_x);
+                    else ux = mas_tt_ent_u(u, C, C, M);
+                }
+                // the scan's softmax (mas_softmax_regs)
+                {
+                    float m = v[0];
+                    for (int c = 1; c < C; ++c) m = (v[c] > m) ? v[c] : m;
+                    const float negM = -(m * invT);
+                    float sum = 0.0f;
+                    for (int c = 0; c < C; ++c) {
+                        v[c] = mas_expf_np(mas_fmaf(v[c], invT, negM));
+                        sum = (c == 0) ? v[c] : (sum + v[c]);
+                    }
+                    const float rinv = 1.0f / sum;
+                    for (int c = 0; c < C; ++c) v[c] = v[c] * rinv;
+                }
+                const bool grp = do_group && (!only_multi || nb > 1);
+                mas_u64* gm = g64 ? g64 + (size_t)n * S * C + (size_t)id * C : nullptr;
+                if (pass == 0) {
+                    if (do_ce) {
+                        const mas_u64 q = mas_fix(mas_pl_loss(v, C, C, Y, MAS_PL_CHOICE), MAS_LOSS_FRAC);
+                        if (nb == 1) { a64[ACC_SUM_CE] += q; a64[ACC_N_CE] += 1; } else { a64[ACC_SUM_MC] += q; a64[ACC_N_MC] += 1; }
+                    }
+                    if (grp) {
+                        for (int c = 0; c < C; ++c) {
+                            if ((Y >> c) & 1u) {
+                                const mas_u64 w64 = ((mas_u64)mas_f2u(v[c]) << 32) | (mas_u64)(0xffffffffu - (unsigned)i);
+                                if (w64 > gm[c]) gm[c] = w64;
+                            }
+                        }
+                    }
+                    continue;
+                }
+                float coef = 0.0f, pos = 0.0f;
+                if (do_ce) {
+                    pos = mas_pl_pos(v, C, C, Y);
+                    coef = ((nb == 1) ? a_ce : a_mc) * (1.0f / (pos + 1e-8f));
+                }
+                unsigned A = 0;
+                float ug = 0.0f;
+                float t[MAS_MAX_CLASSES];
+                for (int c = 0; c < C; ++c) t[c] = 0.0f;
+                if (grp) {
+                    const unsigned key = 0xffffffffu - (unsigned)i;
+                    for (int c = 0; c < C; ++c) {
+                        if ((Y >> c) & 1u) {
+                            const mas_u64 w64 = gm[c];
+                            if ((unsigned)w64 == key && (unsigned)(w64 >> 32) != 0u) {
+                                A |= 1u << c;
+                                t[c] = -(g6 / (v[c] + 1e-8f));
+                                ug = ug + t[c] * v[c];
+                            }
+                        }
+                    }
+                }
+                for (int c = 0; c < C; ++c) {
+                    const float p = v[c];
+                    const float yj = ((Y >> c) & 1u) ? 1.0f : 0.0f;
+                    float d = coef * (p * (pos - yj));
+                    if (A) {
+                        if ((A >> c) & 1u) d = d + t[c] * p;
+                        d = d - p * ug;
+                    }
+                    if (xon) d = d + ((tt == MAS_TT_TOP1) ? mas_pl_grad(gx, MAS_PL_TOPONE, u[c], (int)((Y >> c) & 1u), c)
+                                                          : mas_tt_ent_grad(a_x, ux, u[c], (int)((M >> c) & 1u)));
+                    dz[((size_t)n * C + c) * HW + i] = d;
+                }
+            }
+        }
+        if (pass == 0) {
+            if (do_group) {             // k_group_finalize
+                for (size_t e = 0; e < (size_t)N * S * C; ++e) {
+                    const unsigned pb = (unsigned)(g64[e] >> 32);
+                    if (pb) { a64[ACC_SUM_GROUP] += mas_fix(-mas_logf(mas_u2f(pb) + 1e-8f), MAS_LOSS_FRAC); a64[ACC_N_GROUP] += 1; }
+                }
+            }
+            if (losses4) teacher_values_of(a64, flags, losses4);
+        }
     }
     return 0;
 }

@@ -348,6 +348,102 @@ def partial_loss_bwd_fused(z, size, spx, mask, state, grad, invT, weights=None, 
 
 
 # ------------------------------------------------------------------------------------------------
+# teacher-gated candidate terms: a fourth loss slot in the same scans (csrc/teacher_terms.h, k_teacher_loss_fwd / _bwd)
+# ------------------------------------------------------------------------------------------------
+LOSS_TOP1, LOSS_ENT, LOSS_WITHIN = _lib.LOSS_TOP1, _lib.LOSS_ENT, _lib.LOSS_WITHIN
+
+
+def _teacher_shapes(z, zt, size, spx, mask, bits, flags, host=False):
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    for t, name, dt in ((z, "inputs", torch.float32), (zt, "plbl_inputs", torch.float32), (spx, "superpixels", None),
+                        (mask, "spmasks", torch.uint8), (bits, "bits", torch.int32)):
+        if t is None:
+            continue
+        if host:
+            if t.is_cuda or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous host tensor" % name)
+            if dt is not None and t.dtype != dt:
+                raise TypeError("%s must be %s, got %s" % (name, dt, t.dtype))
+        else:
+            _need(t, name, dt)
+    if (flags & _lib.LOSS_TOP1) and zt is None:
+        raise ValueError("LOSS_TOP1 needs the teacher's logits")
+    if zt is not None and (zt.shape != z.shape or zt.device != z.device):
+        raise ValueError("teacher logits %s do not match the student's %s" % (tuple(zt.shape), tuple(z.shape)))
+    N, C, h, w = z.shape
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if tuple(spx.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W) or bits.shape[0] != N:
+        raise ValueError("shape mismatch between inputs %s%s, superpixels %s, spmasks %s, targets %s"
+                         % (tuple(z.shape), "" if size is None else " at size %s" % ((H, W),), tuple(spx.shape), tuple(mask.shape),
+                            tuple(bits.shape)))
+    return mask, N, C, H, W, bits.shape[1], (0, 0) if size is None else (h, w)
+
+
+def teacher_loss_fwd(z, zt, size, spx, mask, bits, invT, invT_x, plbl_th, flags, reduce_acc=None):
+    """Forward scan with the fourth loss slot: ``flags`` hold LOSS_TOP1 (optionally LOSS_WITHIN; ``zt`` = the eval-mode teacher's
+    logits, shaped as ``z``) or LOSS_ENT (``zt`` None) beside LOSS_CE / LOSS_DECOMP / the group flags.  ``invT``: the ce / group
+    terms' inverse temperature, ``invT_x``: the fourth slot's own.  ``z`` [N,C,H,W] with ``size`` None, or quarter-resolution
+    [N,C,h,w] upsampled in-kernel to ``size``.  Returns (losses f32[4] = ce, mc, group, x; acc i64[16]; gmax or None)."""
+    mask, N, C, H, W, S, (h, w) = _teacher_shapes(z, zt, size, spx, mask, bits, flags)
+    dev = z.device
+    words = _lib.TEACHER_ACC_WORDS
+    if flags & _lib.LOSS_GROUP:
+        buf = torch.zeros(words + N * S * C, dtype=torch.int64, device=dev)
+        acc, gmax = buf[:words], buf[words:].view(N, S, C)
+    else:
+        acc, gmax = torch.zeros(words, dtype=torch.int64, device=dev), None
+    losses = torch.empty(4, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = _stream(z)
+        _lib.check(lib.mas_teacher_loss_fwd(z.data_ptr(), _opt(zt), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), N, C,
+                                            H, W, S, invT, invT_x, plbl_th, flags, _opt(gmax), acc.data_ptr(), st), "mas_teacher_loss_fwd")
+        if gmax is not None:
+            _lib.check(lib.mas_group_finalize(gmax.data_ptr(), gmax.numel(), acc.data_ptr(), st), "mas_group_finalize")
+        if reduce_acc is not None:
+            reduce_acc(acc)
+        _lib.check(lib.mas_teacher_loss_values(acc.data_ptr(), flags, losses.data_ptr(), st), "mas_teacher_loss_values")
+    return losses, acc, gmax
+
+
+def teacher_loss_bwd(z, zt, size, spx, mask, bits, gmax, acc, grad_out, invT, invT_x, plbl_th, flags, want_fix=False):
+    """Backward scan of ``teacher_loss_fwd``: the gradient with respect to ``z`` for upstream gradients ``grad_out`` f32[4]; the
+    teacher is a constant.  At quarter resolution the sums are int64 fixed point (``want_fix`` returns them too)."""
+    mask, N, C, H, W, S, (h, w) = _teacher_shapes(z, zt, size, spx, mask, bits, flags)
+    _need(grad_out, "grad_out", torch.float32)
+    dev = z.device
+    scale = torch.empty(4, dtype=torch.float32, device=dev)
+    fix = None if size is None else torch.zeros(z.shape, dtype=torch.int64, device=dev)
+    dz = torch.empty_like(z)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = _stream(z)
+        _lib.check(lib.mas_teacher_loss_scales(acc.data_ptr(), grad_out.data_ptr(), flags, scale.data_ptr(), st), "mas_teacher_loss_scales")
+        _lib.check(lib.mas_teacher_loss_bwd(z.data_ptr(), _opt(zt), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
+                                            _opt(gmax), scale.data_ptr(), N, C, H, W, S, invT, invT_x, plbl_th, flags, dz.data_ptr(), _opt(fix),
+                                            st), "mas_teacher_loss_bwd")
+        if fix is not None:
+            _lib.check(lib.mas_fix_to_float(fix.data_ptr(), fix.numel(), _lib.GRAD_FRAC, dz.data_ptr(), st), "mas_fix_to_float")
+    return (dz, fix) if want_fix else dz
+
+
+def teacher_loss_reference(z, zt, spx, mask, bits, invT, invT_x, plbl_th, flags, grad_out=None):
+    """Every term of ``teacher_loss_fwd`` / ``_bwd`` at full resolution on HOST tensors: the library's plain loop through
+    csrc/partial_label.h and csrc/teacher_terms.h (``mas_teacher_loss_reference``).  Returns (losses f32[4], acc i64[16], gmax i64
+    [N,S,C] or None) and, with ``grad_out`` f32[4], dz [N,C,H,W] as a fourth value.  Needs no GPU."""
+    mask, N, C, H, W, S, _ = _teacher_shapes(z, zt, None, spx, mask, bits, flags, host=True)
+    acc = torch.zeros(_lib.TEACHER_ACC_WORDS, dtype=torch.int64)
+    gmax = torch.zeros((N, S, C), dtype=torch.int64) if flags & _lib.LOSS_GROUP else None
+    losses = torch.zeros(4, dtype=torch.float32)
+    dz = torch.empty_like(z) if grad_out is not None else None
+    _lib.check(_lib.load().mas_teacher_loss_reference(z.data_ptr(), _opt(zt), spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), N,
+                                                      C, H, W, S, invT, invT_x, plbl_th, flags, _opt(grad_out), acc.data_ptr(), _opt(gmax),
+                                                      losses.data_ptr(), _opt(dz)), "mas_teacher_loss_reference")
+    return (losses, acc, gmax) if dz is None else (losses, acc, gmax, dz)
+
+
+# ------------------------------------------------------------------------------------------------
 # online local-prototype pseudo labels and the cross entropy on them (csrc/online_plbl.hip)
 # ------------------------------------------------------------------------------------------------
 LCE_UNWEIGHTED, LCE_WEIGHTED, LCE_THRESHOLD, LCE_EMPTY_NAN = _lib.LCE_UNWEIGHTED, _lib.LCE_WEIGHTED, _lib.LCE_THRESHOLD, _lib.LCE_EMPTY_NAN

@@ -97,6 +97,10 @@ def get_parser():
     # similarity-weighted soft targets (active_pwce_multi_predignore; refused for every other --method)
     a("--simw_temp", type=float, default=0.1, help="temperature of the softmax over the prototype similarities")
     a('--simw_temp_schedule', action='store_true', default=False, help="hold --simw_temp at 1000 for the first 20000 iterations")
+    # teacher-gated candidate terms (active_joint_multi_predignore_top1plbl / _multient; refused for every other --method)
+    a('--within_filtering', action='store_true', default=False,
+      help="top1plbl: gate on the teacher's top candidate probability divided by its mass on the candidate set")
+    a("--entcoeff", type=float, default=1.0, help="multient: weight of the candidate-entropy term")
     # active learning
     a("--seed", type=int, default=0)
     a("--start_over", action='store_true', default=False)
@@ -158,6 +162,7 @@ def get_parser():
     a('--nseg_list', nargs='+', default=None, type=int)
     a('--plbl_type', type=str, default=None)
     a('--plbl_th', type=float, default=0.0)             # eval_save_naiveplbl: keep labels whose softmax maximum exceeds this (0: the mask)
+    #                                                     top1plbl: a multi-hot pixel counts when the teacher's gate value exceeds this
     a('--loading', default='binary', choices=['binary', 'naive', 'tensor'])
     a('--ignore_size', type=int, default=0)
     a('--mark_topk', type=int, default=-1)
@@ -253,6 +258,13 @@ SIMW_PLBL_METHODS = ('active_onlinesimwplbl_multi_predignore', 'active_pwce_mult
 SIMW_DEFAULTS = dict(simw_temp=0.1, simw_temp_schedule=False)
 
 
+# the teacher-gated candidate terms: top1plbl reads --within_filtering, --plbl_th and the ramp (--lamparam / --lamscale / --dorampup),
+# multient reads --entcoeff
+TEACHER_TERM_METHODS = ('active_joint_multi_predignore_top1plbl', 'active_joint_multi_predignore_multient')
+TOP1_DEFAULTS = dict(within_filtering=False)
+ENT_DEFAULTS = dict(entcoeff=1.0)
+
+
 def _refuse_changed(args, defaults, honoured_by):
     changed = [k for k, v in defaults.items() if getattr(args, k, v) != v]
     if changed:
@@ -283,10 +295,16 @@ def arg_assert(args):
     online = ONLINE_PLBL_METHODS + SIMW_PLBL_METHODS[:1]
     if args.method == SIMW_PLBL_METHODS[0]:         # LocalsimWProtoCE.generate_plbl never reads --weight_wo_proto
         _refuse_changed(args, dict(weight_wo_proto=False), ONLINE_PLBL_METHODS[1:2])
+    elif args.method == TEACHER_TERM_METHODS[0]:    # the ramp of the top-1 term; the prototype flags stay refused
+        _refuse_changed(args, dict(th_wplbl=None, weight_wo_proto=False), online)
     elif args.method not in ONLINE_PLBL_METHODS:
         _refuse_changed(args, ONLINE_PLBL_DEFAULTS, online)
     if args.method != SIMW_PLBL_METHODS[1]:
         _refuse_changed(args, SIMW_DEFAULTS, SIMW_PLBL_METHODS[1:])
+    if args.method != TEACHER_TERM_METHODS[0]:
+        _refuse_changed(args, TOP1_DEFAULTS, TEACHER_TERM_METHODS[:1])
+    if args.method != TEACHER_TERM_METHODS[1]:
+        _refuse_changed(args, ENT_DEFAULTS, TEACHER_TERM_METHODS[1:])
     from ..ops import stage2_threshold_method       # NotImplementedError here; the reference raises it at the first picture
     stage2_threshold_method(getattr(args, 'cosprop_threshold_method', 'median'))            # (trainer/eval_save_cosplbl_prop.py:253)
 

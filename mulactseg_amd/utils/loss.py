@@ -34,6 +34,10 @@ class here                     reference definition
                                inner product with its nearest prototype, negative ones included, or gated by ``--th_wplbl``)
 ``JointLocalProtoWeightingCE`` ``trainer/active_pwce_multi_predignore.py:17-155`` (no hard label: CE against the softmax of
                                the prototype similarities over the candidate classes; one-hot superpixels keep plain CE)
+``TopOnePlbl``                 ``trainer/active_joint_multi_predignore_top1plbl.py:13-82`` (teacher-gated top-1 candidate term)
+``MultiChoiceEnt_``            ``trainer/active_joint_multi_predignore_multient.py:12-70`` (entropy over the candidate set)
+``FusedTeacherTermLoss``       (new) merged-positive CE, group term and one of the two above from ONE scan pair
+                               (``csrc/teacher_terms.h``) -- what the ``top1plbl`` / ``multient`` trainers use
 =============================  =================================================================
 
 Inputs must be ROCm tensors; there is no CPU path (``_lib.MulActSegHipError`` otherwise).
@@ -508,3 +512,136 @@ class JointLocalProtoWeightingCE(nn.Module):
         size = (int(size[0]), int(size[1]))
         softw, live, bits = self.soft_weights(zq_p, featq, targets, superpixels, spmasks, size=size, simw_temp=simw_temp)
         return self._loss(zq, size, superpixels, spmasks, softw, live, bits)
+
+
+class _TeacherLossFn(torch.autograd.Function):
+    """(ce, mc, group, x) = f(z): the scans of ``csrc/losses.hip`` with the fourth loss slot of ``csrc/teacher_terms.h`` -- one forward
+    scan and one backward scan whatever the flags hold.  ``zt`` (the teacher's logits, ``None`` for the entropy) is a constant;
+    ``size`` None: full-resolution tensors, else quarter-resolution ones upsampled inside the scans.  No host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, z, zt, size, targets, superpixels, spmasks, invT, invT_x, plbl_th, flags, sync):
+        z, spx, msk = z.contiguous(), superpixels.contiguous(), spmasks.contiguous()
+        zt = None if zt is None else zt.detach().contiguous()
+        bits = ops.target_bits(targets)
+        losses, acc, gmax = ops.teacher_loss_fwd(z, zt, size, spx, msk, bits, invT, invT_x, plbl_th, flags,
+                                                 reduce_acc=_all_reduce_sum if sync else None)
+        ctx.save_for_backward(z, spx, msk, bits, acc, zt if zt is not None else acc, gmax if gmax is not None else acc)
+        ctx.has = (zt is not None, gmax is not None)
+        ctx.consts = (size, invT, invT_x, plbl_th, flags)
+        ctx.mark_non_differentiable(acc)
+        return losses[0], losses[1], losses[2], losses[3], acc
+
+    @staticmethod
+    def backward(ctx, g_ce, g_mc, g_group, g_x, _g_acc):
+        z, spx, msk, bits, acc, zt, gmax = ctx.saved_tensors
+        size, invT, invT_x, plbl_th, flags = ctx.consts
+        grad_out = torch.stack([g_ce, g_mc, g_group, g_x]).to(torch.float32).contiguous()
+        dz = ops.teacher_loss_bwd(z, zt if ctx.has[0] else None, size, spx, msk, bits, gmax if ctx.has[1] else None, acc, grad_out, invT,
+                                  invT_x, plbl_th, flags)
+        return (dz,) + (None,) * 10
+
+
+def _teacher_run(z, zt, size, targets, superpixels, spmasks, temp, temp_x, plbl_th, flags, sync):
+    if targets.dtype != torch.uint8:
+        targets = targets.to(torch.uint8)
+    size = None if size is None else (int(size[0]), int(size[1]))
+    return _TeacherLossFn.apply(z, zt, size, targets.contiguous(), superpixels, spmasks, ops.inv_temperature(temp),
+                                ops.inv_temperature(temp_x), float(plbl_th), flags, sync)
+
+
+class MultiChoiceEnt_(nn.Module):
+    """Entropy of the softmax restricted to the candidate set, over the selected pixels of multi-hot superpixels, ``sum / (1 + n)`` --
+    reference ``trainer/active_joint_multi_predignore_multient.py:12-70`` (the override that runs; the base class ``MultiChoiceEnt`` of
+    ``utils/loss.py`` does not).  All target columns are used.  As in the reference a candidate whose logit is exactly ``0.0`` drops
+    out of its own softmax (``csrc/teacher_terms.h``)."""
+    _flags = _lib.LOSS_ENT
+
+    def __init__(self, num_class, temperature=1.0, reduction='mean'):
+        super().__init__()
+        if reduction != 'mean':
+            raise NotImplementedError("only reduction='mean' is on the hot path")
+        self.num_class = num_class
+        self.reduction = reduction
+        self.eps = 1e-8
+        self.temp = temperature
+        self.sync_normalisers = True
+
+    def forward(self, inputs, targets, superpixels, spmasks):
+        *_, x, self.last_acc = _teacher_run(inputs, None, None, targets, superpixels, spmasks, self.temp, self.temp, 0.0, self._flags,
+                                            self.sync_normalisers)
+        return x
+
+    def forward_lowres(self, zq, size, targets, superpixels, spmasks):
+        """The same value from the model's quarter-resolution logits, upsampled x4 bilinearly per selected pixel inside the scans."""
+        *_, x, self.last_acc = _teacher_run(zq, None, size, targets, superpixels, spmasks, self.temp, self.temp, 0.0, self._flags,
+                                            self.sync_normalisers)
+        return x
+
+
+class TopOnePlbl(MultiChoiceEnt_):
+    """Self-training on the candidate set: ``-log max_{c in Y} p_c`` on the selected multi-hot pixels whose TEACHER (``plbl_inputs``,
+    an eval-mode forward of the same weights, a constant of the gradient) is confident, ``filtering_threshold < max_{c in Y} t_c``
+    (``within_filtering``: the maximum divided by the teacher's mass on the candidates); ``sum / (1 + n_counted)`` -- reference
+    ``trainer/active_joint_multi_predignore_top1plbl.py:13-82``.  On a tie the gradient goes to the lowest class index."""
+    _flags = _lib.LOSS_TOP1
+
+    def __init__(self, num_class, within_filtering=False, filtering_threshold=0, temperature=1.0, reduction='mean'):
+        super().__init__(num_class, temperature, reduction)
+        self.plbl_th = filtering_threshold
+        self.within_filtering = within_filtering
+
+    def _f(self):
+        return self._flags | (_lib.LOSS_WITHIN if self.within_filtering else 0)
+
+    def forward(self, inputs, plbl_inputs, targets, superpixels, spmasks):
+        *_, x, self.last_acc = _teacher_run(inputs, plbl_inputs, None, targets, superpixels, spmasks, self.temp, self.temp, self.plbl_th,
+                                            self._f(), self.sync_normalisers)
+        return x
+
+    def forward_lowres(self, zq, zq_teacher, size, targets, superpixels, spmasks):
+        """``zq`` / ``zq_teacher`` [N,C,h,w]: the training-mode and the eval-mode quarter-resolution logits; both are interpolated in
+        registers with the same taps -- no ``[N,C,H,W]`` tensor of either exists."""
+        *_, x, self.last_acc = _teacher_run(zq, zq_teacher, size, targets, superpixels, spmasks, self.temp, self.temp, self.plbl_th,
+                                            self._f(), self.sync_normalisers)
+        return x
+
+
+class FusedTeacherTermLoss(nn.Module):
+    """(pos, group, x) of the ``top1plbl`` / ``multient`` trainers from ONE forward scan and ONE backward scan: the merged-positive CE
+    (``MultiChoiceCE_``) and the group term (``GroupMultiLabelCE_``) at their shared temperature, and ``x`` = ``TopOnePlbl``
+    (``term='top1'``) or ``MultiChoiceEnt_`` (``term='ent'``) at ``term_temperature`` -- each value equal, bit for bit, to the
+    stand-alone module's.  Built like ``FusedPartialLabelLoss``."""
+
+    def __init__(self, num_superpixel, term, group_temperature=1.0, multi_temperature=1.0, term_temperature=1.0, within_filtering=False,
+                 filtering_threshold=0.0, sync_normalisers=True):
+        super().__init__()
+        if term not in ('top1', 'ent'):
+            raise ValueError("term must be 'top1' or 'ent', got %r" % (term,))
+        if group_temperature != multi_temperature:
+            raise ValueError("the fused scan shares one softmax: group_ce_temp must equal multi_ce_temp "
+                             "(both 0.1 in the reference scripts)")
+        self.num_superpixel = num_superpixel
+        self.term = term
+        self.temp = multi_temperature
+        self.term_temp = term_temperature
+        self.plbl_th = filtering_threshold
+        self.sync_normalisers = sync_normalisers
+        self.flags = _lib.LOSS_CE | _lib.LOSS_GROUP | (_lib.LOSS_ENT if term == 'ent' else
+                                                       _lib.LOSS_TOP1 | (_lib.LOSS_WITHIN if within_filtering else 0))
+
+    def _run(self, z, zt, size, targets, superpixels, spmasks):
+        if targets.shape[1] != self.num_superpixel:
+            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        if (zt is None) != (self.term == 'ent'):
+            raise ValueError("the top1 term needs the teacher's logits, the entropy takes none")
+        pos, _, group, x, self.last_acc = _teacher_run(z, zt, size, targets, superpixels, spmasks, self.temp, self.term_temp, self.plbl_th,
+                                                       self.flags, self.sync_normalisers)
+        return pos, group, x
+
+    def forward(self, inputs, plbl_inputs, targets, superpixels, spmasks):
+        """``plbl_inputs``: the teacher's logits (``None`` for ``term='ent'``)."""
+        return self._run(inputs, plbl_inputs, None, targets, superpixels, spmasks)
+
+    def forward_lowres(self, zq, zq_teacher, size, targets, superpixels, spmasks):
+        return self._run(zq, zq_teacher, size, targets, superpixels, spmasks)
