@@ -62,7 +62,8 @@ extern "C" {
  * mas_online_plbl_reference, then mas_online_soft_weights, mas_soft_ce_fwd_lowres / _bwd_lowres and mas_simw_plbl_reference with the
  * MAS_OPL_WEIGHT_SIM and MAS_LCE_SIGNED flag bits (a library built before them answers MAS_ERR_RANGE to either bit), then
  * mas_teacher_loss_fwd / _bwd / _values / _scales and mas_teacher_loss_reference with the MAS_LOSS_TOP1 / MAS_LOSS_ENT /
- * MAS_LOSS_WITHIN flag bits (the mas_partial_loss_* entry points answer MAS_ERR_RANGE to them): new entry
+ * MAS_LOSS_WITHIN flag bits (the mas_partial_loss_* entry points answer MAS_ERR_RANGE to them), then mas_wgroup_loss_fwd / _bwd and
+ * mas_wgroup_loss_reference with the MAS_LOSS_WGROUP flag bit (a library built before them answers MAS_ERR_RANGE to the bit): new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -258,6 +259,34 @@ int mas_teacher_loss_reference(const float* z, const float* zt, const void* spx,
                                int N, int C, int H, int W, int S, float invT, float invT_x, float plbl_th, int flags,
                                const float* grad_out4 /* [4] or NULL */, uint64_t* acc /* [16] += */, uint64_t* gmax /* or NULL */,
                                float* losses4 /* [4] or NULL */, float* dz /* or NULL */);
+
+/* ---------------------------------------------------------------------------------------------
+ * Teacher-weighted group term (csrc/teacher_terms.h, `wgroup`; trainer/active_joint_multi_predignore_wgroup.py:12-82,
+ * WeightedGroupMultiLabelCE): the group loss with every counted (superpixel, class) entry multiplied by the eval-mode teacher's own
+ * maximum probability of that class over the selected pixels of that superpixel, at the group temperature; the teacher is a constant.
+ *   MAS_LOSS_WGROUP  valid only with MAS_LOSS_GROUP and a non-NULL zt (either missing: MAS_ERR_RANGE); combines with MAS_LOSS_CE,
+ *                    MAS_LOSS_DECOMP and MAS_LOSS_GROUP_ONLY_MULTI, any other bit is MAS_ERR_RANGE.  The mas_partial_loss_* and
+ *                    mas_teacher_loss_* entry points answer MAS_ERR_RANGE to the bit.
+ * The argument lists are those of mas_teacher_loss_fwd / _bwd without invT_x and plbl_th (the term has no temperature of its own and
+ * no gate) and with tmax u32 [N,S,C], caller-zeroed like gmax: the teacher's table, probability bits.  h = w = 0: z and zt are
+ * [N,C,H,W]; otherwise quarter-resolution [N,C,h,w], upsampled per selected pixel.  acc: the EIGHT caller-zeroed words of
+ * mas_partial_loss_fwd.  mas_wgroup_loss_fwd runs the scan AND the weighted finalize, so acc is complete on return; losses (may be
+ * NULL) = (ce, mc, group) written by the finalize's last workgroup, the value mas_loss_values gives (sum / (1 + n) as before).
+ * Backward: scale [3] from mas_loss_scales; dz [N,C,H,W] written completely, or dzq_fix as mas_partial_loss_bwd_lowres. */
+#define MAS_LOSS_WGROUP 1024
+int mas_wgroup_loss_fwd(const float* z, const float* zt, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask,
+                        const uint32_t* bits, int N, int C, int H, int W, int S, float invT, int flags, uint64_t* gmax /* [N,S,C] */,
+                        uint32_t* tmax /* [N,S,C] */, uint64_t* acc /* [8] */, float* losses /* [3] or NULL */, void* stream);
+int mas_wgroup_loss_bwd(const float* z, const float* zt, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask,
+                        const uint32_t* bits, const uint64_t* gmax, const uint32_t* tmax, const float* scale /* [3] */, int N, int C, int H,
+                        int W, int S, float invT, int flags, float* dz, int64_t* dzq_fix, void* stream);
+/* The CPU-side statement: HOST pointers, full resolution, no device touched.  acc [8] +=, gmax and tmax caller-zeroed and filled,
+ * losses [3] (may be NULL), dz (may be NULL; needs grad_out [3]) = what mas_loss_scales + mas_wgroup_loss_bwd write.  The table maxima
+ * do not depend on the order, so the kernels are tested against it bit for bit. */
+int mas_wgroup_loss_reference(const float* z, const float* zt, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits,
+                              int N, int C, int H, int W, int S, float invT, int flags, const float* grad_out /* [3] or NULL */,
+                              uint64_t* acc /* [8] += */, uint64_t* gmax, uint32_t* tmax, float* losses /* [3] or NULL */,
+                              float* dz /* or NULL */);
 
 /* The CPU-side statement of csrc/partial_label.h: every pointer is a HOST pointer, no device is touched.  A plain loop over the selected
  * pixels for the CE-family flags (MAS_LOSS_CE, optionally with MAS_LOSS_DECOMP and one of MAS_LOSS_RC / MAS_LOSS_TOPONE; any other bit

@@ -20,6 +20,7 @@ LOSS_RC, LOSS_TOPONE = 32, 64       # the multi-hot pixel term of the CE sums (c
 LOSS_TOP1, LOSS_ENT, LOSS_WITHIN = 128, 256, 512     # the fourth loss slot of the mas_teacher_loss_* entry points (csrc/teacher_terms.h)
 ACC_WORDS = 8
 TEACHER_ACC_WORDS, ACC_SUM_X, ACC_N_X = 16, 8, 9
+LOSS_WGROUP = 1024      # the teacher-weighted group term of the mas_wgroup_loss_* entry points (csrc/teacher_terms.h, wgroup)
 GRAD_FRAC = 44
 MS_MAX_SOURCES = 16
 
@@ -172,6 +173,9 @@ SIGNATURES = {
     "mas_teacher_loss_scales": (_i, [_vp, _vp, _i, _vp, _vp]),
     "mas_teacher_loss_bwd": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp]),
     "mas_teacher_loss_reference": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mas_wgroup_loss_fwd": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mas_wgroup_loss_bwd": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "mas_wgroup_loss_reference": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mas_adamw_job_bytes": (_c.c_size_t, []),
     "mas_adamw_max_groups": (_i, []),
     "mas_adamw_job": (_c.c_uint, [_vp, _vp, _vp, _vp, _vp, _c.c_longlong, _i, _c.c_uint]),

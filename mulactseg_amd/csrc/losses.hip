@@ -19,6 +19,12 @@
 //                        teacher_terms.h, beside the merged-positive and group terms.  Kernels of their own, so every
 //                        k_partial_loss_* instantiation compiles to what it was.
 //   mas_teacher_loss_reference   all four terms (the group table included) and dz on HOST pointers.
+//   the MAS_TT_WGROUP instantiations       the same two scan bodies with the TEACHER-WEIGHTED group term (teacher_terms.h, wgroup): a pixel
+//                        that contributes to the group table also soft-maxes the teacher's row and raises a second, u32 table `tmax`
+//                        [N,S,C] of the teacher's per-(superpixel, class) maximum (LDS table beside the student's, same slot keys, same
+//                        overflow path); k_group_finalize<true> weights every entry's -log by it, the backward's arg-pixel gather
+//                        reads it.  No fourth slot, eight accumulator words.
+//   mas_wgroup_loss_reference    the same on HOST pointers, both tables included.
 //
 // Reference semantics: trainer/active_joint_multi_predignore_lossdecomp.py:21-72 (OnehotCEMultihotChoice),
 // trainer/active_joint_multi_predignore_mclossablation2.py:22-79 (GroupMultiLabelCE_onlymulti),
@@ -42,10 +48,11 @@ enum { ACC_SUM_X = 8, ACC_N_X = 9 };
 
 // what the teacher-term kernels take beside the arguments of the plain scans (teacher_terms.h); TT == MAS_TT_NONE bodies never read it
 struct TeacherIn {
-    const float* zt;        // teacher logits, laid out as z (top1; NULL for ent)
+    const float* zt;        // teacher logits, laid out as z (top1, wgroup; NULL for ent)
     float invT;             // the term's own inverse temperature
     float th;               // plbl_th
     int within;             // within_filtering
+    unsigned* tmax;         // wgroup: the teacher's table [N,S,C] of probability bits (written by the forward, read by the backward)
 };
 
 __device__ __forceinline__ mas_u64 pack_max(float p, unsigned pix) {
@@ -219,13 +226,16 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
                                                                 float invT, int flags, int tiles_x, int tiles_y,
                                                                 mas_u64* __restrict__ gmax, mas_u64* __restrict__ acc, const LowRes lr,
                                                                 const TeacherIn te) {
-    constexpr int NR = TT ? 7 : 5;              // scalar accumulators of a workgroup
+    constexpr bool XS = TT == MAS_TT_TOP1 || TT == MAS_TT_ENT;     // a fourth loss slot
+    constexpr bool WG = TT == MAS_TT_WGROUP;                        // the teacher's table beside the student's
+    constexpr int NR = XS ? 7 : 5;              // scalar accumulators of a workgroup
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     mas_u64* t_max = reinterpret_cast<mas_u64*>(smem);                       // [kSlots * C]
     int* t_keys = reinterpret_cast<int*>(smem + sizeof(mas_u64) * kSlots * C);  // [kSlots]
     mas_u64* s_red = reinterpret_cast<mas_u64*>(smem + sizeof(mas_u64) * kSlots * C + sizeof(int) * kSlots);  // [4][NR]
     int* qcount = reinterpret_cast<int*>(s_red + 4 * NR);
     unsigned short* queue = reinterpret_cast<unsigned short*>(qcount + 2);     // [kTilePx]
+    unsigned* t_tmax = reinterpret_cast<unsigned*>(queue + kTilePx);           // [kSlots * C] (WG only: fwd_smem_bytes)
 
     const bool do_ce = flags & MAS_LOSS_CE;
     const bool do_group = flags & MAS_LOSS_GROUP;
@@ -236,6 +246,8 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
     if (do_group) {
         for (int i = threadIdx.x; i < kSlots; i += kThreads) t_keys[i] = -1;
         for (int i = threadIdx.x; i < kSlots * C; i += kThreads) t_max[i] = 0;
+        if (WG)
+            for (int i = threadIdx.x; i < kSlots * C; i += kThreads) t_tmax[i] = 0;
     }
     __syncthreads();
 
@@ -245,11 +257,12 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
     const int n = bid / tiles_y;
     const int HW = H * W;
     const float* zb = z + (size_t)n * C * (LOWRES ? lr.h * lr.w : HW);
-    const float* ztb = (TT == MAS_TT_TOP1) ? te.zt + (size_t)n * C * (LOWRES ? lr.h * lr.w : HW) : nullptr;
+    const float* ztb = (TT == MAS_TT_TOP1 || WG) ? te.zt + (size_t)n * C * (LOWRES ? lr.h * lr.w : HW) : nullptr;
     const IdT* sb = spx + (size_t)n * HW;
     const unsigned char* mb = mask + (size_t)n * HW;
     const unsigned* bb = bits + (size_t)n * S;
     mas_u64* gm = gmax + (size_t)n * S * C;
+    unsigned* tm = WG ? te.tmax + (size_t)n * S * C : nullptr;
     const int lane = threadIdx.x & (MAS_WAVE - 1);
     const int wave = threadIdx.x / MAS_WAVE;
 
@@ -271,7 +284,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
         const unsigned Y = tce ? (1u << id) : bb[id];
         const int nb = __popc(Y);
         if (nb == 0) { n_empty += 1; continue; }
-        if (TT != MAS_TT_NONE && nb > 1) {
+        if (XS && nb > 1) {
             float u[CT];
             unsigned M;
             if (teacher_term_probs<CT, EXACT, LOWRES, TT>(ztb, v, C, HW, pix, py, px, lr, Y, te, u, M)) {
@@ -310,6 +323,19 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
                     else atomicMax(&gm[(size_t)id * C + c], w);
                 }
             }
+            if (WG) {
+                // the teacher's row of the same pixel (same taps / same address) replaces the student's probabilities, which are done
+                load_logits<CT, EXACT, LOWRES>(ztb, C, HW, pix, py, px, lr, v, t_y, t_x);
+                const float rinv = mas_softmax_regs<CT, EXACT>(v, C, invT);
+#pragma unroll
+                for (int c = 0; c < CT; ++c) {
+                    if ((EXACT || c < C) && ((Y >> c) & 1u)) {
+                        const unsigned w = mas_f2u(v[c] * rinv);
+                        if (s >= 0) atomicMax(&t_tmax[s * C + c], w);
+                        else atomicMax(&tm[(size_t)id * C + c], w);
+                    }
+                }
+            }
         }
     }
 
@@ -335,6 +361,15 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
                 atomicMax(&gm[(size_t)t_keys[s] * C + (i - s * C)], w);
             }
         }
+        if (WG) {
+            for (int i = threadIdx.x; i < kSlots * C; i += kThreads) {
+                const unsigned w = t_tmax[i];
+                if (w) {
+                    const int s = i / C;
+                    atomicMax(&tm[(size_t)t_keys[s] * C + (i - s * C)], w);
+                }
+            }
+        }
     }
 }
 
@@ -343,9 +378,11 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_fwd(const float* __re
 constexpr int ACC_DONE = 7;
 __host__ __device__ __forceinline__ void loss_values_of(const mas_u64* acc, int flags, const float* w, float* out);
 
-__global__ __launch_bounds__(kThreads) void k_group_finalize(const mas_u64* __restrict__ gmax, long long n_entries,
-                                                              mas_u64* __restrict__ acc, int flags, const float* __restrict__ w,
-                                                              float* __restrict__ values) {
+// WG: the weighted form (teacher_terms.h, wgroup) -- every counted entry's -log is multiplied by the teacher's maximum tmax[i]
+template <bool WG>
+__global__ __launch_bounds__(kThreads) void k_group_finalize(const mas_u64* __restrict__ gmax, const unsigned* __restrict__ tmax,
+                                                              long long n_entries, mas_u64* __restrict__ acc, int flags,
+                                                              const float* __restrict__ w, float* __restrict__ values) {
     __shared__ mas_u64 s_red[kThreads / MAS_WAVE][2];
     __shared__ int s_last;
     mas_u64 sum = 0, cnt = 0;
@@ -353,7 +390,7 @@ __global__ __launch_bounds__(kThreads) void k_group_finalize(const mas_u64* __re
         const mas_u64 w64 = gmax[i];
         const unsigned pb = (unsigned)(w64 >> 32);
         if (pb) {            // a (superpixel, class) with target bit set whose max prob is non-zero
-            const float l = -mas_logf(mas_u2f(pb) + 1e-8f);
+            const float l = WG ? mas_tt_wg_loss(mas_u2f(tmax[i]), mas_u2f(pb)) : -mas_logf(mas_u2f(pb) + 1e-8f);
             sum += mas_fix(l, MAS_LOSS_FRAC);
             cnt += 1;
         }
@@ -515,7 +552,10 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
     const int HW = H * W;
     const int hw_in = LOWRES ? lr.h * lr.w : HW;
     const float* zb = z + (size_t)n * C * hw_in;
+    constexpr bool XS = TT == MAS_TT_TOP1 || TT == MAS_TT_ENT;     // a fourth loss slot
+    constexpr bool WG = TT == MAS_TT_WGROUP;                        // arg-pixel entries weighted by the teacher's table
     const float* ztb = (TT == MAS_TT_TOP1) ? te.zt + (size_t)n * C * hw_in : nullptr;
+    const unsigned* tm = WG ? te.tmax + (size_t)n * S * C : nullptr;
     float* db = LOWRES ? nullptr : dz + (size_t)n * C * HW;
     mas_u64* qb = LOWRES ? reinterpret_cast<mas_u64*>(dz) + (size_t)n * C * hw_in : nullptr;
     const IdT* sb = spx + (size_t)n * HW;
@@ -528,7 +568,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
     if (scale) { sc3[0] = scale[0]; sc3[1] = scale[1]; sc3[2] = scale[2]; }
     else loss_scales_of(acc, grad, gw, flags, sc3);
     const float a_ce = sc3[0] * invT, a_mc = sc3[1] * invT, g6 = sc3[2] * invT;
-    const float a_x = (TT != MAS_TT_NONE) ? scale[3] * te.invT : 0.0f;
+    const float a_x = XS ? scale[3] * te.invT : 0.0f;
 
     // phase 1: dz = 0 over the whole tile (streaming 16-B stores) while the selected pixels are compacted
     tile_compact<CT, EXACT, VEC, !LOWRES>(mb, C, H, W, HW, tx, ty, queue, qcount, db);
@@ -562,12 +602,12 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
         LTap t_y, t_x;
         load_logits<CT, EXACT, LOWRES>(zb, C, HW, pix, py, px, lr, v, t_y, t_x);
         // the fourth slot: u = the term's own probabilities of this pixel, (gx, ux) the per-pixel constants of its gradient
-        float u[TT != MAS_TT_NONE ? CT : 1];
+        float u[XS ? CT : 1];
         unsigned M = 0;
         bool xon = false;
         mas_pl_grad_ctx gx = {};
         float ux = 0.0f;
-        if constexpr (TT != MAS_TT_NONE) {
+        if constexpr (XS) {
             if (nb > 1) xon = teacher_term_probs<CT, EXACT, LOWRES, TT>(ztb, v, C, HW, pix, py, px, lr, Y, te, u, M);
             if (xon) {
                 if (TT == MAS_TT_TOP1) gx = mas_pl_grad_prepare(u, CT, EXACT ? CT : C, Y, MAS_PL_TOPONE, a_x);
@@ -605,7 +645,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
                     const mas_u64 w = gm[(size_t)id * C + c];
                     if ((unsigned)w == key && (unsigned)(w >> 32) != 0u) {
                         A |= 1u << c;
-                        t[c] = -(g6 / (v[c] + 1e-8f));
+                        t[c] = WG ? mas_tt_wg_coef(g6, mas_u2f(tm[(size_t)id * C + c]), v[c]) : -(g6 / (v[c] + 1e-8f));
                         ug = ug + t[c] * v[c];
                     }
                 }
@@ -622,7 +662,7 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
                     if ((A >> c) & 1u) d = d + t[c] * p;
                     d = d - p * ug;
                 }
-                if constexpr (TT != MAS_TT_NONE) {
+                if constexpr (XS) {
                     if (xon) d = d + ((TT == MAS_TT_TOP1) ? mas_pl_grad(gx, MAS_PL_TOPONE, u[c], (int)((Y >> c) & 1u), c)
                                                           : mas_tt_ent_grad(a_x, ux, u[c], (int)((M >> c) & 1u)));
                 }
@@ -651,9 +691,11 @@ __global__ __launch_bounds__(kThreads) void k_partial_loss_bwd(const float* __re
     }
 }
 
-inline size_t fwd_smem_bytes(int C, bool teacher = false) {
-    return sizeof(mas_u64) * kSlots * (size_t)C + sizeof(int) * kSlots + sizeof(mas_u64) * 4 * (teacher ? 7 : 5) + sizeof(int) * 2 +
-           sizeof(unsigned short) * kTilePx;
+// tt: the MAS_TT_* value of the instantiation -- a fourth slot reduces seven scalars, wgroup appends the teacher's u32 table
+inline size_t fwd_smem_bytes(int C, int tt = MAS_TT_NONE) {
+    const bool xs = tt == MAS_TT_TOP1 || tt == MAS_TT_ENT;
+    return sizeof(mas_u64) * kSlots * (size_t)C + sizeof(int) * kSlots + sizeof(mas_u64) * 4 * (xs ? 7 : 5) + sizeof(int) * 2 +
+           sizeof(unsigned short) * kTilePx + (tt == MAS_TT_WGROUP ? sizeof(unsigned) * kSlots * (size_t)C : 0);
 }
 
 struct LossArgs {
@@ -662,8 +704,9 @@ struct LossArgs {
     mas_u64* gmax; mas_u64* acc; const float* scale; float* dz;
     int h = 0, w = 0;           // > 0: `z` is the quarter-resolution tensor [N,C,h,w] (LOWRES kernels)
     const float* grad = nullptr; const float* gw = nullptr;     // backward with scale == NULL: upstream gradient(s) and optional weights
-    TeacherIn te = {nullptr, 0.f, 0.f, 0};                      // MAS_LOSS_TOP1 / MAS_LOSS_ENT (`scale` then holds four factors)
+    TeacherIn te = {nullptr, 0.f, 0.f, 0, nullptr};             // MAS_LOSS_TOP1 / MAS_LOSS_ENT (`scale` then holds four factors), MAS_LOSS_WGROUP
     bool teacher = false;       // set by the mas_teacher_loss_* entry points: `acc` has 16 words and `te` is filled in
+    bool wgroup = false;        // set by the mas_wgroup_loss_* entry points: `te.zt` and `te.tmax` are filled in, `acc` has 8 words
 };
 
 template <int CT, bool EXACT, typename IdT, bool PLX, int TT = MAS_TT_NONE>
@@ -680,7 +723,7 @@ int launch_loss(const LossArgs& a, bool backward, hipStream_t st) {
 #define MAS_LAUNCH_LOSS(VECV, LOWV)                                                                                                     \
     do {                                                                                                                                \
         if (!backward)                                                                                                                  \
-            hipLaunchKernelGGL((k_partial_loss_fwd<CT, EXACT, IdT, VECV, LOWV, PLX, TT>), grid, block, fwd_smem_bytes(a.C, TT != 0), st, a.z, ids, \
+            hipLaunchKernelGGL((k_partial_loss_fwd<CT, EXACT, IdT, VECV, LOWV, PLX, TT>), grid, block, fwd_smem_bytes(a.C, TT), st, a.z, ids, \
                                a.mask, a.bits, a.C, a.H, a.W, a.S, a.invT, a.flags, tiles_x, tiles_y, a.gmax, a.acc, lr, a.te);           \
         else                                                                                                                            \
             hipLaunchKernelGGL((k_partial_loss_bwd<CT, EXACT, IdT, VECV, LOWV, PLX, TT>), grid, block, 0, st, a.z, ids, a.mask, a.bits, a.gmax, \
@@ -696,7 +739,8 @@ template <int CT, bool EXACT>
 int dispatch_loss_ids(const LossArgs& a, int spx_dtype, bool backward, hipStream_t st) {
     if (const int tt = mas_tt_mode(a.flags)) {
 #define MAS_TEACHER_BY_TERM(IDT) (tt == MAS_TT_TOP1 ? launch_loss<CT, EXACT, IDT, false, MAS_TT_TOP1>(a, backward, st) \
-                                                    : launch_loss<CT, EXACT, IDT, false, MAS_TT_ENT>(a, backward, st))
+                                  : (tt == MAS_TT_ENT ? launch_loss<CT, EXACT, IDT, false, MAS_TT_ENT>(a, backward, st)     \
+                                                      : launch_loss<CT, EXACT, IDT, false, MAS_TT_WGROUP>(a, backward, st)))
         switch (spx_dtype) {
             case MAS_ID_I64: return MAS_TEACHER_BY_TERM(long long);
             case MAS_ID_I32: return MAS_TEACHER_BY_TERM(int);
@@ -720,6 +764,7 @@ int dispatch_loss_ids(const LossArgs& a, int spx_dtype, bool backward, hipStream
 // MAS_LOSS_RC / MAS_LOSS_TOPONE name the multi-hot term of the CE sums: one of them at most, with MAS_LOSS_CE, never with MAS_LOSS_TCE
 inline bool loss_flags_ok(int flags) {
     if (flags & (MAS_LOSS_TOP1 | MAS_LOSS_ENT | MAS_LOSS_WITHIN)) return false;     // (the mas_teacher_loss_* entry points only)
+    if (flags & MAS_LOSS_WGROUP) return false;                                      // (the mas_wgroup_loss_* entry points only)
     const int m = flags & (MAS_LOSS_RC | MAS_LOSS_TOPONE);
     if (!m) return true;
     return m != (MAS_LOSS_RC | MAS_LOSS_TOPONE) && (flags & MAS_LOSS_CE) && !(flags & MAS_LOSS_TCE);
@@ -734,8 +779,14 @@ inline bool teacher_flags_ok(int flags) {
     return !(flags & ~(MAS_LOSS_CE | MAS_LOSS_DECOMP | MAS_LOSS_GROUP | MAS_LOSS_GROUP_ONLY_MULTI | MAS_LOSS_TOP1 | MAS_LOSS_ENT | MAS_LOSS_WITHIN));
 }
 
+// MAS_LOSS_WGROUP: with MAS_LOSS_GROUP, beside MAS_LOSS_CE, MAS_LOSS_DECOMP and MAS_LOSS_GROUP_ONLY_MULTI only
+inline bool wgroup_flags_ok(int flags) {
+    if (!(flags & MAS_LOSS_WGROUP) || !(flags & MAS_LOSS_GROUP)) return false;
+    return !(flags & ~(MAS_LOSS_CE | MAS_LOSS_DECOMP | MAS_LOSS_GROUP | MAS_LOSS_GROUP_ONLY_MULTI | MAS_LOSS_WGROUP));
+}
+
 int dispatch_loss(const LossArgs& a, int spx_dtype, bool backward, hipStream_t st) {
-    if (!(a.teacher ? teacher_flags_ok(a.flags) : loss_flags_ok(a.flags))) return MAS_ERR_RANGE;
+    if (!(a.wgroup ? wgroup_flags_ok(a.flags) : (a.teacher ? teacher_flags_ok(a.flags) : loss_flags_ok(a.flags)))) return MAS_ERR_RANGE;
     if (a.N <= 0 || a.H <= 0 || a.W <= 0 || a.S <= 0 || (long long)a.H * a.W > 0x7fffffffLL / 2) return MAS_ERR_SHAPE;
     if (a.C < 2 || a.C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
     switch (a.C) {
@@ -774,8 +825,8 @@ extern "C" int mas_group_finalize(const uint64_t* gmax, int64_t n_entries, uint6
     if (n_entries <= 0) return MAS_ERR_SHAPE;
     long long nblk = (n_entries + kThreads - 1) / kThreads;
     if (nblk > 1024) nblk = 1024;
-    hipLaunchKernelGGL(k_group_finalize, dim3((unsigned)nblk), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const mas_u64*>(gmax), (long long)n_entries, reinterpret_cast<mas_u64*>(acc), 0,
+    hipLaunchKernelGGL(k_group_finalize<false>, dim3((unsigned)nblk), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const mas_u64*>(gmax), static_cast<const unsigned*>(nullptr), (long long)n_entries, reinterpret_cast<mas_u64*>(acc), 0,
                        static_cast<const float*>(nullptr), static_cast<float*>(nullptr));
     return mas_launch_status();
 }
@@ -916,7 +967,8 @@ extern "C" int mas_partial_loss_fwd_fused(const float* z, int h, int w, const vo
         //  L2 for 40 us, measured; 64 x 256 threads x 10 entries each is 4 us)
         long long nblk = (n_entries + 8 * kThreads - 1) / (8 * kThreads);
         if (nblk > 64) nblk = 64;
-        hipLaunchKernelGGL(k_group_finalize, dim3((unsigned)nblk), dim3(kThreads), 0, st, gmax, n_entries, acc, flags, weights, losses);
+        hipLaunchKernelGGL(k_group_finalize<false>, dim3((unsigned)nblk), dim3(kThreads), 0, st, gmax, static_cast<const unsigned*>(nullptr),
+                           n_entries, acc, flags, weights, losses);
     } else if (losses) {
         if (weights) hipLaunchKernelGGL(k_loss_values_weighted, dim3(1), dim3(64), 0, st, acc, flags, weights, losses);
         else hipLaunchKernelGGL(k_loss_values, dim3(1), dim3(64), 0, st, acc, flags, losses);
@@ -1232,6 +1284,155 @@ extern "C" int mas_teacher_loss_reference(const float* z, const float* zt, const
                 }
             }
             if (losses4) teacher_values_of(a64, flags, losses4);
+        }
+    }
+    return 0;
+}
+
+// ---- teacher-weighted group term (teacher_terms.h, wgroup): the MAS_TT_WGROUP scans and the weighted finalize ------------------------------
+// Reference: trainer/active_joint_multi_predignore_wgroup.py:12-82 (WeightedGroupMultiLabelCE).
+namespace {
+inline int wgroup_args_ok(const float* z, const float* zt, int h, int w, const void* spx, const uint8_t* mask, const uint32_t* bits,
+                          const uint64_t* gmax, const uint32_t* tmax, int H, int W, int flags) {
+    if (!wgroup_flags_ok(flags)) return MAS_ERR_RANGE;
+    if (!zt) return MAS_ERR_RANGE;              // (the flag without a teacher: a combination, not a missing buffer)
+    if (!z || !spx || !mask || !bits || !gmax || !tmax) return MAS_ERR_NULL;
+    if ((h > 0) != (w > 0) || h < 0 || h > H || w > W) return MAS_ERR_SHAPE;
+    return 0;
+}
+}  // namespace
+
+extern "C" int mas_wgroup_loss_fwd(const float* z, const float* zt, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask,
+                                   const uint32_t* bits, int N, int C, int H, int W, int S, float invT, int flags, uint64_t* gmax,
+                                   uint32_t* tmax, uint64_t* acc, float* losses, void* stream) {
+    if (int e = wgroup_args_ok(z, zt, h, w, spx, mask, bits, gmax, tmax, H, W, flags)) return e;
+    if (!acc) return MAS_ERR_NULL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    LossArgs a{z, spx, mask, bits, N, C, H, W, S, invT, flags, reinterpret_cast<mas_u64*>(gmax), reinterpret_cast<mas_u64*>(acc), nullptr,
+               nullptr, h > 0 ? h : 0, h > 0 ? w : 0};
+    a.te = TeacherIn{zt, invT, 0.f, 0, tmax};
+    a.wgroup = true;
+    if (int e = dispatch_loss(a, spx_dtype, false, st)) return e;
+    const long long n_entries = (long long)N * S * C;
+    long long nblk = (n_entries + 8 * kThreads - 1) / (8 * kThreads);       // (few workgroups: see mas_partial_loss_fwd_fused)
+    if (nblk > 64) nblk = 64;
+    hipLaunchKernelGGL(k_group_finalize<true>, dim3((unsigned)nblk), dim3(kThreads), 0, st, reinterpret_cast<const mas_u64*>(gmax),
+                       static_cast<const unsigned*>(tmax), n_entries, reinterpret_cast<mas_u64*>(acc), flags & ~MAS_LOSS_WGROUP,
+                       static_cast<const float*>(nullptr), losses);
+    return mas_launch_status();
+}
+
+extern "C" int mas_wgroup_loss_bwd(const float* z, const float* zt, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask,
+                                   const uint32_t* bits, const uint64_t* gmax, const uint32_t* tmax, const float* scale, int N, int C, int H,
+                                   int W, int S, float invT, int flags, float* dz, int64_t* dzq_fix, void* stream) {
+    if (int e = wgroup_args_ok(z, zt, h, w, spx, mask, bits, gmax, tmax, H, W, flags)) return e;
+    if (!scale || (h > 0 ? !dzq_fix : !dz)) return MAS_ERR_NULL;
+    LossArgs a{z, spx, mask, bits, N, C, H, W, S, invT, flags, const_cast<mas_u64*>(reinterpret_cast<const mas_u64*>(gmax)), nullptr, scale,
+               h > 0 ? reinterpret_cast<float*>(dzq_fix) : dz, h > 0 ? h : 0, h > 0 ? w : 0};
+    a.te = TeacherIn{zt, invT, 0.f, 0, const_cast<unsigned*>(static_cast<const unsigned*>(tmax))};
+    a.wgroup = true;
+    return dispatch_loss(a, spx_dtype, true, static_cast<hipStream_t>(stream));
+}
+
+// ---- the CPU-side statement: host pointers, a plain loop through partial_label.h and teacher_terms.h -- the merged-positive sums, both
+// tables, the weighted finalize and dz in the operation order of the MAS_TT_WGROUP instantiations.  No device is touched.
+extern "C" int mas_wgroup_loss_reference(const float* z, const float* zt, const void* spx, int spx_dtype, const uint8_t* mask,
+                                         const uint32_t* bits, int N, int C, int H, int W, int S, float invT, int flags, const float* grad_out,
+                                         uint64_t* acc, uint64_t* gmax, uint32_t* tmax, float* losses, float* dz) {
+    if (int e = wgroup_args_ok(z, zt, 0, 0, spx, mask, bits, gmax, tmax, H, W, flags)) return e;
+    if (!acc || (dz && !grad_out)) return MAS_ERR_NULL;
+    if (N <= 0 || H <= 0 || W <= 0 || S <= 0 || (long long)H * W > 0x7fffffffLL / 2) return MAS_ERR_SHAPE;
+    if (C < 2 || C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
+    if (spx_dtype != MAS_ID_I64 && spx_dtype != MAS_ID_I32 && spx_dtype != MAS_ID_U16) return MAS_ERR_DTYPE;
+    const bool do_ce = flags & MAS_LOSS_CE, only_multi = flags & MAS_LOSS_GROUP_ONLY_MULTI;
+    const int vflags = flags & ~MAS_LOSS_WGROUP;
+    const size_t HW = (size_t)H * W;
+    mas_u64* a64 = reinterpret_cast<mas_u64*>(acc);
+    mas_u64* g64 = reinterpret_cast<mas_u64*>(gmax);
+    for (int pass = 0; pass < (dz ? 2 : 1); ++pass) {
+        float sc3[3] = {0.f, 0.f, 0.f};
+        if (pass == 1) {
+            loss_scales_of(a64, grad_out, nullptr, vflags, sc3);
+            for (size_t i = 0; i < (size_t)N * C * HW; ++i) dz[i] = 0.0f;
+        }
+        const float a_ce = sc3[0] * invT, a_mc = sc3[1] * invT, g6 = sc3[2] * invT;
+        for (int n = 0; n < N; ++n) {
+            for (size_t i = 0; i < HW; ++i) {
+                const size_t g = (size_t)n * HW + i;
+                if (!mask[g]) continue;
+                long long id;
+                if (spx_dtype == MAS_ID_I64) id = static_cast<const long long*>(spx)[g];
+                else if (spx_dtype == MAS_ID_I32) id = static_cast<const int*>(spx)[g];
+                else id = static_cast<const unsigned short*>(spx)[g];
+                if (id < 0 || id >= S) continue;
+                const uint32_t Y = bits[(size_t)n * S + (size_t)id];
+                const int nb = mas_pl_popcount(Y);
+                if (nb == 0) { if (pass == 0) a64[ACC_N_EMPTY] += 1; continue; }
+                float v[MAS_MAX_CLASSES], u[MAS_MAX_CLASSES];
+                for (int c = 0; c < C; ++c) v[c] = z[((size_t)n * C + c) * HW + i];
+                mas_tt_wg_probs(v, C, invT);
+                const bool grp = !only_multi || nb > 1;
+                mas_u64* gm = g64 + ((size_t)n * S + (size_t)id) * C;
+                uint32_t* tm = tmax + ((size_t)n * S + (size_t)id) * C;
+                if (pass == 0) {
+                    if (do_ce) {
+                        const mas_u64 q = mas_fix(mas_pl_loss(v, C, C, Y, MAS_PL_CHOICE), MAS_LOSS_FRAC);
+                        if (nb == 1) { a64[ACC_SUM_CE] += q; a64[ACC_N_CE] += 1; } else { a64[ACC_SUM_MC] += q; a64[ACC_N_MC] += 1; }
+                    }
+                    if (grp) {
+                        for (int c = 0; c < C; ++c) u[c] = zt[((size_t)n * C + c) * HW + i];
+                        mas_tt_wg_probs(u, C, invT);
+                        for (int c = 0; c < C; ++c) {
+                            if ((Y >> c) & 1u) {
+                                const mas_u64 w64 = ((mas_u64)mas_f2u(v[c]) << 32) | (mas_u64)(0xffffffffu - (unsigned)i);
+                                if (w64 > gm[c]) gm[c] = w64;
+                                const uint32_t tb = mas_f2u(u[c]);
+                                if (tb > tm[c]) tm[c] = tb;
+                            }
+                        }
+                    }
+                    continue;
+                }
+                float coef = 0.0f, pos = 0.0f;
+                if (do_ce) {
+                    pos = mas_pl_pos(v, C, C, Y);
+                    coef = ((nb == 1) ? a_ce : a_mc) * (1.0f / (pos + 1e-8f));
+                }
+                unsigned A = 0;
+                float ug = 0.0f;
+                float t[MAS_MAX_CLASSES];
+                for (int c = 0; c < C; ++c) t[c] = 0.0f;
+                if (grp) {
+                    const unsigned key = 0xffffffffu - (unsigned)i;
+                    for (int c = 0; c < C; ++c) {
+                        if ((Y >> c) & 1u) {
+                            const mas_u64 w64 = gm[c];
+                            if ((unsigned)w64 == key && (unsigned)(w64 >> 32) != 0u) {
+                                A |= 1u << c;
+                                t[c] = mas_tt_wg_coef(g6, mas_u2f(tm[c]), v[c]);
+                                ug = ug + t[c] * v[c];
+                            }
+                        }
+                    }
+                }
+                for (int c = 0; c < C; ++c) {
+                    const float p = v[c];
+                    const float yj = ((Y >> c) & 1u) ? 1.0f : 0.0f;
+                    float d = coef * (p * (pos - yj));
+                    if (A) {
+                        if ((A >> c) & 1u) d = d + t[c] * p;
+                        d = d - p * ug;
+                    }
+                    dz[((size_t)n * C + c) * HW + i] = d;
+                }
+            }
+        }
+        if (pass == 0) {
+            for (size_t e = 0; e < (size_t)N * S * C; ++e) {             // k_group_finalize<true>
+                const unsigned pb = (unsigned)(g64[e] >> 32);
+                if (pb) { a64[ACC_SUM_GROUP] += mas_fix(mas_tt_wg_loss(mas_u2f(tmax[e]), mas_u2f(pb)), MAS_LOSS_FRAC); a64[ACC_N_GROUP] += 1; }
+            }
+            if (losses) loss_values_of(a64, vflags, nullptr, losses);
         }
     }
     return 0;

@@ -48,6 +48,23 @@
  *     against float64, the second on such a pixel).
  *
  * h >= 0 up to the rounding of mas_logf near 1 and l >= 0 likewise; both go through mas_fix, which maps negative values to 0.
+ *
+ *   wgroup  (the group / max-pool term with every (superpixel, class) entry weighted by the teacher's confidence;
+ *            trainer/active_joint_multi_predignore_wgroup.py:12-82, WeightedGroupMultiLabelCE.forward)
+ *     This term lives in the group table, not in the fourth slot: it has no temperature of its own, both tables use the group invT.
+ *     p   = the scan's softmax of the student's logits: r = mas_softmax_regs(z, invT) (common.h), p_c = e_c * r            (:27)
+ *     t   = the same arithmetic on the teacher's logits (mas_tt_wg_probs states it for the host)                          (:39)
+ *     P[s,c]  = max over the selected pixels of s of p_c, with its arg-pixel (the packed u64 table `gmax`), c in Y_s       (:56)
+ *     Wt[s,c] = max over the SAME pixels of t_c -- the teacher's own maximum, not its value at the student's arg-pixel     (:69)
+ *               Probabilities are non-negative floats, whose bit patterns order as unsigned integers: the table `tmax` holds
+ *               u32 bits and is combined with an unsigned maximum.  A maximum does not depend on the order, so the bits are defined.
+ *     an entry counts iff the bits of P are non-zero (:64, nonzero of the student's table; Wt may be anything, 0 included)
+ *     l   = w * (-mas_logf(p + eps)), w = Wt[s,c], p = P[s,c]: the logarithm, its negation, then ONE multiplication         (:75)
+ *     the term is sum l / (1 + n) over the counted entries, l through mas_fix (:74-78)
+ *     t_c = -((g * w) / (p_c + eps)) at the arg-pixel of entry (s,c), g = (upstream / (1 + n)) * invT: the product g * w first,
+ *           then the division, then the negation; it enters the pixel's gradient exactly as the unweighted coefficient
+ *           -(g / (p_c + eps)) of the group term does (d_j += [j = c] t_c p_j - p_j sum_c t_c p_c).  The teacher is a constant (:38, :67).
+ *     Consequence: teacher logits equal to the student's give Wt == (gmax >> 32) as bits wherever gmax != 0.
  */
 #ifndef MULACTSEG_TEACHER_TERMS_H
 #define MULACTSEG_TEACHER_TERMS_H
@@ -57,16 +74,22 @@
 #define MAS_TT_NONE 0
 #define MAS_TT_TOP1 1
 #define MAS_TT_ENT 2
+#define MAS_TT_WGROUP 3
 
 #ifndef MAS_LOSS_TOP1     /* (the flag bits of include/mulactseg_hip.h, for a unit that includes this header alone) */
 #define MAS_LOSS_TOP1 128
 #define MAS_LOSS_ENT 256
 #define MAS_LOSS_WITHIN 512
 #endif
+#ifndef MAS_LOSS_WGROUP
+#define MAS_LOSS_WGROUP 1024
+#endif
 
 #define MAS_TT_EPS 1e-8f
 
-MAS_HD int mas_tt_mode(int flags) { return (flags & MAS_LOSS_TOP1) ? MAS_TT_TOP1 : ((flags & MAS_LOSS_ENT) ? MAS_TT_ENT : MAS_TT_NONE); }
+MAS_HD int mas_tt_mode(int flags) {
+    return (flags & MAS_LOSS_TOP1) ? MAS_TT_TOP1 : ((flags & MAS_LOSS_ENT) ? MAS_TT_ENT : ((flags & MAS_LOSS_WGROUP) ? MAS_TT_WGROUP : MAS_TT_NONE));
+}
 
 /* the mask of all C channels */
 MAS_HD uint32_t mas_tt_all(int C) { return C >= 32 ? 0xffffffffu : ((1u << C) - 1u); }
@@ -136,5 +159,26 @@ MAS_HD float mas_tt_ent_u(const float* q, const int CT, const int C, uint32_t M)
 
 /* ent: d_k of class k with restricted probability qk; in_m = bit k of M */
 MAS_HD float mas_tt_ent_grad(float a, float U, float qk, int in_m) { return in_m ? ((a * qk) * (mas_tt_ent_g(qk) - U)) : 0.0f; }
+
+/* wgroup: x[c] = logits on entry, the group probabilities on return -- the operation order of mas_softmax_regs followed by `* rinv`
+ * (the first exponential starts the sum), which the scans run on the student's and on the teacher's row alike */
+MAS_HD void mas_tt_wg_probs(float* x, const int C, float invT) {
+    float m = x[0];
+    for (int c = 1; c < C; ++c) m = (x[c] > m) ? x[c] : m;
+    const float negM = -(m * invT);
+    float sum = 0.0f;
+    for (int c = 0; c < C; ++c) {
+        x[c] = mas_expf_np(mas_fmaf(x[c], invT, negM));
+        sum = (c == 0) ? x[c] : (sum + x[c]);
+    }
+    const float rinv = 1.0f / sum;
+    for (int c = 0; c < C; ++c) x[c] = x[c] * rinv;
+}
+
+/* wgroup: the term of one counted entry (not yet through mas_fix) */
+MAS_HD float mas_tt_wg_loss(float w, float p) { return w * (-mas_logf(p + MAS_TT_EPS)); }
+
+/* wgroup: the backward coefficient t_c of an arg-pixel entry; g = the group scale * invT */
+MAS_HD float mas_tt_wg_coef(float g, float w, float pc) { return -((g * w) / (pc + MAS_TT_EPS)); }
 
 #endif /* MULACTSEG_TEACHER_TERMS_H */

@@ -444,6 +444,80 @@ def teacher_loss_reference(z, zt, spx, mask, bits, invT, invT_x, plbl_th, flags,
 
 
 # ------------------------------------------------------------------------------------------------
+# teacher-weighted group term: a second (superpixel, class) table beside the student's (csrc/teacher_terms.h, wgroup)
+# ------------------------------------------------------------------------------------------------
+LOSS_WGROUP = _lib.LOSS_WGROUP
+
+
+def _wgroup_shapes(z, zt, size, spx, mask, bits, flags, host=False):
+    if not (flags & _lib.LOSS_WGROUP) or not (flags & _lib.LOSS_GROUP):
+        raise ValueError("the wgroup entry points take LOSS_WGROUP together with LOSS_GROUP")
+    if zt is None:
+        raise ValueError("LOSS_WGROUP needs the teacher's logits")
+    return _teacher_shapes(z, zt, size, spx, mask, bits, 0, host=host)
+
+
+def wgroup_loss_fwd(z, zt, size, spx, mask, bits, invT, flags, reduce_acc=None):
+    """Forward scan and weighted finalize of the teacher-weighted group term: ``flags`` hold LOSS_GROUP | LOSS_WGROUP, optionally with
+    LOSS_CE / LOSS_DECOMP / LOSS_GROUP_ONLY_MULTI; ``zt`` = the eval-mode teacher's logits, shaped as ``z``, soft-maxed at the same
+    ``invT``.  ``z`` [N,C,H,W] with ``size`` None, or quarter-resolution [N,C,h,w] upsampled in-kernel to ``size``.  Returns (losses
+    f32[3] = ce, mc, group; acc i64[8]; gmax i64[N,S,C]; tmax int32[N,S,C], the teacher's maxima as probability bits)."""
+    mask, N, C, H, W, S, (h, w) = _wgroup_shapes(z, zt, size, spx, mask, bits, flags)
+    dev = z.device
+    buf = torch.zeros(_lib.ACC_WORDS + N * S * C + (N * S * C + 1) // 2, dtype=torch.int64, device=dev)     # one memset for all three
+    acc, gmax = buf[:_lib.ACC_WORDS], buf[_lib.ACC_WORDS:_lib.ACC_WORDS + N * S * C].view(N, S, C)
+    tmax = buf[_lib.ACC_WORDS + N * S * C:].view(torch.int32)[:N * S * C].view(N, S, C)
+    losses = torch.empty(3, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = _stream(z)
+        _lib.check(lib.mas_wgroup_loss_fwd(z.data_ptr(), zt.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), N, C,
+                                           H, W, S, invT, flags, gmax.data_ptr(), tmax.data_ptr(), acc.data_ptr(),
+                                           None if reduce_acc is not None else losses.data_ptr(), st), "mas_wgroup_loss_fwd")
+        if reduce_acc is not None:
+            reduce_acc(acc)
+            _lib.check(lib.mas_loss_values(acc.data_ptr(), flags & ~_lib.LOSS_WGROUP, losses.data_ptr(), st), "mas_loss_values")
+    return losses, acc, gmax, tmax
+
+
+def wgroup_loss_bwd(z, zt, size, spx, mask, bits, gmax, tmax, acc, grad_out, invT, flags, want_fix=False):
+    """Backward scan of ``wgroup_loss_fwd``: the gradient with respect to ``z`` for upstream gradients ``grad_out`` f32[3]; both
+    tables are read, the teacher is a constant.  At quarter resolution the sums are int64 fixed point (``want_fix`` returns them)."""
+    mask, N, C, H, W, S, (h, w) = _wgroup_shapes(z, zt, size, spx, mask, bits, flags)
+    _need(grad_out, "grad_out", torch.float32)
+    dev = z.device
+    scale = torch.empty(3, dtype=torch.float32, device=dev)
+    fix = None if size is None else torch.zeros(z.shape, dtype=torch.int64, device=dev)
+    dz = torch.empty_like(z)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = _stream(z)
+        _lib.check(lib.mas_loss_scales(acc.data_ptr(), grad_out.data_ptr(), flags & ~_lib.LOSS_WGROUP, scale.data_ptr(), st), "mas_loss_scales")
+        _lib.check(lib.mas_wgroup_loss_bwd(z.data_ptr(), zt.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
+                                           gmax.data_ptr(), tmax.data_ptr(), scale.data_ptr(), N, C, H, W, S, invT, flags, dz.data_ptr(),
+                                           _opt(fix), st), "mas_wgroup_loss_bwd")
+        if fix is not None:
+            _lib.check(lib.mas_fix_to_float(fix.data_ptr(), fix.numel(), _lib.GRAD_FRAC, dz.data_ptr(), st), "mas_fix_to_float")
+    return (dz, fix) if want_fix else dz
+
+
+def wgroup_loss_reference(z, zt, spx, mask, bits, invT, flags, grad_out=None):
+    """Every term of ``wgroup_loss_fwd`` / ``_bwd`` at full resolution on HOST tensors: the library's plain loop through
+    csrc/partial_label.h and csrc/teacher_terms.h (``mas_wgroup_loss_reference``).  Returns (losses f32[3], acc i64[8], gmax i64
+    [N,S,C], tmax int32[N,S,C]) and, with ``grad_out`` f32[3], dz [N,C,H,W] as a fifth value.  Needs no GPU."""
+    mask, N, C, H, W, S, _ = _wgroup_shapes(z, zt, None, spx, mask, bits, flags, host=True)
+    acc = torch.zeros(_lib.ACC_WORDS, dtype=torch.int64)
+    gmax = torch.zeros((N, S, C), dtype=torch.int64)
+    tmax = torch.zeros((N, S, C), dtype=torch.int32)
+    losses = torch.zeros(3, dtype=torch.float32)
+    dz = torch.empty_like(z) if grad_out is not None else None
+    _lib.check(_lib.load().mas_wgroup_loss_reference(z.data_ptr(), zt.data_ptr(), spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
+                                                     N, C, H, W, S, invT, flags, _opt(grad_out), acc.data_ptr(), gmax.data_ptr(),
+                                                     tmax.data_ptr(), losses.data_ptr(), _opt(dz)), "mas_wgroup_loss_reference")
+    return (losses, acc, gmax, tmax) if dz is None else (losses, acc, gmax, tmax, dz)
+
+
+# ------------------------------------------------------------------------------------------------
 # online local-prototype pseudo labels and the cross entropy on them (csrc/online_plbl.hip)
 # ------------------------------------------------------------------------------------------------
 LCE_UNWEIGHTED, LCE_WEIGHTED, LCE_THRESHOLD, LCE_EMPTY_NAN = _lib.LCE_UNWEIGHTED, _lib.LCE_WEIGHTED, _lib.LCE_THRESHOLD, _lib.LCE_EMPTY_NAN

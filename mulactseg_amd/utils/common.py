@@ -101,6 +101,8 @@ def get_parser():
     a('--within_filtering', action='store_true', default=False,
       help="top1plbl: gate on the teacher's top candidate probability divided by its mass on the candidate set")
     a("--entcoeff", type=float, default=1.0, help="multient: weight of the candidate-entropy term")
+    # teacher-weighted group term (active_joint_multi_predignore_wgroup; refused for every other --method)
+    a('--group_only_single', action='store_true', default=False, help="remove only single spx from group multi loss")
     # active learning
     a("--seed", type=int, default=0)
     a("--start_over", action='store_true', default=False)
@@ -263,6 +265,9 @@ SIMW_DEFAULTS = dict(simw_temp=0.1, simw_temp_schedule=False)
 TEACHER_TERM_METHODS = ('active_joint_multi_predignore_top1plbl', 'active_joint_multi_predignore_multient')
 TOP1_DEFAULTS = dict(within_filtering=False)
 ENT_DEFAULTS = dict(entcoeff=1.0)
+# the teacher-weighted group term reads --group_only_single
+WGROUP_METHODS = ('active_joint_multi_predignore_wgroup',)
+WGROUP_DEFAULTS = dict(group_only_single=False)
 
 
 def _refuse_changed(args, defaults, honoured_by):
@@ -305,6 +310,8 @@ def arg_assert(args):
         _refuse_changed(args, TOP1_DEFAULTS, TEACHER_TERM_METHODS[:1])
     if args.method != TEACHER_TERM_METHODS[1]:
         _refuse_changed(args, ENT_DEFAULTS, TEACHER_TERM_METHODS[1:])
+    if args.method not in WGROUP_METHODS:
+        _refuse_changed(args, WGROUP_DEFAULTS, WGROUP_METHODS)
     from ..ops import stage2_threshold_method       # NotImplementedError here; the reference raises it at the first picture
     stage2_threshold_method(getattr(args, 'cosprop_threshold_method', 'median'))            # (trainer/eval_save_cosplbl_prop.py:253)
 

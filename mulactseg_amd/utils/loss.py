@@ -38,6 +38,10 @@ class here                     reference definition
 ``MultiChoiceEnt_``            ``trainer/active_joint_multi_predignore_multient.py:12-70`` (entropy over the candidate set)
 ``FusedTeacherTermLoss``       (new) merged-positive CE, group term and one of the two above from ONE scan pair
                                (``csrc/teacher_terms.h``) -- what the ``top1plbl`` / ``multient`` trainers use
+``WeightedGroupMultiLabelCE``  ``trainer/active_joint_multi_predignore_wgroup.py:12-82`` (group term weighted by the teacher's
+                               per-(superpixel, class) maximum; ``forward(inputs, plbl_preds, targets, superpixels, spmasks)``)
+``FusedWGroupLoss``            (new) merged-positive CE and the weighted group term from ONE scan pair -- what the ``wgroup``
+                               trainer uses
 =============================  =================================================================
 
 Inputs must be ROCm tensors; there is no CPU path (``_lib.MulActSegHipError`` otherwise).
@@ -642,6 +646,97 @@ class FusedTeacherTermLoss(nn.Module):
     def forward(self, inputs, plbl_inputs, targets, superpixels, spmasks):
         """``plbl_inputs``: the teacher's logits (``None`` for ``term='ent'``)."""
         return self._run(inputs, plbl_inputs, None, targets, superpixels, spmasks)
+
+    def forward_lowres(self, zq, zq_teacher, size, targets, superpixels, spmasks):
+        return self._run(zq, zq_teacher, size, targets, superpixels, spmasks)
+
+
+class _WGroupLossFn(torch.autograd.Function):
+    """(ce, mc, group) = f(z) with the group term weighted by the teacher's table (``csrc/teacher_terms.h``, wgroup): one forward scan
+    with the weighted finalize and one backward scan.  ``zt`` is a constant; ``size`` None: full-resolution tensors, else
+    quarter-resolution ones upsampled inside the scans.  No host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, z, zt, size, targets, superpixels, spmasks, invT, flags, sync):
+        z, spx, msk = z.contiguous(), superpixels.contiguous(), spmasks.contiguous()
+        zt = zt.detach().contiguous()
+        bits = ops.target_bits(targets)
+        losses, acc, gmax, tmax = ops.wgroup_loss_fwd(z, zt, size, spx, msk, bits, invT, flags, reduce_acc=_all_reduce_sum if sync else None)
+        ctx.save_for_backward(z, zt, spx, msk, bits, acc, gmax, tmax)
+        ctx.consts = (size, invT, flags)
+        ctx.mark_non_differentiable(acc)
+        return losses[0], losses[1], losses[2], acc
+
+    @staticmethod
+    def backward(ctx, g_ce, g_mc, g_group, _g_acc):
+        z, zt, spx, msk, bits, acc, gmax, tmax = ctx.saved_tensors
+        size, invT, flags = ctx.consts
+        grad_out = torch.stack([g_ce, g_mc, g_group]).to(torch.float32).contiguous()
+        return (ops.wgroup_loss_bwd(z, zt, size, spx, msk, bits, gmax, tmax, acc, grad_out, invT, flags),) + (None,) * 8
+
+
+def _wgroup_run(z, zt, size, targets, superpixels, spmasks, temp, flags, sync):
+    if zt is None:
+        raise ValueError("the weighted group term needs the teacher's logits")
+    if targets.dtype != torch.uint8:
+        targets = targets.to(torch.uint8)
+    size = None if size is None else (int(size[0]), int(size[1]))
+    return _WGroupLossFn.apply(z, zt, size, targets.contiguous(), superpixels, spmasks, ops.inv_temperature(temp), flags, sync)
+
+
+class WeightedGroupMultiLabelCE(GroupMultiLabelCE_):
+    """The group / MIL loss with every (superpixel, class) term weighted by the TEACHER's maximum probability of that class over the
+    selected pixels of that superpixel (``plbl_preds``, an eval-mode forward of the same weights at the same temperature, a constant
+    of the gradient): ``sum_{(s,c): P > 0} Wt[s,c] * -log(P[s,c] + eps) / (1 + n)`` -- reference
+    ``trainer/active_joint_multi_predignore_wgroup.py:12-82``.  ``args.group_only_single``: only superpixels with more than one
+    target bit (``args=None``: False).  All target columns are used."""
+
+    def __init__(self, args, num_class, num_superpixel, temperature=1.0, reduction='mean'):
+        super().__init__(args, num_class, num_superpixel, temperature, reduction)
+        self.ignore_only_single = bool(getattr(args, 'group_only_single', False))
+        self.sync_normalisers = True
+
+    def _f(self):
+        return _lib.LOSS_GROUP | _lib.LOSS_WGROUP | (_lib.LOSS_GROUP_ONLY_MULTI if self.ignore_only_single else 0)
+
+    def _run(self, z, zt, size, targets, superpixels, spmasks):
+        if targets.shape[1] != self.num_superpixel:
+            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        _, _, group, self.last_acc = _wgroup_run(z, zt, size, targets, superpixels, spmasks, self.temp, self._f(), self.sync_normalisers)
+        return group
+
+    def forward(self, inputs, plbl_preds, targets, superpixels, spmasks):
+        return self._run(inputs, plbl_preds, None, targets, superpixels, spmasks)
+
+    def forward_lowres(self, zq, zq_teacher, size, targets, superpixels, spmasks):
+        """``zq`` / ``zq_teacher`` [N,C,h,w]: the training-mode and the eval-mode quarter-resolution logits, both interpolated in
+        registers with the same taps -- no ``[N,C,H,W]`` tensor of either exists."""
+        return self._run(zq, zq_teacher, size, targets, superpixels, spmasks)
+
+
+class FusedWGroupLoss(nn.Module):
+    """(pos, group) of the ``wgroup`` trainer from ONE forward scan and ONE backward scan: the merged-positive CE (``MultiChoiceCE_``)
+    and ``WeightedGroupMultiLabelCE`` at their shared temperature -- each value equal, bit for bit, to the stand-alone module's.
+    Shaped like ``FusedTeacherTermLoss``."""
+
+    def __init__(self, num_superpixel, group_temperature=1.0, multi_temperature=1.0, group_only_single=False, sync_normalisers=True):
+        super().__init__()
+        if group_temperature != multi_temperature:
+            raise ValueError("the fused scan shares one softmax: group_ce_temp must equal multi_ce_temp "
+                             "(both 0.1 in the reference scripts)")
+        self.num_superpixel = num_superpixel
+        self.temp = multi_temperature
+        self.sync_normalisers = sync_normalisers
+        self.flags = _lib.LOSS_CE | _lib.LOSS_GROUP | _lib.LOSS_WGROUP | (_lib.LOSS_GROUP_ONLY_MULTI if group_only_single else 0)
+
+    def _run(self, z, zt, size, targets, superpixels, spmasks):
+        if targets.shape[1] != self.num_superpixel:
+            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        pos, _, group, self.last_acc = _wgroup_run(z, zt, size, targets, superpixels, spmasks, self.temp, self.flags, self.sync_normalisers)
+        return pos, group
+
+    def forward(self, inputs, plbl_preds, targets, superpixels, spmasks):
+        return self._run(inputs, plbl_preds, None, targets, superpixels, spmasks)
 
     def forward_lowres(self, zq, zq_teacher, size, targets, superpixels, spmasks):
         return self._run(zq, zq_teacher, size, targets, superpixels, spmasks)
