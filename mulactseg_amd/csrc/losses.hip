@@ -6,8 +6,8 @@
 //                        per-(superpixel, class) max with arg-pixel through a per-workgroup LDS table
 //                        of packed (prob bits << 32 | ~pixel) words combined with 64-bit atomic max.
 //   k_group_finalize     -log(max + eps) over the (superpixel, class) table.
-//   k_loss_values        fixed-point sums -> the reference's mean-normalised f32 losses.
-//   k_loss_scales        upstream gradients / (1 + n) -> per-loss scale factors (no host sync).
+//   k_loss_values_weighted   fixed-point sums -> the reference's mean-normalised f32 losses (with weights: and their weighted sum).
+//   k_loss_scales_weighted   upstream gradients / (1 + n) -> per-loss scale factors (no host sync).
 //   k_partial_loss_bwd   one pass writing dz[N,C,H,W] completely (zeros off-mask), softmax recomputed,
 //                        group-loss gradient gathered from the arg-pixel table (no atomics).
 //   PLX instantiations of both scans: the multi-hot pixel term is the risk-consistent (MAS_LOSS_RC) or the top-1 candidate
@@ -473,11 +473,7 @@ __host__ __device__ __forceinline__ void loss_values_of(const mas_u64* acc, int 
     if (w) out[3] = (w[0] * ce + w[1] * mc) + w[2] * gr;
 }
 
-__global__ void k_loss_values(const mas_u64* __restrict__ acc, int flags, float* __restrict__ out) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    loss_values_of(acc, flags, nullptr, out);
-}
-
+// (w == NULL: the three losses alone)
 __global__ void k_loss_values_weighted(const mas_u64* __restrict__ acc, int flags, const float* __restrict__ w, float* __restrict__ out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     loss_values_of(acc, flags, w, out);
@@ -504,16 +500,11 @@ __host__ __device__ __forceinline__ void loss_scales_of(const mas_u64* acc, cons
     scale[2] = g2 / (float)(acc[ACC_N_GROUP] + 1);
 }
 
+// (w == NULL: `grad_total` holds the three upstream gradients)
 __global__ void k_loss_scales_weighted(const mas_u64* __restrict__ acc, const float* __restrict__ grad_total, const float* __restrict__ w,
                                        int flags, float* __restrict__ scale) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     loss_scales_of(acc, grad_total, w, flags, scale);
-}
-
-__global__ void k_loss_scales(const mas_u64* __restrict__ acc, const float* __restrict__ grad_out, int flags,
-                              float* __restrict__ scale) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    loss_scales_of(acc, grad_out, nullptr, flags, scale);
 }
 
 // LOWRES: `dz` is the caller-zeroed int64 fixed-point accumulator dzq_fix [N,C,h,w] (MAS_GRAD_FRAC fractional bits): every
@@ -698,16 +689,35 @@ inline size_t fwd_smem_bytes(int C, int tt = MAS_TT_NONE) {
            sizeof(unsigned short) * kTilePx + (tt == MAS_TT_WGROUP ? sizeof(unsigned) * kSlots * (size_t)C : 0);
 }
 
+// which entry points a call came through: it decides the flag rule (the *_flags_ok predicates below)
+enum LossFamily {
+    FAMILY_PLAIN,               // mas_partial_loss_*: `acc` has 8 words, `te` is unused
+    FAMILY_TEACHER,             // mas_teacher_loss_*: `acc` has 16 words, `te` holds the fourth slot's inputs, `scale` four factors
+    FAMILY_WGROUP               // mas_wgroup_loss_*: `acc` has 8 words, `te.zt` and `te.tmax` are filled in
+};
+
 struct LossArgs {
+    LossFamily family;
     const float* z; const void* spx; const unsigned char* mask; const unsigned* bits;
     int N, C, H, W, S; float invT; int flags;
+    int h, w;                   // > 0: `z` is the quarter-resolution tensor [N,C,h,w] (LOWRES kernels)
     mas_u64* gmax; mas_u64* acc; const float* scale; float* dz;
-    int h = 0, w = 0;           // > 0: `z` is the quarter-resolution tensor [N,C,h,w] (LOWRES kernels)
     const float* grad = nullptr; const float* gw = nullptr;     // backward with scale == NULL: upstream gradient(s) and optional weights
-    TeacherIn te = {nullptr, 0.f, 0.f, 0, nullptr};             // MAS_LOSS_TOP1 / MAS_LOSS_ENT (`scale` then holds four factors), MAS_LOSS_WGROUP
-    bool teacher = false;       // set by the mas_teacher_loss_* entry points: `acc` has 16 words and `te` is filled in
-    bool wgroup = false;        // set by the mas_wgroup_loss_* entry points: `te.zt` and `te.tmax` are filled in, `acc` has 8 words
+    TeacherIn te = {nullptr, 0.f, 0.f, 0, nullptr};
 };
+
+// The one place a scan's arguments are put together: the head every entry point shares, the quarter-resolution extents (h <= 0: full
+// resolution), then what the direction reads and writes -- forward: the table and the accumulators; backward: the table, the scale
+// factors (NULL in the fused backward, which passes `acc` and fills in grad / gw), dz, and the fixed-point sums that take dz's place
+// at quarter resolution.  The tables and sums are the caller's uint64_t / int64_t; the kernels' own types have the same layout.
+inline LossArgs loss_args(LossFamily family, const float* z, int h, int w, const void* spx, const uint8_t* mask, const uint32_t* bits, int N,
+                          int C, int H, int W, int S, float invT, int flags, const void* gmax, const void* acc,
+                          const float* scale = nullptr, float* dz = nullptr, int64_t* dzq_fix = nullptr) {
+    const bool low = h > 0;
+    return LossArgs{family, z, spx, mask, bits, N, C, H, W, S, invT, flags, low ? h : 0, low ? w : 0,
+                    const_cast<mas_u64*>(static_cast<const mas_u64*>(gmax)), const_cast<mas_u64*>(static_cast<const mas_u64*>(acc)), scale,
+                    low ? reinterpret_cast<float*>(dzq_fix) : dz};
+}
 
 template <int CT, bool EXACT, typename IdT, bool PLX, int TT = MAS_TT_NONE>
 int launch_loss(const LossArgs& a, bool backward, hipStream_t st) {
@@ -785,16 +795,51 @@ inline bool wgroup_flags_ok(int flags) {
     return !(flags & ~(MAS_LOSS_CE | MAS_LOSS_DECOMP | MAS_LOSS_GROUP | MAS_LOSS_GROUP_ONLY_MULTI | MAS_LOSS_WGROUP));
 }
 
+inline bool family_flags_ok(LossFamily family, int flags) {
+    return family == FAMILY_WGROUP ? wgroup_flags_ok(flags) : (family == FAMILY_TEACHER ? teacher_flags_ok(flags) : loss_flags_ok(flags));
+}
+
+// the extents and the class count of a scan; `plane_limit`: with the scans' bound on H * W.  (The fused entry points ask without it
+// before their first launch; dispatch_loss then asks with it.)
+inline int loss_dims_status(int N, int C, int H, int W, int S, bool plane_limit) {
+    if (N <= 0 || H <= 0 || W <= 0 || S <= 0 || (plane_limit && (long long)H * W > 0x7fffffffLL / 2)) return MAS_ERR_SHAPE;
+    if (C < 2 || C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
+    return 0;
+}
+
 int dispatch_loss(const LossArgs& a, int spx_dtype, bool backward, hipStream_t st) {
-    if (!(a.wgroup ? wgroup_flags_ok(a.flags) : (a.teacher ? teacher_flags_ok(a.flags) : loss_flags_ok(a.flags)))) return MAS_ERR_RANGE;
-    if (a.N <= 0 || a.H <= 0 || a.W <= 0 || a.S <= 0 || (long long)a.H * a.W > 0x7fffffffLL / 2) return MAS_ERR_SHAPE;
-    if (a.C < 2 || a.C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
-    switch (a.C) {
+    if (!family_flags_ok(a.family, a.flags)) return MAS_ERR_RANGE;
+    if (int e = loss_dims_status(a.N, a.C, a.H, a.W, a.S, true)) return e;
+    switch (a.C) {              // (an unknown spx_dtype is MAS_ERR_DTYPE from dispatch_loss_ids, for every entry point)
         case 19: return dispatch_loss_ids<19, true>(a, spx_dtype, backward, st);
         case 20: return dispatch_loss_ids<20, true>(a, spx_dtype, backward, st);
         case 21: return dispatch_loss_ids<21, true>(a, spx_dtype, backward, st);
         default: return dispatch_loss_ids<MAS_MAX_CLASSES, false>(a, spx_dtype, backward, st);
     }
+}
+
+// k_group_finalize behind a scan, in few workgroups: every one of them ends in atomics on the same accumulator words -- with 640 of
+// them those serialised at the L2 for 40 us, measured; 64 x 256 threads x 10 entries each is 4 us.  So 8 x 256 entries per workgroup,
+// 64 workgroups at the most.  (mas_group_finalize, the entry point of its own, has its own grid.)
+template <bool WG>
+int launch_group_finalize(const mas_u64* gmax, const unsigned* tmax, long long n_entries, mas_u64* acc, int flags, const float* w, float* values,
+                          hipStream_t st) {
+    long long nblk = (n_entries + 8 * kThreads - 1) / (8 * kThreads);
+    if (nblk > 64) nblk = 64;
+    hipLaunchKernelGGL(k_group_finalize<WG>, dim3((unsigned)nblk), dim3(kThreads), 0, st, gmax, tmax, n_entries, acc, flags, w, values);
+    return mas_launch_status();
+}
+
+// w == NULL: losses [3]; else losses [4] with the weighted objective
+int launch_loss_values(const mas_u64* acc, int flags, const float* w, float* losses, hipStream_t st) {
+    hipLaunchKernelGGL(k_loss_values_weighted, dim3(1), dim3(64), 0, st, acc, flags, w, losses);
+    return mas_launch_status();
+}
+
+// w == NULL: grad [3], the upstream gradient of every loss; else grad [1], the upstream gradient of the weighted objective
+int launch_loss_scales(const mas_u64* acc, const float* grad, const float* w, int flags, float* scale, hipStream_t st) {
+    hipLaunchKernelGGL(k_loss_scales_weighted, dim3(1), dim3(64), 0, st, acc, grad, w, flags, scale);
+    return mas_launch_status();
 }
 
 }  // namespace
@@ -815,9 +860,8 @@ extern "C" int mas_partial_loss_fwd(const float* z, const void* spx, int spx_dty
                                     void* stream) {
     if (!z || !spx || !mask || !bits || !acc) return MAS_ERR_NULL;
     if ((flags & MAS_LOSS_GROUP) && !gmax) return MAS_ERR_NULL;
-    LossArgs a{z, spx, mask, bits, N, C, H, W, S, invT, flags, reinterpret_cast<mas_u64*>(gmax),
-               reinterpret_cast<mas_u64*>(acc), nullptr, nullptr};
-    return dispatch_loss(a, spx_dtype, false, static_cast<hipStream_t>(stream));
+    return dispatch_loss(loss_args(FAMILY_PLAIN, z, 0, 0, spx, mask, bits, N, C, H, W, S, invT, flags, gmax, acc), spx_dtype, false,
+                         static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mas_group_finalize(const uint64_t* gmax, int64_t n_entries, uint64_t* acc, void* stream) {
@@ -833,31 +877,23 @@ extern "C" int mas_group_finalize(const uint64_t* gmax, int64_t n_entries, uint6
 
 extern "C" int mas_loss_values(const uint64_t* acc, int flags, float* losses, void* stream) {
     if (!acc || !losses) return MAS_ERR_NULL;
-    hipLaunchKernelGGL(k_loss_values, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const mas_u64*>(acc), flags, losses);
-    return mas_launch_status();
+    return launch_loss_values(reinterpret_cast<const mas_u64*>(acc), flags, nullptr, losses, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mas_loss_values_weighted(const uint64_t* acc, int flags, const float* weights, float* losses4, void* stream) {
     if (!acc || !weights || !losses4) return MAS_ERR_NULL;
-    hipLaunchKernelGGL(k_loss_values_weighted, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), reinterpret_cast<const mas_u64*>(acc),
-                       flags, weights, losses4);
-    return mas_launch_status();
+    return launch_loss_values(reinterpret_cast<const mas_u64*>(acc), flags, weights, losses4, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mas_loss_scales_weighted(const uint64_t* acc, const float* grad_total, const float* weights, int flags, float* scale,
                                         void* stream) {
     if (!acc || !grad_total || !weights || !scale) return MAS_ERR_NULL;
-    hipLaunchKernelGGL(k_loss_scales_weighted, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), reinterpret_cast<const mas_u64*>(acc),
-                       grad_total, weights, flags, scale);
-    return mas_launch_status();
+    return launch_loss_scales(reinterpret_cast<const mas_u64*>(acc), grad_total, weights, flags, scale, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mas_loss_scales(const uint64_t* acc, const float* grad_out, int flags, float* scale, void* stream) {
     if (!acc || !grad_out || !scale) return MAS_ERR_NULL;
-    hipLaunchKernelGGL(k_loss_scales, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream),
-                       reinterpret_cast<const mas_u64*>(acc), grad_out, flags, scale);
-    return mas_launch_status();
+    return launch_loss_scales(reinterpret_cast<const mas_u64*>(acc), grad_out, nullptr, flags, scale, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mas_partial_loss_bwd(const float* z, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits,
@@ -865,9 +901,8 @@ extern "C" int mas_partial_loss_bwd(const float* z, const void* spx, int spx_dty
                                     int flags, float* dz, void* stream) {
     if (!z || !spx || !mask || !bits || !scale || !dz) return MAS_ERR_NULL;
     if ((flags & MAS_LOSS_GROUP) && !gmax) return MAS_ERR_NULL;
-    LossArgs a{z, spx, mask, bits, N, C, H, W, S, invT, flags,
-               const_cast<mas_u64*>(reinterpret_cast<const mas_u64*>(gmax)), nullptr, scale, dz};
-    return dispatch_loss(a, spx_dtype, true, static_cast<hipStream_t>(stream));
+    return dispatch_loss(loss_args(FAMILY_PLAIN, z, 0, 0, spx, mask, bits, N, C, H, W, S, invT, flags, gmax, nullptr, scale, dz), spx_dtype,
+                         true, static_cast<hipStream_t>(stream));
 }
 
 // ---- quarter-resolution forms: the x4 bilinear upsampling of the logits (models/segmentation/utils.py:25) is evaluated per
@@ -878,9 +913,8 @@ extern "C" int mas_partial_loss_fwd_lowres(const float* zq, int h, int w, const 
     if (!zq || !spx || !mask || !bits || !acc) return MAS_ERR_NULL;
     if ((flags & MAS_LOSS_GROUP) && !gmax) return MAS_ERR_NULL;
     if (h <= 0 || w <= 0 || h > H || w > W) return MAS_ERR_SHAPE;
-    LossArgs a{zq, spx, mask, bits, N, C, H, W, S, invT, flags, reinterpret_cast<mas_u64*>(gmax),
-               reinterpret_cast<mas_u64*>(acc), nullptr, nullptr, h, w};
-    return dispatch_loss(a, spx_dtype, false, static_cast<hipStream_t>(stream));
+    return dispatch_loss(loss_args(FAMILY_PLAIN, zq, h, w, spx, mask, bits, N, C, H, W, S, invT, flags, gmax, acc), spx_dtype, false,
+                         static_cast<hipStream_t>(stream));
 }
 
 extern "C" int mas_partial_loss_bwd_lowres(const float* zq, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask,
@@ -889,9 +923,8 @@ extern "C" int mas_partial_loss_bwd_lowres(const float* zq, int h, int w, const 
     if (!zq || !spx || !mask || !bits || !scale || !dzq_fix) return MAS_ERR_NULL;
     if ((flags & MAS_LOSS_GROUP) && !gmax) return MAS_ERR_NULL;
     if (h <= 0 || w <= 0 || h > H || w > W) return MAS_ERR_SHAPE;
-    LossArgs a{zq, spx, mask, bits, N, C, H, W, S, invT, flags, const_cast<mas_u64*>(reinterpret_cast<const mas_u64*>(gmax)), nullptr,
-               scale, reinterpret_cast<float*>(dzq_fix), h, w};
-    return dispatch_loss(a, spx_dtype, true, static_cast<hipStream_t>(stream));
+    return dispatch_loss(loss_args(FAMILY_PLAIN, zq, h, w, spx, mask, bits, N, C, H, W, S, invT, flags, gmax, nullptr, scale, nullptr, dzq_fix),
+                         spx_dtype, true, static_cast<hipStream_t>(stream));
 }
 
 namespace {
@@ -942,8 +975,7 @@ extern "C" int mas_partial_loss_fwd_fused(const float* z, int h, int w, const vo
                                           float* losses, void* stream) {
     if (!z || !spx || !mask || !work || (!targets && !bits)) return MAS_ERR_NULL;
     if (!loss_flags_ok(flags)) return MAS_ERR_RANGE;
-    if (N <= 0 || S <= 0 || H <= 0 || W <= 0) return MAS_ERR_SHAPE;
-    if (C < 2 || C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
+    if (int e = loss_dims_status(N, C, H, W, S, false)) return e;
     if ((h > 0) != (w > 0) || h > H || w > W) return MAS_ERR_SHAPE;
     if (targets && (cols_stored <= 0 || cols_used < 1 || cols_used > cols_stored || cols_used > MAS_MAX_CLASSES)) return MAS_ERR_CLASSES;
     const WorkLayout L = work_layout(N, S, C, flags);
@@ -959,20 +991,10 @@ extern "C" int mas_partial_loss_fwd_fused(const float* z, int h, int w, const vo
     hipLaunchKernelGGL(k_loss_prep, dim3((unsigned)((n_prep + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, acc, n_zero, targets, n_rows,
                        cols_stored, cols_used, wbits);
     if (int e = mas_launch_status()) return e;
-    LossArgs a{z, spx, mask, targets ? wbits : bits, N, C, H, W, S, invT, flags, gmax, acc, nullptr, nullptr, h > 0 ? h : 0, h > 0 ? w : 0};
+    const LossArgs a = loss_args(FAMILY_PLAIN, z, h, w, spx, mask, targets ? wbits : bits, N, C, H, W, S, invT, flags, gmax, acc);
     if (int e = dispatch_loss(a, spx_dtype, false, st)) return e;
-    if (gmax) {
-        const long long n_entries = (long long)N * S * C;
-        // (few workgroups: every one of them ends in atomics on the same accumulator words -- with 640 of them those serialised at the
-        //  L2 for 40 us, measured; 64 x 256 threads x 10 entries each is 4 us)
-        long long nblk = (n_entries + 8 * kThreads - 1) / (8 * kThreads);
-        if (nblk > 64) nblk = 64;
-        hipLaunchKernelGGL(k_group_finalize<false>, dim3((unsigned)nblk), dim3(kThreads), 0, st, gmax, static_cast<const unsigned*>(nullptr),
-                           n_entries, acc, flags, weights, losses);
-    } else if (losses) {
-        if (weights) hipLaunchKernelGGL(k_loss_values_weighted, dim3(1), dim3(64), 0, st, acc, flags, weights, losses);
-        else hipLaunchKernelGGL(k_loss_values, dim3(1), dim3(64), 0, st, acc, flags, losses);
-    }
+    if (gmax) return launch_group_finalize<false>(gmax, nullptr, (long long)N * S * C, acc, flags, weights, losses, st);
+    if (losses) return launch_loss_values(acc, flags, weights, losses, st);
     return mas_launch_status();
 }
 
@@ -981,24 +1003,23 @@ extern "C" int mas_partial_loss_bwd_fused(const float* z, int h, int w, const vo
                                           float invT, int flags, float* dz, int64_t* dzq_fix, void* stream) {
     if (!z || !spx || !mask || !work || !grad || !dz) return MAS_ERR_NULL;
     if (!loss_flags_ok(flags)) return MAS_ERR_RANGE;
-    if (N <= 0 || S <= 0 || H <= 0 || W <= 0) return MAS_ERR_SHAPE;
-    if (C < 2 || C > MAS_MAX_CLASSES) return MAS_ERR_CLASSES;
+    if (int e = loss_dims_status(N, C, H, W, S, false)) return e;
     const bool low = h > 0;
     if ((h > 0) != (w > 0) || h > H || w > W) return MAS_ERR_SHAPE;
     if (low && !dzq_fix) return MAS_ERR_NULL;
     const WorkLayout L = work_layout(N, S, C, flags);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const unsigned char* wb = static_cast<const unsigned char*>(work);
-    mas_u64* acc = const_cast<mas_u64*>(reinterpret_cast<const mas_u64*>(wb));
-    mas_u64* gmax = (flags & MAS_LOSS_GROUP) ? const_cast<mas_u64*>(reinterpret_cast<const mas_u64*>(wb + L.gmax_off)) : nullptr;
+    const void* gmax = (flags & MAS_LOSS_GROUP) ? wb + L.gmax_off : nullptr;
     const unsigned* wbits = bits ? bits : reinterpret_cast<const unsigned*>(wb + L.bits_off);
     const size_t nq = low ? (size_t)N * C * h * w : 0;
     if (low) {
         const hipError_t e = hipMemsetAsync(dzq_fix, 0, nq * sizeof(int64_t), st);
         if (e != hipSuccess) return (int)e;
     }
-    LossArgs a{z, spx, mask, wbits, N, C, H, W, S, invT, flags, gmax, acc, nullptr, low ? reinterpret_cast<float*>(dzq_fix) : dz,
-               low ? h : 0, low ? w : 0, grad, weights};
+    LossArgs a = loss_args(FAMILY_PLAIN, z, h, w, spx, mask, wbits, N, C, H, W, S, invT, flags, gmax, work, nullptr, dz, dzq_fix);
+    a.grad = grad;              // (no scale factors: the scan forms them from the accumulators, the upstream gradient(s) and the weights)
+    a.gw = weights;
     if (int e = dispatch_loss(a, spx_dtype, true, st)) return e;
     if (low) {
         hipLaunchKernelGGL(k_fix_to_float, dim3((unsigned)((nq + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
@@ -1090,10 +1111,8 @@ extern "C" int mas_teacher_loss_fwd(const float* z, const float* zt, int h, int 
                                     uint64_t* gmax, uint64_t* acc, void* stream) {
     if (int e = teacher_args_ok(z, zt, h, w, spx, mask, bits, H, W, invT_x, flags)) return e;
     if (!acc || ((flags & MAS_LOSS_GROUP) && !gmax)) return MAS_ERR_NULL;
-    LossArgs a{z, spx, mask, bits, N, C, H, W, S, invT, flags, reinterpret_cast<mas_u64*>(gmax), reinterpret_cast<mas_u64*>(acc), nullptr,
-               nullptr, h > 0 ? h : 0, h > 0 ? w : 0};
+    LossArgs a = loss_args(FAMILY_TEACHER, z, h, w, spx, mask, bits, N, C, H, W, S, invT, flags, gmax, acc);
     a.te = TeacherIn{zt, invT_x, plbl_th, (flags & MAS_LOSS_WITHIN) ? 1 : 0};
-    a.teacher = true;
     return dispatch_loss(a, spx_dtype, false, static_cast<hipStream_t>(stream));
 }
 
@@ -1102,10 +1121,8 @@ extern "C" int mas_teacher_loss_bwd(const float* z, const float* zt, int h, int 
                                     float invT, float invT_x, float plbl_th, int flags, float* dz, int64_t* dzq_fix, void* stream) {
     if (int e = teacher_args_ok(z, zt, h, w, spx, mask, bits, H, W, invT_x, flags)) return e;
     if (!scale || (h > 0 ? !dzq_fix : !dz) || ((flags & MAS_LOSS_GROUP) && !gmax)) return MAS_ERR_NULL;
-    LossArgs a{z, spx, mask, bits, N, C, H, W, S, invT, flags, const_cast<mas_u64*>(reinterpret_cast<const mas_u64*>(gmax)), nullptr, scale,
-               h > 0 ? reinterpret_cast<float*>(dzq_fix) : dz, h > 0 ? h : 0, h > 0 ? w : 0};
+    LossArgs a = loss_args(FAMILY_TEACHER, z, h, w, spx, mask, bits, N, C, H, W, S, invT, flags, gmax, nullptr, scale, dz, dzq_fix);
     a.te = TeacherIn{zt, invT_x, plbl_th, (flags & MAS_LOSS_WITHIN) ? 1 : 0};
-    a.teacher = true;
     return dispatch_loss(a, spx_dtype, true, static_cast<hipStream_t>(stream));
 }
 
@@ -1308,18 +1325,10 @@ extern "C" int mas_wgroup_loss_fwd(const float* z, const float* zt, int h, int w
     if (int e = wgroup_args_ok(z, zt, h, w, spx, mask, bits, gmax, tmax, H, W, flags)) return e;
     if (!acc) return MAS_ERR_NULL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    LossArgs a{z, spx, mask, bits, N, C, H, W, S, invT, flags, reinterpret_cast<mas_u64*>(gmax), reinterpret_cast<mas_u64*>(acc), nullptr,
-               nullptr, h > 0 ? h : 0, h > 0 ? w : 0};
+    LossArgs a = loss_args(FAMILY_WGROUP, z, h, w, spx, mask, bits, N, C, H, W, S, invT, flags, gmax, acc);
     a.te = TeacherIn{zt, invT, 0.f, 0, tmax};
-    a.wgroup = true;
     if (int e = dispatch_loss(a, spx_dtype, false, st)) return e;
-    const long long n_entries = (long long)N * S * C;
-    long long nblk = (n_entries + 8 * kThreads - 1) / (8 * kThreads);       // (few workgroups: see mas_partial_loss_fwd_fused)
-    if (nblk > 64) nblk = 64;
-    hipLaunchKernelGGL(k_group_finalize<true>, dim3((unsigned)nblk), dim3(kThreads), 0, st, reinterpret_cast<const mas_u64*>(gmax),
-                       static_cast<const unsigned*>(tmax), n_entries, reinterpret_cast<mas_u64*>(acc), flags & ~MAS_LOSS_WGROUP,
-                       static_cast<const float*>(nullptr), losses);
-    return mas_launch_status();
+    return launch_group_finalize<true>(a.gmax, tmax, (long long)N * S * C, a.acc, flags & ~MAS_LOSS_WGROUP, nullptr, losses, st);
 }
 
 extern "C" int mas_wgroup_loss_bwd(const float* z, const float* zt, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask,
@@ -1327,10 +1336,8 @@ extern "C" int mas_wgroup_loss_bwd(const float* z, const float* zt, int h, int w
                                    int W, int S, float invT, int flags, float* dz, int64_t* dzq_fix, void* stream) {
     if (int e = wgroup_args_ok(z, zt, h, w, spx, mask, bits, gmax, tmax, H, W, flags)) return e;
     if (!scale || (h > 0 ? !dzq_fix : !dz)) return MAS_ERR_NULL;
-    LossArgs a{z, spx, mask, bits, N, C, H, W, S, invT, flags, const_cast<mas_u64*>(reinterpret_cast<const mas_u64*>(gmax)), nullptr, scale,
-               h > 0 ? reinterpret_cast<float*>(dzq_fix) : dz, h > 0 ? h : 0, h > 0 ? w : 0};
+    LossArgs a = loss_args(FAMILY_WGROUP, z, h, w, spx, mask, bits, N, C, H, W, S, invT, flags, gmax, nullptr, scale, dz, dzq_fix);
     a.te = TeacherIn{zt, invT, 0.f, 0, const_cast<unsigned*>(static_cast<const unsigned*>(tmax))};
-    a.wgroup = true;
     return dispatch_loss(a, spx_dtype, true, static_cast<hipStream_t>(stream));
 }
 

@@ -137,78 +137,117 @@ def _mask_u8(mask):
     return _need(mask, "spmasks", torch.uint8)
 
 
-def _partial_loss_fwd(z, size, spx, mask, bits, invT, flags, reduce_acc, weights):
-    """The step-by-step forward on ``z`` [N,C,H,W] (``size`` None) or on the bilinear upsampling of ``z`` [N,C,h,w] to ``size`` =
-    (H, W), which is never materialised: scan, group finalize, ``reduce_acc``, loss values."""
-    _need(z, "inputs", torch.float32)
-    _need(spx, "superpixels")
-    mask = _mask_u8(mask)
-    _need(bits, "bits", torch.int32)
+def _loss_shapes(z, zt, size, spx, mask, bits, grad_out=None, host=False, bits_dtype=torch.int32):
+    """The tensor / shape check of every loss family and of the host references: ``z`` [N,C,H,W] (``size`` None) or [N,C,h,w] to be
+    upsampled to ``size`` = (H, W); ``zt`` (optional) the teacher's logits, shaped as ``z``; ``bits`` int32 [N,S] (the fused forward alone asks for
+    ``bits_dtype`` u8: the target rows [N,S,cols] it forms them from); ``grad_out`` (optional) the backward's upstream gradients.  Returns (mask
+    as u8, N, C, H, W, S, (h, w)) with (h, w) = (0, 0) at full resolution, as the entry points that take both resolutions want it."""
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    for t, name, dt in ((z, "inputs", torch.float32), (zt, "plbl_inputs", torch.float32), (spx, "superpixels", None),
+                        (mask, "spmasks", torch.uint8), (bits, "bits", bits_dtype),
+                        (grad_out, "grad_out", torch.float32)):
+        if t is None:
+            continue
+        if host:
+            if t.is_cuda or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous host tensor" % name)
+            if dt is not None and t.dtype != dt:
+                raise TypeError("%s must be %s, got %s" % (name, dt, t.dtype))
+        else:
+            _need(t, name, dt)
+    if zt is not None and (zt.shape != z.shape or zt.device != z.device):
+        raise ValueError("teacher logits %s do not match the student's %s" % (tuple(zt.shape), tuple(z.shape)))
     N, C, h, w = z.shape
     H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
-    S = bits.shape[1]
     if tuple(spx.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W) or bits.shape[0] != N:
         raise ValueError("shape mismatch between inputs %s%s, superpixels %s, spmasks %s, targets %s"
                          % (tuple(z.shape), "" if size is None else " at size %s" % ((H, W),), tuple(spx.shape), tuple(mask.shape),
                             tuple(bits.shape)))
-    dev = z.device
-    if flags & _lib.LOSS_GROUP:             # accumulators and the arg-pixel table from ONE zero-filled allocation (one memset)
-        buf = torch.zeros(_lib.ACC_WORDS + N * S * C, dtype=torch.int64, device=dev)
-        acc, gmax = buf[:_lib.ACC_WORDS], buf[_lib.ACC_WORDS:].view(N, S, C)
-    else:
-        acc, gmax = torch.zeros(_lib.ACC_WORDS, dtype=torch.int64, device=dev), None
-    losses = torch.empty(3 if weights is None else 4, dtype=torch.float32, device=dev)
+    return mask, N, C, H, W, bits.shape[1], (0, 0) if size is None else (h, w)
+
+
+def _loss_buffers(N, S, C, flags, dev, words=_lib.ACC_WORDS, wgroup=False):
+    """(acc i64 [words], gmax i64 [N,S,C], tmax int32 [N,S,C]) as views of ONE zero-filled allocation (one memset): the arg-pixel table
+    only with LOSS_GROUP, the teacher's table only for the wgroup family; None for what is not there."""
+    n = N * S * C if flags & _lib.LOSS_GROUP else 0
+    buf = torch.zeros(words + n + ((n + 1) // 2 if wgroup else 0), dtype=torch.int64, device=dev)
+    gmax = buf[words:words + n].view(N, S, C) if n else None
+    tmax = buf[words + n:].view(torch.int32)[:n].view(N, S, C) if wgroup else None
+    return buf[:words], gmax, tmax
+
+
+def _loss_fwd(z, acc, gmax, n_losses, reduce_acc, entry, head, values_entry, values_head, finalizes=False):
+    """The forward body every family shares.  ``entry(*head, stream)`` is the scan, followed by the group finalize when there is a
+    table, ``reduce_acc(acc)`` (data parallel: between the sums and the division), and ``values_entry(acc, *values_head, losses,
+    stream)``.  ``finalizes``: the entry finalizes itself, ``entry(*head, losses, stream)``, and leaves the values too unless
+    ``reduce_acc`` has to run first.  Returns losses f32 [n_losses]."""
+    losses = torch.empty(n_losses, dtype=torch.float32, device=z.device)
     lib = _lib.load()
-    with torch.cuda.device(dev):
+    with torch.cuda.device(z.device):
         st = _stream(z)
-        if size is None:
-            _lib.check(lib.mas_partial_loss_fwd(z.data_ptr(), spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
-                                                N, C, H, W, S, invT, flags, _opt(gmax), acc.data_ptr(), st), "mas_partial_loss_fwd")
-        else:
-            _lib.check(lib.mas_partial_loss_fwd_lowres(z.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
-                                                       N, C, H, W, S, invT, flags, _opt(gmax), acc.data_ptr(), st),
-                       "mas_partial_loss_fwd_lowres")
-        if gmax is not None:
+        own = (None if reduce_acc is not None else losses.data_ptr(),) if finalizes else ()
+        _lib.check(getattr(lib, entry)(*head, *own, st), entry)
+        if gmax is not None and not finalizes:
             _lib.check(lib.mas_group_finalize(gmax.data_ptr(), gmax.numel(), acc.data_ptr(), st), "mas_group_finalize")
         if reduce_acc is not None:
             reduce_acc(acc)
-        if weights is None:
-            _lib.check(lib.mas_loss_values(acc.data_ptr(), flags, losses.data_ptr(), st), "mas_loss_values")
-        else:
-            _need(weights, "weights", torch.float32)
-            _lib.check(lib.mas_loss_values_weighted(acc.data_ptr(), flags, weights.data_ptr(), losses.data_ptr(), st), "mas_loss_values_weighted")
+        if reduce_acc is not None or not finalizes:
+            _lib.check(getattr(lib, values_entry)(acc.data_ptr(), *values_head, losses.data_ptr(), st), values_entry)
+    return losses
+
+
+def _loss_bwd(z, size, acc, n_scale, want_fix, scales_entry, scales_head, entry, head, dims, both=True):
+    """The backward body every family shares: ``scales_entry(acc, *scales_head, scale, stream)``, the scan ``entry(*head, scale, *dims,
+    dz, fix, stream)`` (``both`` False: the plain family's entries take dz or fix alone) and, at low resolution (``size`` given),
+    the pass that rounds the int64 fixed-point sums ``fix`` to f32.  Returns dz, or (dz, fix)."""
+    dev = z.device
+    scale = torch.empty(n_scale, dtype=torch.float32, device=dev)
+    fix = None if size is None else torch.zeros(z.shape, dtype=torch.int64, device=dev)
+    dz = torch.empty_like(z)
+    out = (dz.data_ptr(), _opt(fix)) if both else ((dz if fix is None else fix).data_ptr(),)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = _stream(z)
+        _lib.check(getattr(lib, scales_entry)(acc.data_ptr(), *scales_head, scale.data_ptr(), st), scales_entry)
+        _lib.check(getattr(lib, entry)(*head, scale.data_ptr(), *dims, *out, st), entry)
+        if fix is not None:
+            _lib.check(lib.mas_fix_to_float(fix.data_ptr(), fix.numel(), _lib.GRAD_FRAC, dz.data_ptr(), st), "mas_fix_to_float")
+    return (dz, fix) if want_fix else dz
+
+
+def _values_call(flags, weights):
+    """The values entry of the plain family and its head: three losses, or four with the weighted objective."""
+    if weights is None:
+        return "mas_loss_values", (flags,)
+    return "mas_loss_values_weighted", (flags, _need(weights, "weights", torch.float32).data_ptr())
+
+
+def _partial_loss_fwd(z, size, spx, mask, bits, invT, flags, reduce_acc, weights):
+    """The step-by-step forward on ``z`` [N,C,H,W] (``size`` None) or on the bilinear upsampling of ``z`` [N,C,h,w] to ``size`` =
+    (H, W), which is never materialised: scan, group finalize, ``reduce_acc``, loss values."""
+    mask, N, C, H, W, S, hw = _loss_shapes(z, None, size, spx, mask, bits)
+    acc, gmax, _ = _loss_buffers(N, S, C, flags, z.device)
+    head = (z.data_ptr(), *(() if size is None else hw), spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), N, C, H, W, S, invT,
+            flags, _opt(gmax), acc.data_ptr())
+    values_entry, values_head = _values_call(flags, weights)
+    losses = _loss_fwd(z, acc, gmax, n_losses=3 if weights is None else 4, reduce_acc=reduce_acc,
+                       entry="mas_partial_loss_fwd" if size is None else "mas_partial_loss_fwd_lowres", head=head,
+                       values_entry=values_entry, values_head=values_head)
     return losses, acc, gmax
 
 
 def _partial_loss_bwd(z, size, spx, mask, bits, gmax, acc, grad_out, invT, flags, want_fix, weights):
     """The step-by-step backward of ``_partial_loss_fwd``: the gradient with respect to ``z``.  At low resolution (``size`` given) it
     is summed in int64 fixed point and rounded to f32 by a pass of its own."""
-    mask = _mask_u8(mask)
-    _need(grad_out, "grad_out", torch.float32)
-    N, C, h, w = z.shape
-    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
-    S = bits.shape[1]
-    dev = z.device
-    scale = torch.empty(3, dtype=torch.float32, device=dev)
-    fix = None if size is None else torch.zeros((N, C, h, w), dtype=torch.int64, device=dev)
-    dz = torch.empty_like(z)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = _stream(z)
-        if weights is None:
-            _lib.check(lib.mas_loss_scales(acc.data_ptr(), grad_out.data_ptr(), flags, scale.data_ptr(), st), "mas_loss_scales")
-        else:               # grad_out is dL/d(total) [1]; the chain rule through the weighted sum happens in the kernel
-            _lib.check(lib.mas_loss_scales_weighted(acc.data_ptr(), grad_out.data_ptr(), weights.data_ptr(), flags, scale.data_ptr(), st),
-                       "mas_loss_scales_weighted")
-        if size is None:
-            _lib.check(lib.mas_partial_loss_bwd(z.data_ptr(), spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), _opt(gmax),
-                                                scale.data_ptr(), N, C, H, W, S, invT, flags, dz.data_ptr(), st), "mas_partial_loss_bwd")
-        else:
-            _lib.check(lib.mas_partial_loss_bwd_lowres(z.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
-                                                       _opt(gmax), scale.data_ptr(), N, C, H, W, S, invT, flags, fix.data_ptr(), st),
-                       "mas_partial_loss_bwd_lowres")
-            _lib.check(lib.mas_fix_to_float(fix.data_ptr(), fix.numel(), _lib.GRAD_FRAC, dz.data_ptr(), st), "mas_fix_to_float")
-    return (dz, fix) if want_fix else dz
+    mask, N, C, H, W, S, hw = _loss_shapes(z, None, size, spx, mask, bits, grad_out)
+    # with weights, grad_out is dL/d(total) [1]; the chain rule through the weighted sum happens in the kernel
+    scales_entry, scales_head = (("mas_loss_scales", (grad_out.data_ptr(), flags)) if weights is None
+                                 else ("mas_loss_scales_weighted", (grad_out.data_ptr(), weights.data_ptr(), flags)))
+    head = (z.data_ptr(), *(() if size is None else hw), spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), _opt(gmax))
+    return _loss_bwd(z, size, acc, n_scale=3, want_fix=want_fix, scales_entry=scales_entry, scales_head=scales_head,
+                     entry="mas_partial_loss_bwd" if size is None else "mas_partial_loss_bwd_lowres", head=head,
+                     dims=(N, C, H, W, S, invT, flags), both=False)
 
 
 def partial_loss_fwd(z, spx, mask, bits, invT, flags, reduce_acc=None):
@@ -249,21 +288,7 @@ def partial_loss_reference(z, spx, mask, bits, invT, flags, grad_out=None):
     csrc/partial_label.h (``mas_partial_loss_reference``), the CPU-side statement of the arithmetic the scans are checked against.
     ``flags``: LOSS_CE, optionally with LOSS_DECOMP and one of LOSS_RC / LOSS_TOPONE.  Returns (losses f32[3], acc i64[8]) and, with
     ``grad_out`` (f32[3], the upstream gradients of (ce, mc, group)), dz [N,C,H,W] as a third value.  Needs no GPU."""
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    for t, name, dt in ((z, "z", torch.float32), (spx, "spx", None), (mask, "mask", torch.uint8), (bits, "bits", torch.int32),
-                        (grad_out, "grad_out", torch.float32)):
-        if t is None:
-            continue
-        if t.is_cuda or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous host tensor" % name)
-        if dt is not None and t.dtype != dt:
-            raise TypeError("%s must be %s, got %s" % (name, dt, t.dtype))
-    N, C, H, W = z.shape
-    S = bits.shape[1]
-    if tuple(spx.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W) or bits.shape[0] != N:
-        raise ValueError("shape mismatch between inputs %s, superpixels %s, spmasks %s, targets %s"
-                         % (tuple(z.shape), tuple(spx.shape), tuple(mask.shape), tuple(bits.shape)))
+    mask, N, C, H, W, S, _ = _loss_shapes(z, None, None, spx, mask, bits, grad_out, host=True)
     acc = torch.zeros(_lib.ACC_WORDS, dtype=torch.int64)
     losses = torch.zeros(3, dtype=torch.float32)
     dz = torch.empty_like(z) if grad_out is not None else None
@@ -284,49 +309,23 @@ def partial_loss_fwd_fused(z, size, spx, mask, invT, flags, targets=None, cols_u
     (u8 [N,S,cols], masks over the first ``cols_used`` columns are formed in the prep launch) or ready ``bits`` (int32 [N,S]).
     ``weights`` f32 [3]: losses gets a fourth entry, the weighted objective.  ``reduce_acc`` (data parallel): called on the
     accumulators between the scans and the division.  Returns (losses, LossState)."""
-    _need(z, "inputs", torch.float32)
-    _need(spx, "superpixels")
-    mask = _mask_u8(mask)
-    N, C = z.shape[0], z.shape[1]
-    low = size is not None
-    H, W = (int(size[0]), int(size[1])) if low else (z.shape[2], z.shape[3])
-    h, w = (z.shape[2], z.shape[3]) if low else (0, 0)
-    if targets is not None:
-        _need(targets, "targets", torch.uint8)
-        S, cols = targets.shape[1], targets.shape[2]
-        cols_used = cols if cols_used is None else int(cols_used)
-        if targets.shape[0] != N:
-            raise ValueError("targets %s do not match the batch of %d" % (tuple(targets.shape), N))
+    if targets is None:
+        mask, N, C, H, W, S, (h, w) = _loss_shapes(z, None, size, spx, mask, bits)
     else:
-        _need(bits, "bits", torch.int32)
-        S, cols, cols_used = bits.shape[1], 0, 0
-        if bits.shape[0] != N:
-            raise ValueError("bits %s do not match the batch of %d" % (tuple(bits.shape), N))
-    if tuple(spx.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W):
-        raise ValueError("shape mismatch between inputs %s at size %s, superpixels %s, spmasks %s"
-                         % (tuple(z.shape), (H, W), tuple(spx.shape), tuple(mask.shape)))
-    dev = z.device
-    lib = _lib.load()
-    nbytes = int(lib.mas_partial_loss_work_bytes(N, S, C, flags))
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)          # (zeroed by the prep launch)
-    losses = torch.empty(3 if weights is None else 4, dtype=torch.float32, device=dev)
-    if weights is not None:
-        _need(weights, "weights", torch.float32)
+        mask, N, C, H, W, S, (h, w) = _loss_shapes(z, None, size, spx, mask, targets, bits_dtype=torch.uint8)
+    cols = 0 if targets is None else targets.shape[2]
+    cols_used = 0 if targets is None else cols if cols_used is None else int(cols_used)
+    values_entry, values_head = _values_call(flags, weights)
+    nbytes = int(_lib.load().mas_partial_loss_work_bytes(N, S, C, flags))
+    work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=z.device)     # (zeroed by the prep launch)
     st8 = LossState()
     st8.work, st8.acc, st8.N, st8.S, st8.C, st8.flags = work, work[:_lib.ACC_WORDS], N, S, C, flags
     st8.gmax = work[_lib.ACC_WORDS:_lib.ACC_WORDS + N * S * C].view(N, S, C) if flags & _lib.LOSS_GROUP else None
     st8.bits = bits
-    with torch.cuda.device(dev):
-        st = _stream(z)
-        _lib.check(lib.mas_partial_loss_fwd_fused(z.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), _opt(targets), cols, cols_used,
-                                                  _opt(bits), N, C, H, W, S, invT, flags, _opt(weights), work.data_ptr(), work.numel() * 8,
-                                                  None if reduce_acc is not None else losses.data_ptr(), st), "mas_partial_loss_fwd_fused")
-        if reduce_acc is not None:
-            reduce_acc(st8.acc)
-            if weights is None:
-                _lib.check(lib.mas_loss_values(st8.acc.data_ptr(), flags, losses.data_ptr(), st), "mas_loss_values")
-            else:
-                _lib.check(lib.mas_loss_values_weighted(st8.acc.data_ptr(), flags, weights.data_ptr(), losses.data_ptr(), st), "mas_loss_values_weighted")
+    head = (z.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), _opt(targets), cols, cols_used, _opt(bits), N, C, H, W, S, invT,
+            flags, _opt(weights), work.data_ptr(), work.numel() * 8)
+    losses = _loss_fwd(z, st8.acc, st8.gmax, n_losses=3 if weights is None else 4, reduce_acc=reduce_acc, entry="mas_partial_loss_fwd_fused",
+                       head=head, values_entry=values_entry, values_head=values_head, finalizes=True)
     return losses, st8
 
 
@@ -353,31 +352,15 @@ def partial_loss_bwd_fused(z, size, spx, mask, state, grad, invT, weights=None, 
 LOSS_TOP1, LOSS_ENT, LOSS_WITHIN = _lib.LOSS_TOP1, _lib.LOSS_ENT, _lib.LOSS_WITHIN
 
 
-def _teacher_shapes(z, zt, size, spx, mask, bits, flags, host=False):
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    for t, name, dt in ((z, "inputs", torch.float32), (zt, "plbl_inputs", torch.float32), (spx, "superpixels", None),
-                        (mask, "spmasks", torch.uint8), (bits, "bits", torch.int32)):
-        if t is None:
-            continue
-        if host:
-            if t.is_cuda or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous host tensor" % name)
-            if dt is not None and t.dtype != dt:
-                raise TypeError("%s must be %s, got %s" % (name, dt, t.dtype))
-        else:
-            _need(t, name, dt)
+def _teacher_shapes(z, zt, size, spx, mask, bits, flags, grad_out=None, host=False):
     if (flags & _lib.LOSS_TOP1) and zt is None:
         raise ValueError("LOSS_TOP1 needs the teacher's logits")
-    if zt is not None and (zt.shape != z.shape or zt.device != z.device):
-        raise ValueError("teacher logits %s do not match the student's %s" % (tuple(zt.shape), tuple(z.shape)))
-    N, C, h, w = z.shape
-    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
-    if tuple(spx.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W) or bits.shape[0] != N:
-        raise ValueError("shape mismatch between inputs %s%s, superpixels %s, spmasks %s, targets %s"
-                         % (tuple(z.shape), "" if size is None else " at size %s" % ((H, W),), tuple(spx.shape), tuple(mask.shape),
-                            tuple(bits.shape)))
-    return mask, N, C, H, W, bits.shape[1], (0, 0) if size is None else (h, w)
+    return _loss_shapes(z, zt, size, spx, mask, bits, grad_out, host)
+
+
+def _teacher_head(z, zt, hw, spx, mask, bits):
+    """What the scan entry points of both teacher families begin with."""
+    return (z.data_ptr(), _opt(zt), *hw, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr())
 
 
 def teacher_loss_fwd(z, zt, size, spx, mask, bits, invT, invT_x, plbl_th, flags, reduce_acc=None):
@@ -385,54 +368,28 @@ def teacher_loss_fwd(z, zt, size, spx, mask, bits, invT, invT_x, plbl_th, flags,
     logits, shaped as ``z``) or LOSS_ENT (``zt`` None) beside LOSS_CE / LOSS_DECOMP / the group flags.  ``invT``: the ce / group
     terms' inverse temperature, ``invT_x``: the fourth slot's own.  ``z`` [N,C,H,W] with ``size`` None, or quarter-resolution
     [N,C,h,w] upsampled in-kernel to ``size``.  Returns (losses f32[4] = ce, mc, group, x; acc i64[16]; gmax or None)."""
-    mask, N, C, H, W, S, (h, w) = _teacher_shapes(z, zt, size, spx, mask, bits, flags)
-    dev = z.device
-    words = _lib.TEACHER_ACC_WORDS
-    if flags & _lib.LOSS_GROUP:
-        buf = torch.zeros(words + N * S * C, dtype=torch.int64, device=dev)
-        acc, gmax = buf[:words], buf[words:].view(N, S, C)
-    else:
-        acc, gmax = torch.zeros(words, dtype=torch.int64, device=dev), None
-    losses = torch.empty(4, dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = _stream(z)
-        _lib.check(lib.mas_teacher_loss_fwd(z.data_ptr(), _opt(zt), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), N, C,
-                                            H, W, S, invT, invT_x, plbl_th, flags, _opt(gmax), acc.data_ptr(), st), "mas_teacher_loss_fwd")
-        if gmax is not None:
-            _lib.check(lib.mas_group_finalize(gmax.data_ptr(), gmax.numel(), acc.data_ptr(), st), "mas_group_finalize")
-        if reduce_acc is not None:
-            reduce_acc(acc)
-        _lib.check(lib.mas_teacher_loss_values(acc.data_ptr(), flags, losses.data_ptr(), st), "mas_teacher_loss_values")
+    mask, N, C, H, W, S, hw = _teacher_shapes(z, zt, size, spx, mask, bits, flags)
+    acc, gmax, _ = _loss_buffers(N, S, C, flags, z.device, words=_lib.TEACHER_ACC_WORDS)
+    head = (*_teacher_head(z, zt, hw, spx, mask, bits), N, C, H, W, S, invT, invT_x, plbl_th, flags, _opt(gmax), acc.data_ptr())
+    losses = _loss_fwd(z, acc, gmax, n_losses=4, reduce_acc=reduce_acc, entry="mas_teacher_loss_fwd", head=head,
+                       values_entry="mas_teacher_loss_values", values_head=(flags,))
     return losses, acc, gmax
 
 
 def teacher_loss_bwd(z, zt, size, spx, mask, bits, gmax, acc, grad_out, invT, invT_x, plbl_th, flags, want_fix=False):
     """Backward scan of ``teacher_loss_fwd``: the gradient with respect to ``z`` for upstream gradients ``grad_out`` f32[4]; the
     teacher is a constant.  At quarter resolution the sums are int64 fixed point (``want_fix`` returns them too)."""
-    mask, N, C, H, W, S, (h, w) = _teacher_shapes(z, zt, size, spx, mask, bits, flags)
-    _need(grad_out, "grad_out", torch.float32)
-    dev = z.device
-    scale = torch.empty(4, dtype=torch.float32, device=dev)
-    fix = None if size is None else torch.zeros(z.shape, dtype=torch.int64, device=dev)
-    dz = torch.empty_like(z)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = _stream(z)
-        _lib.check(lib.mas_teacher_loss_scales(acc.data_ptr(), grad_out.data_ptr(), flags, scale.data_ptr(), st), "mas_teacher_loss_scales")
-        _lib.check(lib.mas_teacher_loss_bwd(z.data_ptr(), _opt(zt), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
-                                            _opt(gmax), scale.data_ptr(), N, C, H, W, S, invT, invT_x, plbl_th, flags, dz.data_ptr(), _opt(fix),
-                                            st), "mas_teacher_loss_bwd")
-        if fix is not None:
-            _lib.check(lib.mas_fix_to_float(fix.data_ptr(), fix.numel(), _lib.GRAD_FRAC, dz.data_ptr(), st), "mas_fix_to_float")
-    return (dz, fix) if want_fix else dz
+    mask, N, C, H, W, S, hw = _teacher_shapes(z, zt, size, spx, mask, bits, flags, grad_out)
+    return _loss_bwd(z, size, acc, n_scale=4, want_fix=want_fix, scales_entry="mas_teacher_loss_scales", scales_head=(grad_out.data_ptr(), flags),
+                     entry="mas_teacher_loss_bwd", head=(*_teacher_head(z, zt, hw, spx, mask, bits), _opt(gmax)),
+                     dims=(N, C, H, W, S, invT, invT_x, plbl_th, flags))
 
 
 def teacher_loss_reference(z, zt, spx, mask, bits, invT, invT_x, plbl_th, flags, grad_out=None):
     """Every term of ``teacher_loss_fwd`` / ``_bwd`` at full resolution on HOST tensors: the library's plain loop through
     csrc/partial_label.h and csrc/teacher_terms.h (``mas_teacher_loss_reference``).  Returns (losses f32[4], acc i64[16], gmax i64
     [N,S,C] or None) and, with ``grad_out`` f32[4], dz [N,C,H,W] as a fourth value.  Needs no GPU."""
-    mask, N, C, H, W, S, _ = _teacher_shapes(z, zt, None, spx, mask, bits, flags, host=True)
+    mask, N, C, H, W, S, _ = _teacher_shapes(z, zt, None, spx, mask, bits, flags, grad_out, host=True)
     acc = torch.zeros(_lib.TEACHER_ACC_WORDS, dtype=torch.int64)
     gmax = torch.zeros((N, S, C), dtype=torch.int64) if flags & _lib.LOSS_GROUP else None
     losses = torch.zeros(4, dtype=torch.float32)
@@ -449,12 +406,12 @@ def teacher_loss_reference(z, zt, spx, mask, bits, invT, invT_x, plbl_th, flags,
 LOSS_WGROUP = _lib.LOSS_WGROUP
 
 
-def _wgroup_shapes(z, zt, size, spx, mask, bits, flags, host=False):
+def _wgroup_shapes(z, zt, size, spx, mask, bits, flags, grad_out=None, host=False):
     if not (flags & _lib.LOSS_WGROUP) or not (flags & _lib.LOSS_GROUP):
         raise ValueError("the wgroup entry points take LOSS_WGROUP together with LOSS_GROUP")
     if zt is None:
         raise ValueError("LOSS_WGROUP needs the teacher's logits")
-    return _teacher_shapes(z, zt, size, spx, mask, bits, 0, host=host)
+    return _loss_shapes(z, zt, size, spx, mask, bits, grad_out, host)
 
 
 def wgroup_loss_fwd(z, zt, size, spx, mask, bits, invT, flags, reduce_acc=None):
@@ -462,50 +419,28 @@ def wgroup_loss_fwd(z, zt, size, spx, mask, bits, invT, flags, reduce_acc=None):
     LOSS_CE / LOSS_DECOMP / LOSS_GROUP_ONLY_MULTI; ``zt`` = the eval-mode teacher's logits, shaped as ``z``, soft-maxed at the same
     ``invT``.  ``z`` [N,C,H,W] with ``size`` None, or quarter-resolution [N,C,h,w] upsampled in-kernel to ``size``.  Returns (losses
     f32[3] = ce, mc, group; acc i64[8]; gmax i64[N,S,C]; tmax int32[N,S,C], the teacher's maxima as probability bits)."""
-    mask, N, C, H, W, S, (h, w) = _wgroup_shapes(z, zt, size, spx, mask, bits, flags)
-    dev = z.device
-    buf = torch.zeros(_lib.ACC_WORDS + N * S * C + (N * S * C + 1) // 2, dtype=torch.int64, device=dev)     # one memset for all three
-    acc, gmax = buf[:_lib.ACC_WORDS], buf[_lib.ACC_WORDS:_lib.ACC_WORDS + N * S * C].view(N, S, C)
-    tmax = buf[_lib.ACC_WORDS + N * S * C:].view(torch.int32)[:N * S * C].view(N, S, C)
-    losses = torch.empty(3, dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = _stream(z)
-        _lib.check(lib.mas_wgroup_loss_fwd(z.data_ptr(), zt.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), N, C,
-                                           H, W, S, invT, flags, gmax.data_ptr(), tmax.data_ptr(), acc.data_ptr(),
-                                           None if reduce_acc is not None else losses.data_ptr(), st), "mas_wgroup_loss_fwd")
-        if reduce_acc is not None:
-            reduce_acc(acc)
-            _lib.check(lib.mas_loss_values(acc.data_ptr(), flags & ~_lib.LOSS_WGROUP, losses.data_ptr(), st), "mas_loss_values")
+    mask, N, C, H, W, S, hw = _wgroup_shapes(z, zt, size, spx, mask, bits, flags)
+    acc, gmax, tmax = _loss_buffers(N, S, C, flags, z.device, wgroup=True)
+    head = (*_teacher_head(z, zt, hw, spx, mask, bits), N, C, H, W, S, invT, flags, gmax.data_ptr(), tmax.data_ptr(), acc.data_ptr())
+    losses = _loss_fwd(z, acc, gmax, n_losses=3, reduce_acc=reduce_acc, entry="mas_wgroup_loss_fwd", head=head,
+                       values_entry="mas_loss_values", values_head=(flags & ~_lib.LOSS_WGROUP,), finalizes=True)
     return losses, acc, gmax, tmax
 
 
 def wgroup_loss_bwd(z, zt, size, spx, mask, bits, gmax, tmax, acc, grad_out, invT, flags, want_fix=False):
     """Backward scan of ``wgroup_loss_fwd``: the gradient with respect to ``z`` for upstream gradients ``grad_out`` f32[3]; both
     tables are read, the teacher is a constant.  At quarter resolution the sums are int64 fixed point (``want_fix`` returns them)."""
-    mask, N, C, H, W, S, (h, w) = _wgroup_shapes(z, zt, size, spx, mask, bits, flags)
-    _need(grad_out, "grad_out", torch.float32)
-    dev = z.device
-    scale = torch.empty(3, dtype=torch.float32, device=dev)
-    fix = None if size is None else torch.zeros(z.shape, dtype=torch.int64, device=dev)
-    dz = torch.empty_like(z)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = _stream(z)
-        _lib.check(lib.mas_loss_scales(acc.data_ptr(), grad_out.data_ptr(), flags & ~_lib.LOSS_WGROUP, scale.data_ptr(), st), "mas_loss_scales")
-        _lib.check(lib.mas_wgroup_loss_bwd(z.data_ptr(), zt.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(),
-                                           gmax.data_ptr(), tmax.data_ptr(), scale.data_ptr(), N, C, H, W, S, invT, flags, dz.data_ptr(),
-                                           _opt(fix), st), "mas_wgroup_loss_bwd")
-        if fix is not None:
-            _lib.check(lib.mas_fix_to_float(fix.data_ptr(), fix.numel(), _lib.GRAD_FRAC, dz.data_ptr(), st), "mas_fix_to_float")
-    return (dz, fix) if want_fix else dz
+    mask, N, C, H, W, S, hw = _wgroup_shapes(z, zt, size, spx, mask, bits, flags, grad_out)
+    return _loss_bwd(z, size, acc, n_scale=3, want_fix=want_fix, scales_entry="mas_loss_scales",
+                     scales_head=(grad_out.data_ptr(), flags & ~_lib.LOSS_WGROUP), entry="mas_wgroup_loss_bwd",
+                     head=(*_teacher_head(z, zt, hw, spx, mask, bits), gmax.data_ptr(), tmax.data_ptr()), dims=(N, C, H, W, S, invT, flags))
 
 
 def wgroup_loss_reference(z, zt, spx, mask, bits, invT, flags, grad_out=None):
     """Every term of ``wgroup_loss_fwd`` / ``_bwd`` at full resolution on HOST tensors: the library's plain loop through
     csrc/partial_label.h and csrc/teacher_terms.h (``mas_wgroup_loss_reference``).  Returns (losses f32[3], acc i64[8], gmax i64
     [N,S,C], tmax int32[N,S,C]) and, with ``grad_out`` f32[3], dz [N,C,H,W] as a fifth value.  Needs no GPU."""
-    mask, N, C, H, W, S, _ = _wgroup_shapes(z, zt, None, spx, mask, bits, flags, host=True)
+    mask, N, C, H, W, S, _ = _wgroup_shapes(z, zt, None, spx, mask, bits, flags, grad_out, host=True)
     acc = torch.zeros(_lib.ACC_WORDS, dtype=torch.int64)
     gmax = torch.zeros((N, S, C), dtype=torch.int64)
     tmax = torch.zeros((N, S, C), dtype=torch.int32)

@@ -80,28 +80,17 @@ def _fused_backward(ctx, grad):
 
 class _PartialLossFn(torch.autograd.Function):
     """(ce, mc, group) = f(inputs): the forward direction (accumulators, arg-pixel table, loss values) and the backward direction
-    (one scan writing dz) are one library call each.  No host synchronisation in either direction."""
+    (one scan writing dz) are one library call each.  No host synchronisation in either direction.
 
-    @staticmethod
-    def forward(ctx, inputs, tgt, cols_used, superpixels, spmasks, invT, flags, sync):
-        losses, acc = _fused_forward(ctx, inputs, None, tgt, cols_used, superpixels, spmasks, invT, flags, sync, None)
-        return losses[0], losses[1], losses[2], acc
-
-    @staticmethod
-    def backward(ctx, g_ce, g_mc, g_group, _g_acc):
-        grad_out = torch.stack([g_ce, g_mc, g_group]).to(torch.float32).contiguous()
-        return _fused_backward(ctx, grad_out), None, None, None, None, None, None, None
-
-
-class _PartialLossLowResFn(torch.autograd.Function):
-    """(ce, mc, group) = f(zq) with the x4 bilinear upsampling of the logits evaluated inside both scans: the
-    full-resolution logits and their gradient never exist (``csrc/losses.hip`` LOWRES kernels).  Forward values are
-    bit-identical to ``_PartialLossFn`` on ``F.interpolate(zq, size, 'bilinear')``; the gradient of ``zq`` is an
+    ``size`` None: ``inputs`` are the full-resolution logits.  ``size`` = (H, W): they are the quarter-resolution logits, and their x4
+    bilinear upsampling is evaluated inside both scans -- the full-resolution logits and their gradient never exist (``csrc/losses.hip``
+    LOWRES kernels).  Forward values are bit-identical to those on ``F.interpolate(inputs, size, 'bilinear')``; the gradient is an
     order-independent fixed-point sum (run-to-run identical)."""
 
     @staticmethod
-    def forward(ctx, zq, size, tgt, cols_used, superpixels, spmasks, invT, flags, sync):
-        losses, acc = _fused_forward(ctx, zq, (int(size[0]), int(size[1])), tgt, cols_used, superpixels, spmasks, invT, flags, sync, None)
+    def forward(ctx, inputs, size, tgt, cols_used, superpixels, spmasks, invT, flags, sync):
+        size = None if size is None else (int(size[0]), int(size[1]))
+        losses, acc = _fused_forward(ctx, inputs, size, tgt, cols_used, superpixels, spmasks, invT, flags, sync, None)
         return losses[0], losses[1], losses[2], acc
 
     @staticmethod
@@ -137,7 +126,7 @@ def _all_reduce_sum(acc):
         dist.all_reduce(acc, op=dist.ReduceOp.SUM)
 
 
-def _run(inputs, targets, superpixels, spmasks, temp, flags, drop_last_column, sync=True):
+def _run(inputs, targets, superpixels, spmasks, temp, flags, drop_last_column, sync=True, size=None):
     """CONTRACT of the drop-in modules under torch.distributed: with ``sync`` (the default of every partial-label module below,
     attribute ``sync_normalisers`` where it is configurable) the returned loss is the objective over the GLOBAL batch, identical
     on every rank; a caller that lets DistributedDataParallel average the gradients must multiply it by the world size before
@@ -147,11 +136,13 @@ def _run(inputs, targets, superpixels, spmasks, temp, flags, drop_last_column, s
     ``sync``: under torch.distributed (world > 1) the integer sums and counts are all-reduced before the division, so
     every rank holds the SAME loss value -- the loss over the global batch.  The reference's skip-on-zero / raise-on-NaN
     decisions (``active_joint_multi.py:31-37``) are then global by construction: no rank can skip ``backward()`` while
-    its peers wait in the gradient all-reduce."""
+    its peers wait in the gradient all-reduce.
+
+    ``size`` = (H, W): ``inputs`` are the quarter-resolution logits (``_PartialLossFn``)."""
     if targets.dtype != torch.uint8:
         targets = targets.to(torch.uint8)
     cols = targets.shape[-1]
-    return _PartialLossFn.apply(inputs, targets.contiguous(), cols - 1 if drop_last_column else cols, superpixels, spmasks,
+    return _PartialLossFn.apply(inputs, size, targets.contiguous(), cols - 1 if drop_last_column else cols, superpixels, spmasks,
                                 ops.inv_temperature(temp), flags, sync)
 
 
@@ -188,7 +179,7 @@ class MyCrossEntropyLoss(nn.CrossEntropyLoss):
         if not self._fused(input, target):
             return super().forward(input / self.temperature, target)
         labels, mask, bits = self._labels_mask(input, target)
-        ce, _, _, self.last_acc = _PartialLossFn.apply(input, bits, None, labels, mask, ops.inv_temperature(self.temperature),
+        ce, _, _, self.last_acc = _PartialLossFn.apply(input, None, bits, None, labels, mask, ops.inv_temperature(self.temperature),
                                                         _lib.LOSS_CE | _lib.LOSS_TCE, self.sync_normalisers)
         return ce
 
@@ -198,9 +189,9 @@ class MyCrossEntropyLoss(nn.CrossEntropyLoss):
             up = torch.nn.functional.interpolate(quarter_logits, size=tuple(size), mode='bilinear', align_corners=False)
             return super().forward(up / self.temperature, target)
         labels, mask, bits = self._labels_mask(quarter_logits, target)
-        ce, _, _, self.last_acc = _PartialLossLowResFn.apply(quarter_logits, tuple(size), bits, None, labels, mask,
-                                                             ops.inv_temperature(self.temperature), _lib.LOSS_CE | _lib.LOSS_TCE,
-                                                             self.sync_normalisers)
+        ce, _, _, self.last_acc = _PartialLossFn.apply(quarter_logits, tuple(size), bits, None, labels, mask,
+                                                        ops.inv_temperature(self.temperature), _lib.LOSS_CE | _lib.LOSS_TCE,
+                                                        self.sync_normalisers)
         return ce
 
 
@@ -348,10 +339,8 @@ class FusedPartialLabelLoss(nn.Module):
     def forward_lowres(self, quarter_logits, size, targets, superpixels, spmasks):
         """The same three losses from the model's quarter-resolution logits (``net(images, lowres=True)``): the final x4
         bilinear upsampling (``models/segmentation/utils.py:25``) happens per selected pixel inside the scans."""
-        if targets.dtype != torch.uint8:
-            targets = targets.to(torch.uint8)
-        ce, mc, group, self.last_acc = _PartialLossLowResFn.apply(quarter_logits, tuple(size), targets.contiguous(), targets.shape[-1], superpixels, spmasks,
-                                                                  ops.inv_temperature(self.temp), self.flags, self.sync_normalisers)
+        ce, mc, group, self.last_acc = _run(quarter_logits, targets, superpixels, spmasks, self.temp, self.flags, False,
+                                            sync=self.sync_normalisers, size=tuple(size))
         return group, ce, mc
 
     def weighted_lowres(self, quarter_logits, size, targets, superpixels, spmasks, coeff, coeff_mc, coeff_gm):
