@@ -63,7 +63,8 @@ extern "C" {
  * MAS_OPL_WEIGHT_SIM and MAS_LCE_SIGNED flag bits (a library built before them answers MAS_ERR_RANGE to either bit), then
  * mas_teacher_loss_fwd / _bwd / _values / _scales and mas_teacher_loss_reference with the MAS_LOSS_TOP1 / MAS_LOSS_ENT /
  * MAS_LOSS_WITHIN flag bits (the mas_partial_loss_* entry points answer MAS_ERR_RANGE to them), then mas_wgroup_loss_fwd / _bwd and
- * mas_wgroup_loss_reference with the MAS_LOSS_WGROUP flag bit (a library built before them answers MAS_ERR_RANGE to the bit): new entry
+ * mas_wgroup_loss_reference with the MAS_LOSS_WGROUP flag bit (a library built before them answers MAS_ERR_RANGE to the bit), then
+ * mas_hier_group_fwd / _value / _bwd and mas_hier_group_reference: new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -388,6 +389,50 @@ int mas_simw_plbl_reference(const float* zq_p, const float* featq, int Ch, int h
                             const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, float invT, float invtau,
                             float* softw, int32_t* live, const float* zq, float invT_ce, const float* grad, uint64_t* acc, float* loss,
                             int64_t* dzq_fix);
+
+/* ---------------------------------------------------------------------------------------------
+ * Hierarchical group term (utils/loss.py:143-235 HierGroupMultiLabelCE, :439-533 AugHierGroupMultiLabelCE; the trainer
+ * active_joint_hier_multi).  Arithmetic: csrc/hier_group.h.  The decision of the group term -- the arg-pixel of every (superpixel,
+ * class of its target row) -- is spread over the whole FINE superpixel around that pixel: with `small` the ids of a finer map
+ * [N,H,W] (ids in [0, Ss); a pad pixel carries Ss), pair (s', c) = (small[arg-pixel], c) is counted once per arg-pixel that falls into
+ * s' (mult u32 [N,Ss,C], the multiplicity; any u32 [N,Ss], bit c set when mult > 0), and
+ *   loss = sum over the counted pixels p and the classes c of mult[small(p), c] * -log(p_c(p) + 1e-8)  /  (1 + n),
+ *   n    = sum over the counted pixels p and the classes c of mult[small(p), c],
+ * a pixel being counted when its mask byte is set, its small id lies in [0, Ss) and any[small] != 0.  The softmax runs at temperature
+ * 1.0 (the reference's constructor discards the temperature it is given), so there is no invT argument.
+ *   MAS_HIER_ONLY_MULTI  only superpixels with more than one target bit choose arg-pixels (--group_only_single)
+ *   MAS_HIER_NOCROPSP    the rows of bits of every superpixel id in [0, S) that occurs on the outermost row or column of its picture
+ *                        are cleared first (AugHierGroupMultiLabelCE, --nocropsp).  The caller's bits stay as they are: the cleared
+ *                        table is written to bits_eff u32 [N,S] (required with the flag, MAS_ERR_NULL; ignored without), which the
+ *                        caller hands to the merged-positive term -- the reference clears the trainer's tensor in place.
+ * Any other flag bit is MAS_ERR_RANGE.  spx_dtype and small_dtype: MAS_ID_* (MAS_ERR_DTYPE otherwise); 2 <= C <= MAS_MAX_CLASSES
+ * (MAS_ERR_CLASSES); S, Ss > 0; h <= H, w <= W (h = H, w = W is the full-resolution form: the taps are exactly (1, 0)).
+ *
+ * mas_hier_group_fwd: memsets, the group scan (mas_partial_loss_fwd_lowres with MAS_LOSS_GROUP at invT = 1, into `work`:
+ * mas_online_plbl_work_bytes(N, S, C) bytes, 8-byte aligned; the table gmax u64 [N,S,C] starts at its ninth word), one lane per table
+ * word for the pairs (integer atomics only: mult and any are the same bytes on every run), then the tile-queue forward.  mult, any
+ * (4-byte aligned) and acc u64 [2] = {fixed-point sum (MAS_LOSS_FRAC_BITS), n} (8-byte aligned) are zeroed by the call; loss (may be
+ * NULL) = sum / (1 + n).  mas_hier_group_value turns an all-reduced acc into the loss.
+ * mas_hier_group_bwd: dzq_fix int64 [N,C,h,w] (zeroed by the call; MAS_GRAD_FRAC_BITS) += the gradient of every counted pixel through
+ * its four taps for the upstream gradient grad [1] (device) -- integer sums, run-to-run identical bytes; dzq (may be NULL) = its
+ * rounding to f32.  The arg-pixel choice carries no gradient, so neither spx nor bits is read. */
+#define MAS_HIER_ONLY_MULTI 1
+#define MAS_HIER_NOCROPSP 2
+int mas_hier_group_fwd(const float* zq, int h, int w, const void* spx, int spx_dtype, const void* small, int small_dtype,
+                       const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, int Ss, int flags, void* work,
+                       size_t work_bytes, uint32_t* bits_eff /* [N,S] or NULL */, uint32_t* mult /* [N,Ss,C] */,
+                       uint32_t* any /* [N,Ss] */, uint64_t* acc /* [2] */, float* loss /* [1] or NULL */, void* stream);
+int mas_hier_group_value(const uint64_t* acc, float* loss, void* stream);
+int mas_hier_group_bwd(const float* zq, int h, int w, const void* small, int small_dtype, const uint8_t* mask, const uint32_t* mult,
+                       const uint32_t* any, const uint64_t* acc, const float* grad /* [1] */, int N, int C, int H, int W, int Ss,
+                       int64_t* dzq_fix /* [N,C,h,w] */, float* dzq /* [N,C,h,w] or NULL */, void* stream);
+/* The CPU-side statement of the whole chain: HOST pointers, no device is touched.  Writes gmax u64 [N,S,C] (may be NULL), bits_eff
+ * (as above), mult, any, acc [2], loss [1] (may be NULL) and, for grad [1], dzq_fix [N,C,h,w] (may be NULL).  The kernels are tested
+ * against it bit for bit. */
+int mas_hier_group_reference(const float* zq, int h, int w, const void* spx, int spx_dtype, const void* small, int small_dtype,
+                             const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, int Ss, int flags,
+                             const float* grad, uint64_t* gmax, uint32_t* bits_eff, uint32_t* mult, uint32_t* any, uint64_t* acc,
+                             float* loss, int64_t* dzq_fix);
 
 /* =============================================================================================
  * K4  ordering of the region scores and the budgeted selection walk

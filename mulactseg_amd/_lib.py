@@ -21,6 +21,7 @@ LOSS_TOP1, LOSS_ENT, LOSS_WITHIN = 128, 256, 512     # the fourth loss slot of t
 ACC_WORDS = 8
 TEACHER_ACC_WORDS, ACC_SUM_X, ACC_N_X = 16, 8, 9
 LOSS_WGROUP = 1024      # the teacher-weighted group term of the mas_wgroup_loss_* entry points (csrc/teacher_terms.h, wgroup)
+HIER_ONLY_MULTI, HIER_NOCROPSP = 1, 2       # mas_hier_group_*: --group_only_single, --nocropsp (csrc/hier_group.h)
 GRAD_FRAC = 44
 MS_MAX_SOURCES = 16
 
@@ -193,6 +194,12 @@ SIGNATURES = {
     "mas_soft_ce_bwd_lowres": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "mas_simw_plbl_reference": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _f, _vp, _vp, _vp,
                                      _vp]),
+    "mas_hier_group_fwd": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _c.c_size_t, _vp, _vp, _vp, _vp, _vp,
+                                _vp]),
+    "mas_hier_group_value": (_i, [_vp, _vp, _vp]),
+    "mas_hier_group_bwd": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mas_hier_group_reference": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp]),
 }
 
 _lib = None

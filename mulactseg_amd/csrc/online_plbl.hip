@@ -24,6 +24,9 @@
 //                         LabelCe  (k_label_ce_fwd / _bwd)  the labelled pixels; the mode's weight, MAS_LCE_SIGNED sums.
 //                         SoftCe   (k_soft_ce_fwd / _bwd)   the counted pixels (mask set, id in range) of the live pictures; cross
 //                                                           entropy against the soft target.
+//                         HierCe   (k_hier_fwd / _bwd)      the hierarchical group term (hier_group.h): the selected pixels of the fine
+//                                                           superpixels that hold an arg-pixel of the group scan, weighted per class
+//                                                           by the pair table `mult` that k_hier_pairs builds between the two scans.
 //   host_ce             the same two passes on host pointers through online_plbl.h, with host policies of its own:
 //                       mas_online_plbl_reference and mas_simw_plbl_reference, the statement the kernels are tested against.
 // losses.hip keeps a twin of queue_push, the tile compaction and the LDS image (another tap struct, the benchmarked training step).
@@ -31,6 +34,7 @@
 
 #include "common.h"
 #include "online_plbl.h"
+#include "hier_group.h"
 
 namespace {
 constexpr int kThreads = 256;
@@ -225,6 +229,8 @@ __device__ __forceinline__ void ce_probs(const float* __restrict__ zq, const Geo
 //   pixel(n, py, px, v, t, s, term)   probabilities v and tap t of a queued pixel, the policy's state s and the pixel's term;
 //                             returns whether it is counted;
 //   fix(term)                 what a counted term adds to the u64 sum;
+//   count(s)                  what a counted pixel adds to the count;
+//   scale(grad, count)        the backward's common factor from the upstream gradient and the forward's count;
 //   k(s, scale), dir(s, c, p_c)   the gradient of class c is k * dir.
 struct LabelCe {
     const float* zq; const unsigned char* labels; const float* weight;
@@ -244,6 +250,8 @@ struct LabelCe {
         return counted != 0;
     }
     __device__ __forceinline__ mas_u64 fix(float term) const { return mas_opl_fix_term(term, sgn); }
+    __device__ __forceinline__ mas_u64 count(const Px&) const { return 1; }
+    __device__ __forceinline__ float scale(float grad, mas_u64 n) const { return (grad / (float)n) * invT; }
     __device__ __forceinline__ float k(const Px& s, float scale) const { return scale * s.wgt; }
     __device__ __forceinline__ float dir(const Px& s, int c, float pc) const { return pc - ((c == s.lab) ? 1.0f : 0.0f); }
 };
@@ -277,11 +285,45 @@ struct SoftCe {
         return true;
     }
     __device__ __forceinline__ mas_u64 fix(float term) const { return mas_fix(term, MAS_LOSS_FRAC_BITS); }
+    __device__ __forceinline__ mas_u64 count(const Px&) const { return 1; }
+    __device__ __forceinline__ float scale(float grad, mas_u64 n) const { return (grad / (float)n) * invT; }
     __device__ __forceinline__ float k(const Px&, float scale) const { return scale; }
     __device__ __forceinline__ float dir(const Px& s, int c, float pc) const {
         const int in_y = (int)((s.Yc >> c) & 1u);
         const float wj = (in_y && s.multi) ? s.sw[(size_t)c * ((size_t)g.H * g.W)] : 1.0f;
         return mas_opl_soft_dir(pc, s.A, in_y, wj);
+    }
+};
+
+// g.S is the number of FINE superpixels here.  The softmax runs at temperature 1 (hier_group.h).
+struct HierCe {
+    const float* zq; const void* small; const unsigned char* mask; const unsigned* mult; const unsigned* any;
+    Geo g; int small_dtype; int tiles_x, tiles_y;
+    struct Px { unsigned Yc; const unsigned* m; float U; unsigned cnt; };
+
+    __device__ __forceinline__ bool runs(int) const { return true; }
+    __device__ __forceinline__ bool selects(size_t i, int) const {
+        if (!mask[i]) return false;
+        const int id = load_id_any(small, small_dtype, i);
+        if (id < 0 || id >= g.S) return false;
+        return any[(i / ((size_t)g.H * g.W)) * g.S + id] != 0u;
+    }
+    template <int CT, bool EXACT>
+    __device__ __forceinline__ bool pixel(int n, int py, int px, float (&v)[CT], OplTap& t, Px& s, float& term) const {
+        const int C = EXACT ? CT : g.C;
+        const size_t row = (size_t)n * g.S + load_id_any(small, small_dtype, ((size_t)n * g.H + py) * g.W + px);
+        s.Yc = C < 32 ? (any[row] & ((1u << C) - 1u)) : any[row];
+        s.m = mult + row * C;
+        ce_probs<CT, EXACT>(zq, g, 1.0f, n, py, px, v, t);
+        term = mas_hg_term<CT>(v, C, s.Yc, s.m, &s.U, &s.cnt);
+        return true;
+    }
+    __device__ __forceinline__ mas_u64 fix(float term) const { return mas_fix(term, MAS_LOSS_FRAC_BITS); }
+    __device__ __forceinline__ mas_u64 count(const Px& s) const { return s.cnt; }
+    __device__ __forceinline__ float scale(float grad, mas_u64 n) const { return mas_hg_scale(grad, n); }
+    __device__ __forceinline__ float k(const Px&, float scale) const { return scale; }
+    __device__ __forceinline__ float dir(const Px& s, int c, float pc) const {
+        return mas_hg_dir(pc, s.U, ((s.Yc >> c) & 1u) ? (float)s.m[c] : 0.0f);
     }
 };
 
@@ -302,7 +344,7 @@ __device__ __forceinline__ void ce_fwd(const P& a, mas_u64* __restrict__ acc) {
         float term;
         if (a.template pixel<CT, EXACT>(n, ty * kTileH + (int)(off >> 8), tx * kTileW + (int)(off & 255u), v, t, s, term)) {
             sum += a.fix(term);
-            cnt += 1;
+            cnt += a.count(s);
         }
     }
     const int lane = threadIdx.x & (MAS_WAVE - 1), wave = threadIdx.x / MAS_WAVE;
@@ -375,7 +417,7 @@ __device__ __forceinline__ void ce_bwd(const P& a, const mas_u64* __restrict__ a
     const QuarterImage<CT, EXACT> img{(lds_u64*)s_acc, dq + (size_t)n * C * hw, hw, a.g.w, make_tap(a.g.sh, ty * kTileH, a.g.h).i0,
                                       make_tap(a.g.sw, tx * kTileW, a.g.w).i0};
     img.zero();
-    const float scale = (grad[0] / (float)acc[1]) * a.invT;
+    const float scale = a.scale(grad[0], acc[1]);
     for (int i = threadIdx.x; i < nq; i += kThreads) {
         const unsigned off = queue[i];
         float v[CT];
@@ -412,14 +454,63 @@ template <int CT, bool EXACT>
 __global__ __launch_bounds__(kThreads) void k_soft_ce_bwd(const SoftCe a, const mas_u64* __restrict__ acc, const float* __restrict__ grad,
                                                            mas_u64* __restrict__ dq) { ce_bwd<CT, EXACT>(a, acc, grad, dq); }
 
+template <int CT, bool EXACT>
+__global__ __launch_bounds__(kThreads) void k_hier_fwd(const HierCe a, mas_u64* __restrict__ acc) { ce_fwd<CT, EXACT>(a, acc); }
+template <int CT, bool EXACT>
+__global__ __launch_bounds__(kThreads) void k_hier_bwd(const HierCe a, const mas_u64* __restrict__ acc, const float* __restrict__ grad,
+                                                        mas_u64* __restrict__ dq) { ce_bwd<CT, EXACT>(a, acc, grad, dq); }
+
 template <int CT, bool EXACT> auto fwd_kernel(const LabelCe&) { return &k_label_ce_fwd<CT, EXACT>; }
 template <int CT, bool EXACT> auto bwd_kernel(const LabelCe&) { return &k_label_ce_bwd<CT, EXACT>; }
 template <int CT, bool EXACT> auto fwd_kernel(const SoftCe&) { return &k_soft_ce_fwd<CT, EXACT>; }
 template <int CT, bool EXACT> auto bwd_kernel(const SoftCe&) { return &k_soft_ce_bwd<CT, EXACT>; }
+template <int CT, bool EXACT> auto fwd_kernel(const HierCe&) { return &k_hier_fwd<CT, EXACT>; }
+template <int CT, bool EXACT> auto bwd_kernel(const HierCe&) { return &k_hier_bwd<CT, EXACT>; }
 
 __global__ void k_label_ce_value(const mas_u64* __restrict__ acc, int flags, float* __restrict__ loss) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     loss[0] = mas_opl_value(acc[0], acc[1], flags);
+}
+
+// ---- the hierarchical group term between the two scans (hier_group.h) -----------------------------------------------------------------
+// One lane per word of the group scan's table [N,S,C]: the arg-pixel's fine superpixel s' takes the pair (s', c).
+__global__ __launch_bounds__(kThreads) void k_hier_pairs(const mas_u64* __restrict__ gmax, const void* __restrict__ small, int small_dtype,
+                                                          long long total, int S, int C, int HW, int Ss, unsigned* __restrict__ mult,
+                                                          unsigned* __restrict__ any) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const mas_u64 w64 = gmax[i];
+    if ((unsigned)(w64 >> 32) == 0u) return;
+    const unsigned pp = mas_opl_word_pixel(w64);
+    if (pp >= (unsigned)HW) return;
+    const int c = (int)(i % C);
+    const size_t n = (size_t)(i / ((long long)S * C));
+    const int id = load_id_any(small, small_dtype, n * HW + pp);
+    if (id < 0 || id >= Ss) return;
+    atomicAdd(&mult[(n * Ss + id) * C + c], 1u);
+    atomicOr(&any[n * Ss + id], 1u << c);
+}
+
+// One lane per pixel of the outermost rows and columns (2W + 2H per picture, the corners twice): its superpixel's row of out = 0.
+// Every writer writes the same value.
+__global__ __launch_bounds__(kThreads) void k_clear_boundary_bits(const void* __restrict__ spx, int spx_dtype, int N, int H, int W, int S,
+                                                                   unsigned* __restrict__ out) {
+    const int per = 2 * W + 2 * H;
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= (long long)N * per) return;
+    const int n = (int)(i / per), k = (int)(i % per);
+    int y, x;
+    if (k < W) { y = 0; x = k; }
+    else if (k < 2 * W) { y = H - 1; x = k - W; }
+    else if (k < 2 * W + H) { y = k - 2 * W; x = 0; }
+    else { y = k - 2 * W - H; x = W - 1; }
+    const int id = load_id_any(spx, spx_dtype, ((size_t)n * H + y) * W + x);
+    if (id >= 0 && id < S) out[(size_t)n * S + id] = 0u;
+}
+
+__global__ void k_hier_value(const mas_u64* __restrict__ acc, float* __restrict__ loss) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    loss[0] = mas_hg_value(acc[0], acc[1]);
 }
 
 // ---- dispatch -----------------------------------------------------------------------------------------------------------------------
@@ -637,18 +728,19 @@ long long host_id(const void* spx, int spx_dtype, size_t i) {
     return static_cast<const unsigned short*>(spx)[i];
 }
 
-// bits[n, id] of a valid pixel (mask set, id in range, more than one bit), 0 otherwise
-uint32_t host_valid_bits(const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits, int n, int S, size_t g, long long* id) {
+// bits[n, id] of a valid pixel (mask set, id in range, at least min_bits bits: more than one for the prototypes), 0 otherwise
+uint32_t host_valid_bits(const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits, int n, int S, size_t g, long long* id,
+                         int min_bits = 2) {
     if (!mask[g]) return 0;
     *id = (int)host_id(spx, spx_dtype, g);         // (the kernels' mas_load_id)
     if (*id < 0 || *id >= S) return 0;
     const uint32_t Y = bits[(size_t)n * S + (size_t)*id];
-    return __builtin_popcount(Y) > 1 ? Y : 0;
+    return __builtin_popcount(Y) >= min_bits ? Y : 0;
 }
 
 // the arg-pixel table [N,S,C] of the valid pixels (what the group scan leaves)
 void host_table(const float* zq_p, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask, const uint32_t* bits, int N, int C, int H,
-                int W, int S, float invT, uint64_t* table) {
+                int W, int S, float invT, uint64_t* table, int min_bits = 2) {
     const size_t HW = (size_t)H * W, hw = (size_t)h * w;
     const float sh = (float)h / (float)H, sw = (float)w / (float)W;
     for (size_t i = 0; i < (size_t)N * S * C; ++i) table[i] = 0;
@@ -656,7 +748,7 @@ void host_table(const float* zq_p, int h, int w, const void* spx, int spx_dtype,
         for (size_t pix = 0; pix < HW; ++pix) {
             const size_t gi = (size_t)n * HW + pix;
             long long id = 0;
-            const uint32_t Y = host_valid_bits(spx, spx_dtype, mask, bits, n, S, gi, &id);
+            const uint32_t Y = host_valid_bits(spx, spx_dtype, mask, bits, n, S, gi, &id, min_bits);
             if (!Y) continue;
             const OplTap t = mas_opl_tap(sh, sw, (int)(pix / W), (int)(pix % W), h, w);
             float p[MAS_MAX_CLASSES];
@@ -701,6 +793,9 @@ struct HostLabelCe {
         return counted != 0;
     }
     uint64_t fix(float term) const { return mas_opl_fix_term(term, sgn); }
+    uint64_t count(const Px&) const { return 1; }
+    float scale(float grad, uint64_t n, float invT) const { return (grad / (float)n) * invT; }
+    float value(uint64_t sum, uint64_t n, int flags) const { return mas_opl_value(sum, n, flags); }
     float k(const Px& s, float scale) const { return scale * s.wgt; }
     float dir(const Px& s, int c, float pc) const { return pc - ((c == s.lab) ? 1.0f : 0.0f); }
 };
@@ -722,11 +817,38 @@ struct HostSoftCe {
         return true;
     }
     uint64_t fix(float term) const { return mas_fix(term, MAS_LOSS_FRAC_BITS); }
+    uint64_t count(const Px&) const { return 1; }
+    float scale(float grad, uint64_t n, float invT) const { return (grad / (float)n) * invT; }
+    float value(uint64_t sum, uint64_t n, int flags) const { return mas_opl_value(sum, n, flags); }
     float k(const Px&, float scale) const { return scale; }
     float dir(const Px& s, int c, float pc) const {
         const int in_y = (int)((s.Yc >> c) & 1u);
         return mas_opl_soft_dir(pc, s.A, in_y, (in_y && s.multi) ? s.sw[(size_t)c * HW] : 1.0f);
     }
+};
+
+struct HostHierCe {
+    const void* small; int small_dtype; const uint8_t* mask; const uint32_t* mult; const uint32_t* any; int C, Ss;
+    struct Px { uint32_t Yc; const uint32_t* m; float U; uint32_t cnt; };
+
+    bool takes(int n, size_t i) const {
+        if (!mask[i]) return false;
+        const long long id = (int)host_id(small, small_dtype, i);
+        return id >= 0 && id < Ss && any[(size_t)n * Ss + (size_t)id] != 0u;
+    }
+    bool pixel(int n, size_t i, const float (&p)[MAS_MAX_CLASSES], Px& s, float& term) const {
+        const size_t row = (size_t)n * Ss + (size_t)(int)host_id(small, small_dtype, i);
+        s.Yc = C < 32 ? (any[row] & ((1u << C) - 1u)) : any[row];
+        s.m = mult + row * C;
+        term = mas_hg_term<MAS_MAX_CLASSES>(p, C, s.Yc, s.m, &s.U, &s.cnt);
+        return true;
+    }
+    uint64_t fix(float term) const { return mas_fix(term, MAS_LOSS_FRAC_BITS); }
+    uint64_t count(const Px& s) const { return s.cnt; }
+    float scale(float grad, uint64_t n, float) const { return mas_hg_scale(grad, n); }
+    float value(uint64_t sum, uint64_t n, int) const { return mas_hg_value(sum, n); }
+    float k(const Px&, float scale) const { return scale; }
+    float dir(const Px& s, int c, float pc) const { return mas_hg_dir(pc, s.U, ((s.Yc >> c) & 1u) ? (float)s.m[c] : 0.0f); }
 };
 
 // pass 0 counts and sums the terms of the counted pixels; pass 1, with dzq_fix, scatters their gradient through the four taps
@@ -738,7 +860,7 @@ void host_ce(const P& a, const float* zq, const Geo& g, int N, float invT, int v
     for (int pass = 0; pass < (dzq_fix ? 2 : 1); ++pass) {
         float scale = 0.0f;
         if (pass == 1) {
-            scale = (grad[0] / (float)acc[1]) * invT;
+            scale = a.scale(grad[0], acc[1], invT);
             for (size_t i = 0; i < (size_t)N * g.C * hw; ++i) dzq_fix[i] = 0;
         }
         for (int n = 0; n < N; ++n) {
@@ -754,7 +876,7 @@ void host_ce(const P& a, const float* zq, const Geo& g, int N, float invT, int v
                 if (!a.pixel(n, gi, p, s, term)) continue;
                 if (pass == 0) {
                     acc[0] += a.fix(term);
-                    acc[1] += 1;
+                    acc[1] += a.count(s);
                     continue;
                 }
                 const float k = a.k(s, scale);
@@ -769,7 +891,7 @@ void host_ce(const P& a, const float* zq, const Geo& g, int N, float invT, int v
                 }
             }
         }
-        if (pass == 0 && loss) loss[0] = mas_opl_value(acc[0], acc[1], value_flags);
+        if (pass == 0 && loss) loss[0] = a.value(acc[0], acc[1], value_flags);
     }
 }
 }  // namespace
@@ -879,5 +1001,126 @@ extern "C" int mas_simw_plbl_reference(const float* zq_p, const float* featq, in
     if (!acc) return MAS_ERR_NULL;
     if (dzq_fix && !grad) return MAS_ERR_NULL;
     host_ce(HostSoftCe{spx, spx_dtype, mask, bits, softw, live, C, S, HW}, zq, g, N, invT_ce, 0, grad, acc, loss, dzq_fix);
+    return 0;
+}
+
+// ---- the hierarchical group term (hier_group.h) ---------------------------------------------------------------------------------------
+namespace {
+int check_hier(const float* zq, const void* small, int small_dtype, const uint8_t* mask, const uint32_t* mult, const uint32_t* any,
+               const uint64_t* acc, int N, int C, int h, int w, int H, int W, int Ss) {
+    if (!zq || !small || !mask || !mult || !any || !acc) return MAS_ERR_NULL;
+    if (Ss <= 0) return MAS_ERR_SHAPE;
+    if (int e = check_geometry(N, C, h, w, H, W)) return e;
+    if (!id_dtype_ok(small_dtype)) return MAS_ERR_DTYPE;
+    if ((uintptr_t)mult % 4 != 0 || (uintptr_t)any % 4 != 0 || (uintptr_t)acc % 8 != 0) return MAS_ERR_ALIGN;
+    return 0;
+}
+
+HierCe hier_ce(const float* zq, int h, int w, const void* small, int small_dtype, const uint8_t* mask, const uint32_t* mult,
+               const uint32_t* any, int C, int H, int W, int Ss) {
+    return HierCe{zq, small, mask, mult, any, make_geo(C, 0, h, w, H, W, Ss), small_dtype, 0, 0};
+}
+}  // namespace
+
+extern "C" int mas_hier_group_value(const uint64_t* acc, float* loss, void* stream) {
+    if (!acc || !loss) return MAS_ERR_NULL;
+    hipLaunchKernelGGL(k_hier_value, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), reinterpret_cast<const mas_u64*>(acc), loss);
+    return mas_launch_status();
+}
+
+extern "C" int mas_hier_group_fwd(const float* zq, int h, int w, const void* spx, int spx_dtype, const void* small, int small_dtype,
+                                  const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, int Ss, int flags, void* work,
+                                  size_t work_bytes, uint32_t* bits_eff, uint32_t* mult, uint32_t* any, uint64_t* acc, float* loss,
+                                  void* stream) {
+    if (!spx || !bits || !work) return MAS_ERR_NULL;
+    if (int e = check_hier(zq, small, small_dtype, mask, mult, any, acc, N, C, h, w, H, W, Ss)) return e;
+    if (S <= 0) return MAS_ERR_SHAPE;
+    if (flags & ~(MAS_HIER_ONLY_MULTI | MAS_HIER_NOCROPSP)) return MAS_ERR_RANGE;
+    if (!id_dtype_ok(spx_dtype)) return MAS_ERR_DTYPE;
+    const bool clear = (flags & MAS_HIER_NOCROPSP) != 0;
+    if (clear && !bits_eff) return MAS_ERR_NULL;
+    if (clear && (uintptr_t)bits_eff % 4 != 0) return MAS_ERR_ALIGN;
+    const size_t need = mas_online_plbl_work_bytes(N, S, C);
+    if (work_bytes < need) return MAS_ERR_WORKSPACE;
+    if ((uintptr_t)work % 8 != 0) return MAS_ERR_ALIGN;
+    const long long words = (long long)N * S * C;
+    if (words > 0x7fffffffLL * kThreads || (long long)N * Ss * C > 0x7fffffffLL) return MAS_ERR_SHAPE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t me = hipMemsetAsync(work, 0, need, st);
+    if (me == hipSuccess) me = hipMemsetAsync(mult, 0, (size_t)N * Ss * C * sizeof(uint32_t), st);
+    if (me == hipSuccess) me = hipMemsetAsync(any, 0, (size_t)N * Ss * sizeof(uint32_t), st);
+    if (me == hipSuccess) me = hipMemsetAsync(acc, 0, 2 * sizeof(uint64_t), st);
+    if (me == hipSuccess && clear) me = hipMemcpyAsync(bits_eff, bits, (size_t)N * S * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+    if (me != hipSuccess) return (int)me;
+    if (clear) {
+        const long long lanes = (long long)N * (2 * W + 2 * H);
+        hipLaunchKernelGGL(k_clear_boundary_bits, dim3((unsigned)((lanes + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, spx, spx_dtype, N,
+                           H, W, S, bits_eff);
+        if (int e = mas_launch_status()) return e;
+    }
+    uint64_t* scan_acc = static_cast<uint64_t*>(work);
+    if (int e = mas_partial_loss_fwd_lowres(zq, h, w, spx, spx_dtype, mask, clear ? bits_eff : bits, N, C, H, W, S, 1.0f,
+                                            MAS_LOSS_GROUP | ((flags & MAS_HIER_ONLY_MULTI) ? MAS_LOSS_GROUP_ONLY_MULTI : 0), scan_acc + 8,
+                                            scan_acc, stream))
+        return e;
+    hipLaunchKernelGGL(k_hier_pairs, dim3((unsigned)((words + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                       reinterpret_cast<const mas_u64*>(scan_acc + 8), small, small_dtype, words, S, C, H * W, Ss, mult, any);
+    if (int e = mas_launch_status()) return e;
+    if (int e = launch_ce(hier_ce(zq, h, w, small, small_dtype, mask, mult, any, C, H, W, Ss), N, nullptr, nullptr,
+                          reinterpret_cast<mas_u64*>(acc), st))
+        return e;
+    return loss ? mas_hier_group_value(acc, loss, stream) : 0;
+}
+
+extern "C" int mas_hier_group_bwd(const float* zq, int h, int w, const void* small, int small_dtype, const uint8_t* mask,
+                                  const uint32_t* mult, const uint32_t* any, const uint64_t* acc, const float* grad, int N, int C, int H,
+                                  int W, int Ss, int64_t* dzq_fix, float* dzq, void* stream) {
+    if (!grad || !dzq_fix) return MAS_ERR_NULL;
+    if (int e = check_hier(zq, small, small_dtype, mask, mult, any, acc, N, C, h, w, H, W, Ss)) return e;
+    return ce_backward(hier_ce(zq, h, w, small, small_dtype, mask, mult, any, C, H, W, Ss), N, acc, grad, dzq_fix, dzq, stream);
+}
+
+extern "C" int mas_hier_group_reference(const float* zq, int h, int w, const void* spx, int spx_dtype, const void* small, int small_dtype,
+                                        const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, int Ss, int flags,
+                                        const float* grad, uint64_t* gmax, uint32_t* bits_eff, uint32_t* mult, uint32_t* any, uint64_t* acc,
+                                        float* loss, int64_t* dzq_fix) {
+    if (!spx || !bits) return MAS_ERR_NULL;
+    if (int e = check_hier(zq, small, small_dtype, mask, mult, any, acc, N, C, h, w, H, W, Ss)) return e;
+    if (S <= 0) return MAS_ERR_SHAPE;
+    if (flags & ~(MAS_HIER_ONLY_MULTI | MAS_HIER_NOCROPSP)) return MAS_ERR_RANGE;
+    if (!id_dtype_ok(spx_dtype)) return MAS_ERR_DTYPE;
+    const bool clear = (flags & MAS_HIER_NOCROPSP) != 0;
+    if (clear && !bits_eff) return MAS_ERR_NULL;
+    if (dzq_fix && !grad) return MAS_ERR_NULL;
+    const size_t HW = (size_t)H * W;
+    if (clear) {
+        for (size_t i = 0; i < (size_t)N * S; ++i) bits_eff[i] = bits[i];
+        for (int n = 0; n < N; ++n) {
+            for (size_t pix = 0; pix < HW; ++pix) {
+                const int y = (int)(pix / W), x = (int)(pix % W);
+                if (y != 0 && y != H - 1 && x != 0 && x != W - 1) continue;
+                const long long id = (int)host_id(spx, spx_dtype, (size_t)n * HW + pix);
+                if (id >= 0 && id < S) bits_eff[(size_t)n * S + (size_t)id] = 0u;
+            }
+        }
+        bits = bits_eff;
+    }
+    uint64_t* table = gmax ? gmax : new uint64_t[(size_t)N * S * C];
+    host_table(zq, h, w, spx, spx_dtype, mask, bits, N, C, H, W, S, 1.0f, table, (flags & MAS_HIER_ONLY_MULTI) ? 2 : 1);
+    for (size_t i = 0; i < (size_t)N * Ss * C; ++i) mult[i] = 0;
+    for (size_t i = 0; i < (size_t)N * Ss; ++i) any[i] = 0;
+    for (size_t i = 0; i < (size_t)N * S * C; ++i) {
+        if ((table[i] >> 32) == 0) continue;
+        const uint32_t pp = mas_opl_word_pixel(table[i]);
+        if (pp >= (uint32_t)HW) continue;
+        const size_t n = i / ((size_t)S * C);
+        const int c = (int)(i % C);
+        const long long id = (int)host_id(small, small_dtype, n * HW + pp);
+        if (id < 0 || id >= Ss) continue;
+        mult[(n * Ss + (size_t)id) * C + c] += 1;
+        any[n * Ss + (size_t)id] |= 1u << c;
+    }
+    if (!gmax) delete[] table;
+    host_ce(HostHierCe{small, small_dtype, mask, mult, any, C, Ss}, zq, make_geo(C, 0, h, w, H, W, Ss), N, 1.0f, 0, grad, acc, loss, dzq_fix);
     return 0;
 }

@@ -20,9 +20,9 @@ class RegionCityscapesOr(RegionCityscapes):
                  region_dict=None, mask_region=True, dominant_labeling=False, loading='binary', load_smaller_spx=False, store=None):
         super().__init__(args, root, datalist, split, transform, return_spx, region_dict, mask_region, dominant_labeling, store=store)
         self.loading = loading
-        if load_smaller_spx:
-            raise NotImplementedError("--load_smaller_spx (a second, finer superpixel map per sample) is outside the hot path")
-        self.load_smaller_spx = False
+        self.load_smaller_spx = bool(load_smaller_spx)      # a second, finer id map per labelled sample (:76-80, :91-92)
+        if self.load_smaller_spx:
+            assert getattr(args, 'spx_method', 'seeds') == 'seeds'
         assert not (getattr(args, 'ignore_size', 0) != 0 and getattr(args, 'mark_topk', -1) != -1)
         mh_path, _ = self.multi_hot_files()
         self.multi_hot_cls = self.prepare_multi_hot(torch.from_numpy(np.load(mh_path)))      # (n_img, nseg, n_cls [+ 1])
@@ -50,17 +50,30 @@ class RegionCityscapesOr(RegionCityscapes):
             self._mh_dev = self.multi_hot_cls.to(device)            # 116 MB for Cityscapes: resident once
         return self._mh_dev[self.id_to_index[lbl_fname.split('/')[-1].split('.')[0]]]
 
+    def small_spx_fname(self, spx_fname):
+        """The finer map lies beside the superpixel map, under ``seeds_<small_nseg>`` (:78)."""
+        return spx_fname.replace("seeds_{}".format(self.args.nseg), "seeds_{}".format(self.args.small_nseg))
+
     def sample_files(self, index):
         img, _, spx = self.im_idx[index]
-        return [('rgb', img), ('ids', spx)]
+        files = [('rgb', img), ('ids', spx)]
+        if self.load_smaller_spx and self.split != 'active-ulabel':
+            files.append(('ids', self.small_spx_fname(spx)))
+        return files
 
     def __getitem__(self, index):
         assert self.mask_region
         img_fname, lbl_fname, spx_fname = self.im_idx[index]
         picture = self.store.picture(img_fname)
-        image, (superpixel,) = self.transform(picture, [self.store.idmap(spx_fname)])
+        small = self.load_smaller_spx and self.split != 'active-ulabel'
+        maps = [self.store.idmap(spx_fname)] + ([self.store.idmap(self.small_spx_fname(spx_fname))] if small else [])
+        image, maps = self.transform(picture, maps)
+        superpixel = maps[0]
         target = self.multi_hot_row(lbl_fname, image.device)
         if self.split == 'active-ulabel':                           # pool sample (:47-52,72-73)
             return {'images': image, 'spx': superpixel, 'labels': target}
-        return {'images': image, 'labels': target, 'spx': superpixel, 'spmask': self.selection_mask(spx_fname, superpixel),
-                'fnames': self.im_idx[index]}
+        sample = {'images': image, 'labels': target, 'spx': superpixel, 'spmask': self.selection_mask(spx_fname, superpixel),
+                  'fnames': self.im_idx[index]}
+        if small:
+            sample['spx_small'] = maps[1]
+        return sample

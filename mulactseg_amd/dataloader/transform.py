@@ -12,8 +12,11 @@ pins 9.2.0).  The geometry draws stay on Python's ``random``, the photometric dr
 the reference.  ``rescale_769_multi_notrg_ignore_strongv1`` is the reference's own name; the other ``_strongv1`` names apply the
 same stage to the other built crops.
 
-Not offered (outside the production configurations): the unpadded 512x1024 crops (``orig_*``, ``rescale``), ``load_smaller_spx``
-(a third map).  ``eval_spx_identity`` (VOC) keeps the picture and its two maps at their own size;
+``--load_smaller_spx`` (the finer superpixel map of the hierarchical group loss) is taken by ``rescale_769_multi_notrg`` alone, where
+it is the second of two maps [superpixel, small], padded with [nseg, small_nseg]; the names that would need a THIRD map
+(``rescale_769_multi``, ``..._ignore``) and every ``_strongv1`` name refuse it.
+
+Not offered (outside the production configurations): the unpadded 512x1024 crops (``orig_*``, ``rescale``).  ``eval_spx_identity`` (VOC) keeps the picture and its two maps at their own size;
 ``eval_spx_identity_ms`` (VOC) returns a LIST of ten pictures (five scales, then the same
 flipped) and takes no map (``n_maps == 0``)."""
 from .device_transforms import (DeviceIdentity, DeviceMultiScaleFlip, DeviceResize, DeviceResizeFlip, DeviceResizeThreeMaps, DeviceTrainAugment,
@@ -48,7 +51,8 @@ def get_train_transform(args, transform):
         _no_small(args, transform)
         return _with_maps(DeviceTrainAugment(pad_values=[args.ignore_idx, args.nseg], **crop), 2)
     if transform == 'rescale_769_multi_notrg':                      # [superpixel]: the stage-1 production transform
-        _no_small(args, transform)
+        if getattr(args, 'load_smaller_spx', False):                # [superpixel, small] (transform.py:96-110 of the reference)
+            return _with_maps(DeviceTrainAugment(pad_values=[args.nseg, args.small_nseg], **crop), 2)
         return _with_maps(DeviceTrainAugment(pad_values=[args.nseg], **crop), 1)
     if transform == 'rescale_769_multi_notrg_ignore':               # [label padded with 0, superpixel]
         _no_small(args, transform)

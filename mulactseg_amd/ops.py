@@ -453,6 +453,100 @@ def wgroup_loss_reference(z, zt, spx, mask, bits, invT, flags, grad_out=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# hierarchical group term: the group scan's arg-pixels spread over the fine superpixels around them (csrc/hier_group.h)
+# ------------------------------------------------------------------------------------------------
+HIER_ONLY_MULTI, HIER_NOCROPSP = _lib.HIER_ONLY_MULTI, _lib.HIER_NOCROPSP
+
+
+def _hier_shapes(z, size, spx, small, small_nseg, mask, bits, grad=None, host=False):
+    """``_loss_shapes`` plus the fine map: ``small`` ids [N,H,W] of a dtype the id loader knows, ``small_nseg`` > 0.  Full resolution
+    (``size`` None) is the same entry points with h = H and w = W, where the taps are exactly (1, 0)."""
+    mask, N, C, H, W, S, _ = _loss_shapes(z, None, size, spx, mask, bits, grad, host)
+    if host:
+        if small.is_cuda or not small.is_contiguous():
+            raise ValueError("superpixel_smalls must be a contiguous host tensor")
+    else:
+        _need(small, "superpixel_smalls")
+    if tuple(small.shape) != (N, H, W):
+        raise ValueError("superpixel_smalls %s do not match superpixels %s" % (tuple(small.shape), (N, H, W)))
+    if int(small_nseg) <= 0:
+        raise ValueError("small_nseg must be positive, got %r" % (small_nseg,))
+    return mask, N, C, H, W, S, int(small_nseg), z.shape[2], z.shape[3]
+
+
+def _hier_flags(only_single, nocropsp):
+    return (_lib.HIER_ONLY_MULTI if only_single else 0) | (_lib.HIER_NOCROPSP if nocropsp else 0)
+
+
+def hier_group_loss_fwd(z, size, spx, small, small_nseg, mask, bits, only_single=False, nocropsp=False, reduce_acc=None):
+    """Forward of the hierarchical group term in ONE library call: group scan at temperature 1, pair table, tile-queue sum.  ``z``
+    [N,C,H,W] with ``size`` None, or quarter-resolution [N,C,h,w] upsampled in-kernel to ``size``; ``bits`` int32 [N,S] over the class
+    columns.  Returns a dict: loss f32 [1] = sum / (1 + n); acc i64 [2] = (fixed-point sum, n); mult int32 [N,Ss,C] and any int32
+    [N,Ss], the pair table the backward reads; gmax i64 [N,S,C]; bits_eff int32 [N,S] (``nocropsp`` only, else None): ``bits`` with
+    the rows of the superpixels on the crop's outermost rows and columns cleared -- ``bits`` itself is not modified."""
+    mask, N, C, H, W, S, Ss, h, w = _hier_shapes(z, size, spx, small, small_nseg, mask, bits)
+    dev = z.device
+    work, gmax, _ = _loss_buffers(N, S, C, _lib.LOSS_GROUP, dev)          # the scan's eight words and its table, contiguous
+    tab = torch.empty(N * Ss * C + N * Ss + (N * S if nocropsp else 0), dtype=torch.int32, device=dev)
+    mult, any_ = tab[:N * Ss * C].view(N, Ss, C), tab[N * Ss * C:N * Ss * (C + 1)].view(N, Ss)
+    bits_eff = tab[N * Ss * (C + 1):].view(N, S) if nocropsp else None
+    acc = torch.empty(2, dtype=torch.int64, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        st = _stream(z)
+        _lib.check(lib.mas_hier_group_fwd(z.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), small.data_ptr(), _id_code(small), mask.data_ptr(),
+                                          bits.data_ptr(), N, C, H, W, S, Ss, _hier_flags(only_single, nocropsp), work.data_ptr(),
+                                          (work.numel() + gmax.numel()) * 8, _opt(bits_eff), mult.data_ptr(), any_.data_ptr(), acc.data_ptr(),
+                                          None if reduce_acc is not None else loss.data_ptr(), st), "mas_hier_group_fwd")
+        if reduce_acc is not None:
+            reduce_acc(acc)
+            _lib.check(lib.mas_hier_group_value(acc.data_ptr(), loss.data_ptr(), st), "mas_hier_group_value")
+    return dict(loss=loss, acc=acc, mult=mult, any=any_, gmax=gmax, bits_eff=bits_eff)
+
+
+def hier_group_loss_bwd(z, size, small, small_nseg, mask, mult, any_, acc, grad, want_fix=False):
+    """Backward of ``hier_group_loss_fwd``: the gradient with respect to ``z`` for the upstream gradient ``grad`` f32 [1], summed in
+    int64 fixed point (run-to-run identical bytes) and rounded to f32; ``want_fix`` returns (dz, the sums)."""
+    _need(z, "inputs", torch.float32)
+    _need(small, "superpixel_smalls")
+    _need(grad, "grad", torch.float32)
+    mask = _mask_u8(mask)
+    N, C, h, w = z.shape
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if tuple(small.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W) or tuple(mult.shape) != (N, int(small_nseg), C):
+        raise ValueError("shape mismatch between inputs %s, superpixel_smalls %s, spmasks %s and the pair table %s"
+                         % (tuple(z.shape), tuple(small.shape), tuple(mask.shape), tuple(mult.shape)))
+    fix = torch.empty(z.shape, dtype=torch.int64, device=z.device)               # (zeroed inside the call)
+    dz = torch.empty_like(z)
+    with torch.cuda.device(z.device):
+        _lib.check(_lib.load().mas_hier_group_bwd(z.data_ptr(), h, w, small.data_ptr(), _id_code(small), mask.data_ptr(), mult.data_ptr(),
+                                                  any_.data_ptr(), acc.data_ptr(), grad.data_ptr(), N, C, H, W, int(small_nseg),
+                                                  fix.data_ptr(), dz.data_ptr(), _stream(z)), "mas_hier_group_bwd")
+    return (dz, fix) if want_fix else dz
+
+
+def hier_group_loss_reference(z, size, spx, small, small_nseg, mask, bits, only_single=False, nocropsp=False, grad=None):
+    """``hier_group_loss_fwd`` / ``_bwd`` on HOST tensors: the library's plain loop through csrc/hier_group.h
+    (``mas_hier_group_reference``), the statement the kernels are held to bit for bit.  Needs no GPU.  Returns the forward's dict and,
+    with ``grad`` f32 [1], dzq_fix i64 (shaped as ``z``) and dz f32."""
+    mask, N, C, H, W, S, Ss, h, w = _hier_shapes(z, size, spx, small, small_nseg, mask, bits, grad, host=True)
+    gmax = torch.zeros((N, S, C), dtype=torch.int64)
+    mult, any_ = torch.zeros((N, Ss, C), dtype=torch.int32), torch.zeros((N, Ss), dtype=torch.int32)
+    bits_eff = torch.zeros((N, S), dtype=torch.int32) if nocropsp else None
+    acc, loss = torch.zeros(2, dtype=torch.int64), torch.zeros(1, dtype=torch.float32)
+    fix = torch.zeros(z.shape, dtype=torch.int64) if grad is not None else None
+    _lib.check(_lib.load().mas_hier_group_reference(z.data_ptr(), h, w, spx.data_ptr(), _id_code(spx), small.data_ptr(), _id_code(small),
+                                                    mask.data_ptr(), bits.data_ptr(), N, C, H, W, S, Ss, _hier_flags(only_single, nocropsp),
+                                                    _opt(grad), gmax.data_ptr(), _opt(bits_eff), mult.data_ptr(), any_.data_ptr(),
+                                                    acc.data_ptr(), loss.data_ptr(), _opt(fix)), "mas_hier_group_reference")
+    out = dict(loss=loss, acc=acc, mult=mult, any=any_, gmax=gmax, bits_eff=bits_eff)
+    if fix is not None:
+        out.update(dzq_fix=fix, dz=(fix.to(torch.float64) * 2.0 ** -_lib.GRAD_FRAC).to(torch.float32))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # online local-prototype pseudo labels and the cross entropy on them (csrc/online_plbl.hip)
 # ------------------------------------------------------------------------------------------------
 LCE_UNWEIGHTED, LCE_WEIGHTED, LCE_THRESHOLD, LCE_EMPTY_NAN = _lib.LCE_UNWEIGHTED, _lib.LCE_WEIGHTED, _lib.LCE_THRESHOLD, _lib.LCE_EMPTY_NAN

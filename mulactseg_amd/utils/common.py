@@ -101,8 +101,12 @@ def get_parser():
     a('--within_filtering', action='store_true', default=False,
       help="top1plbl: gate on the teacher's top candidate probability divided by its mass on the candidate set")
     a("--entcoeff", type=float, default=1.0, help="multient: weight of the candidate-entropy term")
-    # teacher-weighted group term (active_joint_multi_predignore_wgroup; refused for every other --method)
+    # teacher-weighted group term and hierarchical group term (active_joint_multi_predignore_wgroup, active_joint_hier_multi; refused for
+    # every other --method)
     a('--group_only_single', action='store_true', default=False, help="remove only single spx from group multi loss")
+    # hierarchical group term (active_joint_hier_multi; refused for every other --method)
+    a('--nocropsp', action='store_true', default=False, help="drop the labels of the superpixels on the crop's border")
+    a('--gumbel_scale', type=float, default=-1, help="-1 (off) only: the reference's Gumbel-max sampling cannot be reproduced")
     # active learning
     a("--seed", type=int, default=0)
     a("--start_over", action='store_true', default=False)
@@ -268,6 +272,9 @@ ENT_DEFAULTS = dict(entcoeff=1.0)
 # the teacher-weighted group term reads --group_only_single
 WGROUP_METHODS = ('active_joint_multi_predignore_wgroup',)
 WGROUP_DEFAULTS = dict(group_only_single=False)
+# the hierarchical group term reads --group_only_single, --nocropsp, --gumbel_scale (-1 only) and needs --load_smaller_spx
+HIER_METHODS = ('active_joint_hier_multi',)
+HIER_DEFAULTS = dict(nocropsp=False, gumbel_scale=-1)
 
 
 def _refuse_changed(args, defaults, honoured_by):
@@ -310,8 +317,16 @@ def arg_assert(args):
         _refuse_changed(args, TOP1_DEFAULTS, TEACHER_TERM_METHODS[:1])
     if args.method != TEACHER_TERM_METHODS[1]:
         _refuse_changed(args, ENT_DEFAULTS, TEACHER_TERM_METHODS[1:])
-    if args.method not in WGROUP_METHODS:
-        _refuse_changed(args, WGROUP_DEFAULTS, WGROUP_METHODS)
+    if args.method not in WGROUP_METHODS + HIER_METHODS:
+        _refuse_changed(args, WGROUP_DEFAULTS, WGROUP_METHODS + HIER_METHODS)
+    if args.method not in HIER_METHODS:
+        _refuse_changed(args, HIER_DEFAULTS, HIER_METHODS)
+    else:
+        if getattr(args, 'gumbel_scale', -1) != -1:     # (utils/loss.py:193-196 of the reference: torch-sampled noise before the arg-max)
+            raise NotImplementedError("--gumbel_scale %r: the reference's Gumbel-max sampling cannot be reproduced; only -1 (off) exists"
+                                      % (args.gumbel_scale,))
+        if not getattr(args, 'load_smaller_spx', False):
+            raise ValueError("--method active_joint_hier_multi reads the finer superpixel map: give --load_smaller_spx (and --small_nseg)")
     from ..ops import stage2_threshold_method       # NotImplementedError here; the reference raises it at the first picture
     stage2_threshold_method(getattr(args, 'cosprop_threshold_method', 'median'))            # (trainer/eval_save_cosplbl_prop.py:253)
 

@@ -42,6 +42,9 @@ class here                     reference definition
                                per-(superpixel, class) maximum; ``forward(inputs, plbl_preds, targets, superpixels, spmasks)``)
 ``FusedWGroupLoss``            (new) merged-positive CE and the weighted group term from ONE scan pair -- what the ``wgroup``
                                trainer uses
+``HierGroupMultiLabelCE``      ``utils/loss.py:143-235`` (the group term spread over the fine superpixel around every arg-pixel;
+                               ``forward(inputs, targets, spmasks, superpixels, superpixel_smalls)``; ``csrc/hier_group.h``)
+``AugHierGroupMultiLabelCE``   ``utils/loss.py:439-533`` (``--nocropsp``: rows of the superpixels on the crop's border cleared)
 =============================  =================================================================
 
 Inputs must be ROCm tensors; there is no CPU path (``_lib.MulActSegHipError`` otherwise).
@@ -729,3 +732,109 @@ class FusedWGroupLoss(nn.Module):
 
     def forward_lowres(self, zq, zq_teacher, size, targets, superpixels, spmasks):
         return self._run(zq, zq_teacher, size, targets, superpixels, spmasks)
+
+
+class _HierGroupFn(torch.autograd.Function):
+    """loss = f(z) of the hierarchical group term (``csrc/hier_group.h``): one library call forward (group scan, pair table, tile-queue
+    sum), one backward.  ``size`` None: full-resolution logits, else quarter-resolution ones upsampled inside the kernels.  The
+    arg-pixel choice and the pair table carry no gradient.  Returns (loss, acc i64 [2], the bits table both terms see)."""
+
+    @staticmethod
+    def forward(ctx, z, size, bits, superpixels, smalls, small_nseg, spmasks, only_single, nocropsp, sync):
+        z, spx, sml, msk = z.contiguous(), superpixels.contiguous(), smalls.contiguous(), spmasks.contiguous()
+        out = ops.hier_group_loss_fwd(z, size, spx, sml, small_nseg, msk, bits, only_single=only_single, nocropsp=nocropsp,
+                                      reduce_acc=_all_reduce_sum if sync else None)
+        ctx.save_for_backward(z, sml, msk, out['mult'], out['any'], out['acc'])
+        ctx.consts = (size, small_nseg)
+        bits_eff = out['bits_eff'] if nocropsp else bits.new_empty(0)          # (nothing cleared: the caller keeps its own table)
+        ctx.mark_non_differentiable(out['acc'], bits_eff)
+        return out['loss'][0], out['acc'], bits_eff
+
+    @staticmethod
+    def backward(ctx, g, _g_acc, _g_bits):
+        z, sml, msk, mult, any_, acc = ctx.saved_tensors
+        size, small_nseg = ctx.consts
+        dz = ops.hier_group_loss_bwd(z, size, sml, small_nseg, msk, mult, any_, acc, g.reshape(1).to(torch.float32).contiguous())
+        return (dz,) + (None,) * 9
+
+
+class HierGroupMultiLabelCE(nn.Module):
+    """Hierarchical group loss -- reference ``utils/loss.py:143-235``.  The group term decides one arg-pixel per (superpixel, class of
+    its target row, last column dropped); here that decision is spread over the whole FINE superpixel (``superpixel_smalls``, ids in
+    ``[0, args.small_nseg)``, pads carry ``small_nseg``) the arg-pixel lies in: ``sum_p sum_c M[small(p), c] * -log(p_c(p) + eps) /
+    (1 + sum_p sum_c M[small(p), c])`` over the selected pixels p, with ``M`` the number of arg-pixels of class c inside the fine
+    superpixel (pairs are not deduplicated: the reference gathers by index).
+
+    ``temperature`` is accepted and has NO effect: the reference's constructor hands ``temperature=1.0`` to its base class whatever
+    it is given (``:145``), so ``--group_ce_temp`` does not reach this term; the softmax runs at 1.0.  ``only_single``
+    (``--group_only_single``): only superpixels with more than one target bit choose arg-pixels.  ``gumbel_scale`` other than -1 adds
+    torch-sampled Gumbel noise before the arg-max in the reference and cannot be pinned: ``NotImplementedError``.
+    ``reduction='none'`` returns ``(sum, 1 + n)``.  Under torch.distributed the sum and the count are all-reduced before the division
+    (``sync_normalisers``, see ``_run``); the pair table is per picture and needs no exchange.  No host synchronisation; run-to-run
+    identical bytes.
+
+    After a call ``last_bits`` int32 [N,S] holds the target bits the term saw, and ``merged_positive`` evaluates the merged-positive CE
+    on them (the same as ``MultiChoiceCE`` for this class; see ``AugHierGroupMultiLabelCE``)."""
+    _nocropsp = False
+
+    def __init__(self, args, num_class, num_superpixel, only_single, gumbel_scale, reduction='mean', temperature=1.0):
+        super().__init__()
+        if gumbel_scale != -1:
+            raise NotImplementedError("gumbel_scale=%r: the reference samples torch Gumbel noise before the arg-max, which cannot be "
+                                      "reproduced; only -1 (off) exists" % (gumbel_scale,))
+        if reduction not in ('mean', 'none'):
+            raise NotImplementedError("reduction must be 'mean' or 'none', got %r" % (reduction,))
+        self.args = args
+        self.num_class = num_class
+        self.num_superpixel = num_superpixel
+        self.num_small_superpixel = int(args.small_nseg)
+        self.only_single = bool(only_single)
+        self.gumbel_scale = gumbel_scale
+        self.reduction = reduction
+        self.eps = 1e-8
+        self.temp = 1.0                 # (the reference's base-class call, whatever `temperature` says)
+        self.sync_normalisers = True
+        self.last_bits = None
+
+    def _run(self, z, size, targets, spmasks, superpixels, superpixel_smalls):
+        if targets.shape[1] != self.num_superpixel:
+            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        if targets.dtype != torch.uint8:
+            targets = targets.to(torch.uint8)
+        bits = ops.target_bits(targets.contiguous(), targets.shape[-1] - 1)
+        size = None if size is None else (int(size[0]), int(size[1]))
+        loss, self.last_acc, cleared = _HierGroupFn.apply(z, size, bits, superpixels, superpixel_smalls, self.num_small_superpixel, spmasks,
+                                                          self.only_single, self._nocropsp, self.sync_normalisers)
+        self.last_bits = cleared if self._nocropsp else bits
+        if self.reduction == 'mean':
+            return loss
+        num_valid = self.last_acc[1] + 1
+        return loss * num_valid.to(torch.float32), num_valid
+
+    def forward(self, inputs, targets, spmasks, superpixels, superpixel_smalls):
+        return self._run(inputs, None, targets, spmasks, superpixels, superpixel_smalls)
+
+    def forward_lowres(self, zq, size, targets, spmasks, superpixels, superpixel_smalls):
+        """``zq`` [N,C,h,w]: the quarter-resolution logits, interpolated in registers -- no ``[N,C,H,W]`` tensor exists."""
+        return self._run(zq, size, targets, spmasks, superpixels, superpixel_smalls)
+
+    def merged_positive(self, inputs, size, superpixels, spmasks, temperature):
+        """The merged-positive CE (``MultiChoiceCE``, last target column dropped) at ``temperature`` on ``last_bits``, the rows this
+        term saw in its last call."""
+        if self.last_bits is None:
+            raise RuntimeError("merged_positive reads the bits of the last forward; call the loss first")
+        size = None if size is None else (int(size[0]), int(size[1]))
+        ce, _, _, _ = _PartialLossFn.apply(inputs, size, self.last_bits, None, superpixels, spmasks, ops.inv_temperature(temperature),
+                                           _lib.LOSS_CE, self.sync_normalisers)
+        return ce
+
+
+class AugHierGroupMultiLabelCE(HierGroupMultiLabelCE):
+    """``HierGroupMultiLabelCE`` for ``--nocropsp`` -- reference ``utils/loss.py:439-533``: every superpixel id (other than ``nseg``)
+    that occurs on the outermost row or column of the crop has its target row cleared before the arg-pixels are chosen.
+
+    The reference clears the rows IN PLACE through a view of the trainer's ``labels`` (``:493-498``), and the trainer calls the
+    merged-positive loss afterwards on the same tensor: under ``--nocropsp`` the cleared rows are missing from BOTH terms.  That
+    effective objective is what is built here, without touching the caller's tensor: the rows are cleared in a copy of the bits table
+    on the device (``last_bits``), and ``merged_positive`` gives the second term on it."""
+    _nocropsp = True
