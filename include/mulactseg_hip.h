@@ -64,7 +64,8 @@ extern "C" {
  * mas_teacher_loss_fwd / _bwd / _values / _scales and mas_teacher_loss_reference with the MAS_LOSS_TOP1 / MAS_LOSS_ENT /
  * MAS_LOSS_WITHIN flag bits (the mas_partial_loss_* entry points answer MAS_ERR_RANGE to them), then mas_wgroup_loss_fwd / _bwd and
  * mas_wgroup_loss_reference with the MAS_LOSS_WGROUP flag bit (a library built before them answers MAS_ERR_RANGE to the bit), then
- * mas_hier_group_fwd / _value / _bwd and mas_hier_group_reference: new entry
+ * mas_hier_group_fwd / _value / _bwd and mas_hier_group_reference, then mas_async_hier_work_bytes / _tables / _fwd / _value / _bwd and
+ * mas_async_hier_reference, and mas_train_augment_maps: new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -434,6 +435,45 @@ int mas_hier_group_reference(const float* zq, int h, int w, const void* spx, int
                              const float* grad, uint64_t* gmax, uint32_t* bits_eff, uint32_t* mult, uint32_t* any, uint64_t* acc,
                              float* loss, int64_t* dzq_fix);
 
+/* ---------------------------------------------------------------------------------------------
+ * Cross-view hierarchical group term (utils/loss.py:341-437 AsyncHierGroupMultiLabelCE, :237-339 WeightAsyncHierGroupMultiLabelCE; the
+ * trainers active_joint_hier_multi_async and ..._async_weight).  Arithmetic: the second section of csrc/hier_group.h.  The pair table
+ * comes from a WEAK view of the picture (the eval-mode teacher's logits zq [N,C,h,w] upsampled to that view's own H x W, its ids, fine
+ * ids and mask); the sum runs over the STRONG view, whose fine ids name the same fine superpixels.  Tables and loss are separate calls,
+ * so a caller may hand in a table of its own.
+ *
+ * mas_async_hier_tables: memsets, the group scan at invT = 1 without the only-multi filter, k_hier_pairs, and for mode MAX / MEAN the
+ * teacher's weight of every existing pair: wgt f32 [N,Ss,C] (4-byte aligned; required then, MAS_ERR_NULL; ignored for NONE) = the
+ * maximum, or the fixed-point mean rounded once, of the teacher's p_c over the selected weak pixels of the fine superpixel; 0 where no
+ * pair exists.  Integer atomics only: mult, any and wgt are the same bytes on every run.  `work`: mas_async_hier_work_bytes(N, S, Ss, C,
+ * mode) bytes, 8-byte aligned; the table gmax u64 [N,S,C] starts at its ninth word.  Any other mode is MAS_ERR_RANGE.
+ * mas_async_hier_fwd / _bwd: mas_hier_group_fwd's last stage and mas_hier_group_bwd on given tables.  wgt NULL: the unweighted class,
+ * the same kernels as mas_hier_group_*.  With wgt, w_c = (float)mult * wgt and the count adds mult only where wgt != 0.
+ * mas_async_hier_reference: HOST pointers, the whole chain; writes gmax (may be NULL), mult, any, wgt (modes MAX / MEAN), acc [2], loss
+ * (may be NULL) and, for grad [1], dzq_fix (may be NULL).  With MAS_AHG_TABLES_GIVEN or-ed into mode the weak view is not read (its
+ * pointers may be NULL) and mult, any and wgt are inputs. */
+#define MAS_AHG_WEIGHT_NONE 0
+#define MAS_AHG_WEIGHT_MAX 1
+#define MAS_AHG_WEIGHT_MEAN 2
+#define MAS_AHG_TABLES_GIVEN 4
+size_t mas_async_hier_work_bytes(int N, int S, int Ss, int C, int mode);
+int mas_async_hier_tables(const float* zq, int h, int w, const void* spx, int spx_dtype, const void* small, int small_dtype,
+                          const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, int Ss, int mode, void* work,
+                          size_t work_bytes, uint32_t* mult /* [N,Ss,C] */, uint32_t* any /* [N,Ss] */, float* wgt /* [N,Ss,C] or NULL */,
+                          void* stream);
+int mas_async_hier_fwd(const float* zq, int h, int w, const void* small, int small_dtype, const uint8_t* mask, const uint32_t* mult,
+                       const uint32_t* any, const float* wgt /* or NULL */, int N, int C, int H, int W, int Ss, uint64_t* acc /* [2] */,
+                       float* loss /* [1] or NULL */, void* stream);
+int mas_async_hier_value(const uint64_t* acc, float* loss, void* stream);
+int mas_async_hier_bwd(const float* zq, int h, int w, const void* small, int small_dtype, const uint8_t* mask, const uint32_t* mult,
+                       const uint32_t* any, const float* wgt /* or NULL */, const uint64_t* acc, const float* grad /* [1] */, int N, int C,
+                       int H, int W, int Ss, int64_t* dzq_fix /* [N,C,h,w] */, float* dzq /* [N,C,h,w] or NULL */, void* stream);
+int mas_async_hier_reference(const float* zq_weak, int h_o, int w_o, const void* spx_weak, int spx_dtype, const void* small_weak,
+                             int small_weak_dtype, const uint8_t* mask_weak, const uint32_t* bits, int H_o, int W_o, int S, int mode,
+                             const float* zq, int h, int w, const void* small, int small_dtype, const uint8_t* mask, int N, int C, int H,
+                             int W, int Ss, const float* grad, uint64_t* gmax, uint32_t* mult, uint32_t* any, float* wgt, uint64_t* acc,
+                             float* loss, int64_t* dzq_fix);
+
 /* =============================================================================================
  * K4  ordering of the region scores and the budgeted selection walk
  * ============================================================================================= */
@@ -707,6 +747,12 @@ int mas_train_augment(const uint8_t* img, int H, int W, int th, int tw, const in
                       int gap_x, int crop_i, int crop_j, int flip, int out_h, int out_w, const float* mean, const float* std,
                       const uint8_t* fill, const void* map0, int map0_dtype, int64_t pad0, void* out_map0, int out0_u8,
                       const void* map1, int map1_dtype, int64_t pad1, void* out_map1, int out1_u8, float* out_img, void* stream);
+/* The maps alone, for a third (and fourth) map of a sample: the geometry arguments of mas_train_augment that the NEAREST resampling
+ * reads (no picture, no bilinear tables), up to two maps, the same draws and tables as the sample's main launch -- the picture is not
+ * resampled a second time.  At least one map (MAS_ERR_NULL). */
+int mas_train_augment_maps(int H, int W, int th, int tw, const int32_t* xidx, const int32_t* yidx, int gap_y, int gap_x, int crop_i,
+                           int crop_j, int flip, int out_h, int out_w, const void* map0, int map0_dtype, int64_t pad0, void* out_map0,
+                           int out0_u8, const void* map1, int map1_dtype, int64_t pad1, void* out_map1, int out1_u8, void* stream);
 
 /* Photometric augmentation of ONE sample (dataloader/transform.py:139-153 of the reference: ExtColorJitter + ExtRandomGrayscale after
  * crop and flip), for the samples that draw it; the arithmetic is csrc/photometric.h (Pillow's ImageEnhance / convert('HSV') /

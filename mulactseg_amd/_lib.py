@@ -22,6 +22,7 @@ ACC_WORDS = 8
 TEACHER_ACC_WORDS, ACC_SUM_X, ACC_N_X = 16, 8, 9
 LOSS_WGROUP = 1024      # the teacher-weighted group term of the mas_wgroup_loss_* entry points (csrc/teacher_terms.h, wgroup)
 HIER_ONLY_MULTI, HIER_NOCROPSP = 1, 2       # mas_hier_group_*: --group_only_single, --nocropsp (csrc/hier_group.h)
+AHG_WEIGHT_NONE, AHG_WEIGHT_MAX, AHG_WEIGHT_MEAN, AHG_TABLES_GIVEN = 0, 1, 2, 4      # mas_async_hier_*: --weight_reduce (csrc/hier_group.h)
 GRAD_FRAC = 44
 MS_MAX_SOURCES = 16
 
@@ -87,6 +88,7 @@ SIGNATURES = {
     "mas_aspp_dw3_bwd_w": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mas_train_augment": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp,
                                _vp, _i, _i64, _vp, _i, _vp, _i, _i64, _vp, _i, _vp, _vp]),
+    "mas_train_augment_maps": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp, _i, _vp, _i, _i64, _vp, _i, _vp]),
     "mas_train_augment_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp,
                                   _vp, _i, _i64, _vp, _i, _vp, _i, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "mas_photometric": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -200,6 +202,13 @@ SIGNATURES = {
     "mas_hier_group_bwd": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mas_hier_group_reference": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp]),
+    "mas_async_hier_work_bytes": (_c.c_size_t, [_i, _i, _i, _i, _i]),
+    "mas_async_hier_tables": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _c.c_size_t, _vp, _vp, _vp, _vp]),
+    "mas_async_hier_fwd": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mas_async_hier_value": (_i, [_vp, _vp, _vp]),
+    "mas_async_hier_bwd": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mas_async_hier_reference": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

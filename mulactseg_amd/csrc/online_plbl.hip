@@ -327,6 +327,39 @@ struct HierCe {
     }
 };
 
+// HierCe with the teacher's per-pair weight (hier_group.h, the cross-view forms): w_c = mult * wgt, a pair of weight 0 is not counted.
+struct WHierCe {
+    const float* zq; const void* small; const unsigned char* mask; const unsigned* mult; const unsigned* any; const float* wgt;
+    Geo g; int small_dtype; int tiles_x, tiles_y;
+    struct Px { unsigned Yc; const unsigned* m; const float* wg; float U; unsigned cnt; };
+
+    __device__ __forceinline__ bool runs(int) const { return true; }
+    __device__ __forceinline__ bool selects(size_t i, int) const {
+        if (!mask[i]) return false;
+        const int id = load_id_any(small, small_dtype, i);
+        if (id < 0 || id >= g.S) return false;
+        return any[(i / ((size_t)g.H * g.W)) * g.S + id] != 0u;
+    }
+    template <int CT, bool EXACT>
+    __device__ __forceinline__ bool pixel(int n, int py, int px, float (&v)[CT], OplTap& t, Px& s, float& term) const {
+        const int C = EXACT ? CT : g.C;
+        const size_t row = (size_t)n * g.S + load_id_any(small, small_dtype, ((size_t)n * g.H + py) * g.W + px);
+        s.Yc = C < 32 ? (any[row] & ((1u << C) - 1u)) : any[row];
+        s.m = mult + row * C;
+        s.wg = wgt + row * C;
+        ce_probs<CT, EXACT>(zq, g, 1.0f, n, py, px, v, t);
+        term = mas_ahg_term<CT>(v, C, s.Yc, s.m, s.wg, &s.U, &s.cnt);
+        return true;
+    }
+    __device__ __forceinline__ mas_u64 fix(float term) const { return mas_fix(term, MAS_LOSS_FRAC_BITS); }
+    __device__ __forceinline__ mas_u64 count(const Px& s) const { return s.cnt; }
+    __device__ __forceinline__ float scale(float grad, mas_u64 n) const { return mas_hg_scale(grad, n); }
+    __device__ __forceinline__ float k(const Px&, float scale) const { return scale; }
+    __device__ __forceinline__ float dir(const Px& s, int c, float pc) const {
+        return mas_hg_dir(pc, s.U, ((s.Yc >> c) & 1u) ? (float)s.m[c] * s.wg[c] : 0.0f);
+    }
+};
+
 template <int CT, bool EXACT, typename P>
 __device__ __forceinline__ void ce_fwd(const P& a, mas_u64* __restrict__ acc) {
     __shared__ int qcount[2];
@@ -467,6 +500,14 @@ template <int CT, bool EXACT> auto bwd_kernel(const SoftCe&) { return &k_soft_ce
 template <int CT, bool EXACT> auto fwd_kernel(const HierCe&) { return &k_hier_fwd<CT, EXACT>; }
 template <int CT, bool EXACT> auto bwd_kernel(const HierCe&) { return &k_hier_bwd<CT, EXACT>; }
 
+template <int CT, bool EXACT>
+__global__ __launch_bounds__(kThreads) void k_whier_fwd(const WHierCe a, mas_u64* __restrict__ acc) { ce_fwd<CT, EXACT>(a, acc); }
+template <int CT, bool EXACT>
+__global__ __launch_bounds__(kThreads) void k_whier_bwd(const WHierCe a, const mas_u64* __restrict__ acc, const float* __restrict__ grad,
+                                                         mas_u64* __restrict__ dq) { ce_bwd<CT, EXACT>(a, acc, grad, dq); }
+template <int CT, bool EXACT> auto fwd_kernel(const WHierCe&) { return &k_whier_fwd<CT, EXACT>; }
+template <int CT, bool EXACT> auto bwd_kernel(const WHierCe&) { return &k_whier_bwd<CT, EXACT>; }
+
 __global__ void k_label_ce_value(const mas_u64* __restrict__ acc, int flags, float* __restrict__ loss) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     loss[0] = mas_opl_value(acc[0], acc[1], flags);
@@ -511,6 +552,52 @@ __global__ __launch_bounds__(kThreads) void k_clear_boundary_bits(const void* __
 __global__ void k_hier_value(const mas_u64* __restrict__ acc, float* __restrict__ loss) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     loss[0] = mas_hg_value(acc[0], acc[1]);
+}
+
+// ---- the teacher's per-pair weight over the weak view (hier_group.h, the cross-view forms) --------------------------------------------
+// One lane per pixel of the weak view; g.S is the number of FINE superpixels.  Only a selected pixel whose fine superpixel holds a pair
+// computes a softmax, and only the classes of existing pairs are touched: the traffic is as sparse as the pair table.  Integer atomics
+// only -- an unsigned maximum of the bit patterns (p_c >= 0), or a u64 fixed-point sum beside a u32 pixel count per fine superpixel.
+template <int CT, bool EXACT, bool MEAN>
+__global__ __launch_bounds__(kThreads) void k_hier_weights(const float* __restrict__ zq, const void* __restrict__ small, int small_dtype,
+                                                            const unsigned char* __restrict__ mask, const unsigned* __restrict__ any,
+                                                            const Geo g, long long total, unsigned* __restrict__ wgt_bits,
+                                                            mas_u64* __restrict__ wsum, unsigned* __restrict__ wcnt) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    if (!mask[i]) return;
+    const int id = load_id_any(small, small_dtype, (size_t)i);
+    if (id < 0 || id >= g.S) return;
+    const int C = EXACT ? CT : g.C;
+    const int HW = g.H * g.W;
+    const int n = (int)(i / HW);
+    const int pix = (int)(i - (long long)n * HW);
+    const size_t row = (size_t)n * g.S + id;
+    const unsigned Yc = C < 32 ? (any[row] & ((1u << C) - 1u)) : any[row];
+    if (!Yc) return;
+    float v[CT];
+    OplTap t;
+    ce_probs<CT, EXACT>(zq, g, 1.0f, n, pix / g.W, pix % g.W, v, t);
+    if (MEAN) atomicAdd(&wcnt[row], 1u);
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+        if (c < C && ((Yc >> c) & 1u)) {
+            if (MEAN) atomicAdd(&wsum[row * C + c], (mas_u64)mas_ahg_fix(v[c]));
+            else atomicMax(&wgt_bits[row * C + c], mas_f2u(v[c]));
+        }
+    }
+}
+
+// One lane per word of the table [N,Ss,C]: the mean weight of an existing pair whose fine superpixel has selected weak pixels.
+__global__ __launch_bounds__(kThreads) void k_hier_weights_mean(const mas_u64* __restrict__ wsum, const unsigned* __restrict__ wcnt,
+                                                                 const unsigned* __restrict__ any, long long total, int C,
+                                                                 float* __restrict__ wgt) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= total) return;
+    const long long row = i / C;
+    const int c = (int)(i - row * C);
+    const unsigned cnt = wcnt[row];
+    if (cnt != 0u && ((any[row] >> c) & 1u)) wgt[i] = mas_ahg_mean(wsum[i], cnt);
 }
 
 // ---- dispatch -----------------------------------------------------------------------------------------------------------------------
@@ -1122,5 +1209,205 @@ extern "C" int mas_hier_group_reference(const float* zq, int h, int w, const voi
     }
     if (!gmax) delete[] table;
     host_ce(HostHierCe{small, small_dtype, mask, mult, any, C, Ss}, zq, make_geo(C, 0, h, w, H, W, Ss), N, 1.0f, 0, grad, acc, loss, dzq_fix);
+    return 0;
+}
+
+// ---- the cross-view forms (hier_group.h): tables from the weak view, the sum over the strong view ---------------------------------------
+namespace {
+struct HostWHierCe {
+    const void* small; int small_dtype; const uint8_t* mask; const uint32_t* mult; const uint32_t* any; const float* wgt; int C, Ss;
+    struct Px { uint32_t Yc; const uint32_t* m; const float* wg; float U; uint32_t cnt; };
+
+    bool takes(int n, size_t i) const {
+        if (!mask[i]) return false;
+        const long long id = (int)host_id(small, small_dtype, i);
+        return id >= 0 && id < Ss && any[(size_t)n * Ss + (size_t)id] != 0u;
+    }
+    bool pixel(int n, size_t i, const float (&p)[MAS_MAX_CLASSES], Px& s, float& term) const {
+        const size_t row = (size_t)n * Ss + (size_t)(int)host_id(small, small_dtype, i);
+        s.Yc = C < 32 ? (any[row] & ((1u << C) - 1u)) : any[row];
+        s.m = mult + row * C;
+        s.wg = wgt + row * C;
+        term = mas_ahg_term<MAS_MAX_CLASSES>(p, C, s.Yc, s.m, s.wg, &s.U, &s.cnt);
+        return true;
+    }
+    uint64_t fix(float term) const { return mas_fix(term, MAS_LOSS_FRAC_BITS); }
+    uint64_t count(const Px& s) const { return s.cnt; }
+    float scale(float grad, uint64_t n, float) const { return mas_hg_scale(grad, n); }
+    float value(uint64_t sum, uint64_t n, int) const { return mas_hg_value(sum, n); }
+    float k(const Px&, float scale) const { return scale; }
+    float dir(const Px& s, int c, float pc) const { return mas_hg_dir(pc, s.U, ((s.Yc >> c) & 1u) ? (float)s.m[c] * s.wg[c] : 0.0f); }
+};
+
+bool weight_mode_ok(int mode) { return mode == MAS_AHG_WEIGHT_NONE || mode == MAS_AHG_WEIGHT_MAX || mode == MAS_AHG_WEIGHT_MEAN; }
+
+int check_weight(const float* wgt) { return (wgt && (uintptr_t)wgt % 4 != 0) ? MAS_ERR_ALIGN : 0; }
+}  // namespace
+
+extern "C" size_t mas_async_hier_work_bytes(int N, int S, int Ss, int C, int mode) {
+    if (N <= 0 || S <= 0 || Ss <= 0 || C <= 0) return 0;
+    size_t words = 8 + (size_t)N * S * C;                                           // the scan's eight words and its table
+    if (mode == MAS_AHG_WEIGHT_MEAN) words += (size_t)N * Ss * C + ((size_t)N * Ss + 1) / 2;      // u64 sums, then u32 pixel counts
+    return words * sizeof(mas_u64);
+}
+
+extern "C" int mas_async_hier_tables(const float* zq, int h, int w, const void* spx, int spx_dtype, const void* small, int small_dtype,
+                                     const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, int Ss, int mode, void* work,
+                                     size_t work_bytes, uint32_t* mult, uint32_t* any, float* wgt, void* stream) {
+    if (!zq || !spx || !small || !mask || !bits || !work || !mult || !any) return MAS_ERR_NULL;
+    if (S <= 0 || Ss <= 0) return MAS_ERR_SHAPE;
+    if (int e = check_geometry(N, C, h, w, H, W)) return e;
+    if (!weight_mode_ok(mode)) return MAS_ERR_RANGE;
+    if (!id_dtype_ok(spx_dtype) || !id_dtype_ok(small_dtype)) return MAS_ERR_DTYPE;
+    if (mode != MAS_AHG_WEIGHT_NONE && !wgt) return MAS_ERR_NULL;
+    const size_t need = mas_async_hier_work_bytes(N, S, Ss, C, mode);
+    if (work_bytes < need) return MAS_ERR_WORKSPACE;
+    if ((uintptr_t)work % 8 != 0 || (uintptr_t)mult % 4 != 0 || (uintptr_t)any % 4 != 0) return MAS_ERR_ALIGN;
+    if (int e = check_weight(wgt)) return e;
+    const long long words = (long long)N * S * C, pairs = (long long)N * Ss * C;
+    if (words > 0x7fffffffLL * kThreads || pairs > 0x7fffffffLL) return MAS_ERR_SHAPE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t me = hipMemsetAsync(work, 0, need, st);
+    if (me == hipSuccess) me = hipMemsetAsync(mult, 0, (size_t)pairs * sizeof(uint32_t), st);
+    if (me == hipSuccess) me = hipMemsetAsync(any, 0, (size_t)N * Ss * sizeof(uint32_t), st);
+    if (me == hipSuccess && mode != MAS_AHG_WEIGHT_NONE) me = hipMemsetAsync(wgt, 0, (size_t)pairs * sizeof(float), st);
+    if (me != hipSuccess) return (int)me;
+    uint64_t* scan_acc = static_cast<uint64_t*>(work);
+    if (int e = mas_partial_loss_fwd_lowres(zq, h, w, spx, spx_dtype, mask, bits, N, C, H, W, S, 1.0f, MAS_LOSS_GROUP, scan_acc + 8, scan_acc,
+                                            stream))
+        return e;
+    hipLaunchKernelGGL(k_hier_pairs, dim3((unsigned)((words + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                       reinterpret_cast<const mas_u64*>(scan_acc + 8), small, small_dtype, words, S, C, H * W, Ss, mult, any);
+    if (int e = mas_launch_status()) return e;
+    if (mode == MAS_AHG_WEIGHT_NONE) return 0;
+    const bool mean = mode == MAS_AHG_WEIGHT_MEAN;
+    mas_u64* wsum = reinterpret_cast<mas_u64*>(scan_acc + 8 + words);
+    unsigned* wcnt = reinterpret_cast<unsigned*>(wsum + pairs);
+    const Geo g = make_geo(C, 0, h, w, H, W, Ss);
+    const long long total = (long long)N * H * W;
+    const dim3 grid((unsigned)((total + kThreads - 1) / kThreads));
+    if (int e = for_class_count(C, [&](auto ct, auto exact) {
+            constexpr int CT = decltype(ct)::value;
+            constexpr bool EXACT = decltype(exact)::value;
+            if (mean)
+                hipLaunchKernelGGL((k_hier_weights<CT, EXACT, true>), grid, dim3(kThreads), 0, st, zq, small, small_dtype, mask, any, g, total,
+                                   (unsigned*)nullptr, wsum, wcnt);
+            else
+                hipLaunchKernelGGL((k_hier_weights<CT, EXACT, false>), grid, dim3(kThreads), 0, st, zq, small, small_dtype, mask, any, g, total,
+                                   reinterpret_cast<unsigned*>(wgt), (mas_u64*)nullptr, (unsigned*)nullptr);
+            return mas_launch_status();
+        }))
+        return e;
+    if (!mean) return 0;
+    hipLaunchKernelGGL(k_hier_weights_mean, dim3((unsigned)((pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, wsum, wcnt, any, pairs, C,
+                       wgt);
+    return mas_launch_status();
+}
+
+extern "C" int mas_async_hier_value(const uint64_t* acc, float* loss, void* stream) { return mas_hier_group_value(acc, loss, stream); }
+
+extern "C" int mas_async_hier_fwd(const float* zq, int h, int w, const void* small, int small_dtype, const uint8_t* mask, const uint32_t* mult,
+                                  const uint32_t* any, const float* wgt, int N, int C, int H, int W, int Ss, uint64_t* acc, float* loss,
+                                  void* stream) {
+    if (int e = check_hier(zq, small, small_dtype, mask, mult, any, acc, N, C, h, w, H, W, Ss)) return e;
+    if (int e = check_weight(wgt)) return e;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const hipError_t me = hipMemsetAsync(acc, 0, 2 * sizeof(uint64_t), st);
+    if (me != hipSuccess) return (int)me;
+    const int e = wgt ? launch_ce(WHierCe{zq, small, mask, mult, any, wgt, make_geo(C, 0, h, w, H, W, Ss), small_dtype, 0, 0}, N, nullptr, nullptr,
+                                  reinterpret_cast<mas_u64*>(acc), st)
+                      : launch_ce(hier_ce(zq, h, w, small, small_dtype, mask, mult, any, C, H, W, Ss), N, nullptr, nullptr,
+                                  reinterpret_cast<mas_u64*>(acc), st);
+    if (e) return e;
+    return loss ? mas_hier_group_value(acc, loss, stream) : 0;
+}
+
+extern "C" int mas_async_hier_bwd(const float* zq, int h, int w, const void* small, int small_dtype, const uint8_t* mask, const uint32_t* mult,
+                                  const uint32_t* any, const float* wgt, const uint64_t* acc, const float* grad, int N, int C, int H, int W,
+                                  int Ss, int64_t* dzq_fix, float* dzq, void* stream) {
+    if (!grad || !dzq_fix) return MAS_ERR_NULL;
+    if (int e = check_hier(zq, small, small_dtype, mask, mult, any, acc, N, C, h, w, H, W, Ss)) return e;
+    if (int e = check_weight(wgt)) return e;
+    if (wgt)
+        return ce_backward(WHierCe{zq, small, mask, mult, any, wgt, make_geo(C, 0, h, w, H, W, Ss), small_dtype, 0, 0}, N, acc, grad, dzq_fix,
+                           dzq, stream);
+    return ce_backward(hier_ce(zq, h, w, small, small_dtype, mask, mult, any, C, H, W, Ss), N, acc, grad, dzq_fix, dzq, stream);
+}
+
+extern "C" int mas_async_hier_reference(const float* zq_weak, int h_o, int w_o, const void* spx_weak, int spx_dtype, const void* small_weak,
+                                        int small_weak_dtype, const uint8_t* mask_weak, const uint32_t* bits, int H_o, int W_o, int S, int mode,
+                                        const float* zq, int h, int w, const void* small, int small_dtype, const uint8_t* mask, int N, int C,
+                                        int H, int W, int Ss, const float* grad, uint64_t* gmax, uint32_t* mult, uint32_t* any, float* wgt,
+                                        uint64_t* acc, float* loss, int64_t* dzq_fix) {
+    const bool given = (mode & MAS_AHG_TABLES_GIVEN) != 0;
+    const int wmode = mode & ~MAS_AHG_TABLES_GIVEN;
+    if (!weight_mode_ok(wmode)) return MAS_ERR_RANGE;
+    if (int e = check_hier(zq, small, small_dtype, mask, mult, any, acc, N, C, h, w, H, W, Ss)) return e;
+    if (wmode != MAS_AHG_WEIGHT_NONE && !wgt) return MAS_ERR_NULL;
+    if (int e = check_weight(wgt)) return e;
+    if (dzq_fix && !grad) return MAS_ERR_NULL;
+    if (!given) {
+        if (!zq_weak || !spx_weak || !small_weak || !mask_weak || !bits) return MAS_ERR_NULL;
+        if (S <= 0) return MAS_ERR_SHAPE;
+        if (int e = check_geometry(N, C, h_o, w_o, H_o, W_o)) return e;
+        if (!id_dtype_ok(spx_dtype) || !id_dtype_ok(small_weak_dtype)) return MAS_ERR_DTYPE;
+        const size_t HWo = (size_t)H_o * W_o, hwo = (size_t)h_o * w_o, pairs = (size_t)N * Ss * C;
+        uint64_t* table = gmax ? gmax : new uint64_t[(size_t)N * S * C];
+        host_table(zq_weak, h_o, w_o, spx_weak, spx_dtype, mask_weak, bits, N, C, H_o, W_o, S, 1.0f, table, 1);
+        for (size_t i = 0; i < pairs; ++i) mult[i] = 0;
+        for (size_t i = 0; i < (size_t)N * Ss; ++i) any[i] = 0;
+        for (size_t i = 0; i < (size_t)N * S * C; ++i) {
+            if ((table[i] >> 32) == 0) continue;
+            const uint32_t pp = mas_opl_word_pixel(table[i]);
+            if (pp >= (uint32_t)HWo) continue;
+            const size_t n = i / ((size_t)S * C);
+            const int c = (int)(i % C);
+            const long long id = (int)host_id(small_weak, small_weak_dtype, n * HWo + pp);
+            if (id < 0 || id >= Ss) continue;
+            mult[(n * Ss + (size_t)id) * C + c] += 1;
+            any[n * Ss + (size_t)id] |= 1u << c;
+        }
+        if (!gmax) delete[] table;
+        if (wmode != MAS_AHG_WEIGHT_NONE) {
+            const bool mean = wmode == MAS_AHG_WEIGHT_MEAN;
+            uint64_t* wsum = new uint64_t[pairs]();
+            uint32_t* wcnt = new uint32_t[(size_t)N * Ss]();
+            uint32_t* wbits = reinterpret_cast<uint32_t*>(wgt);
+            for (size_t i = 0; i < pairs; ++i) wbits[i] = 0u;
+            const float sh = (float)h_o / (float)H_o, sw = (float)w_o / (float)W_o;
+            for (int n = 0; n < N; ++n) {
+                for (size_t pix = 0; pix < HWo; ++pix) {
+                    const size_t gi = (size_t)n * HWo + pix;
+                    if (!mask_weak[gi]) continue;
+                    const long long id = (int)host_id(small_weak, small_weak_dtype, gi);
+                    if (id < 0 || id >= Ss) continue;
+                    const size_t row = (size_t)n * Ss + (size_t)id;
+                    const uint32_t Yc = C < 32 ? (any[row] & ((1u << C) - 1u)) : any[row];
+                    if (!Yc) continue;
+                    const OplTap t = mas_opl_tap(sh, sw, (int)(pix / W_o), (int)(pix % W_o), h_o, w_o);
+                    float p[MAS_MAX_CLASSES];
+                    mas_opl_logits<MAS_MAX_CLASSES>(zq_weak + (size_t)n * C * hwo, hwo, t, C, p);
+                    mas_opl_softmax<MAS_MAX_CLASSES>(p, C, 1.0f);
+                    if (mean) wcnt[row] += 1;
+                    for (int c = 0; c < C; ++c) {
+                        if (!((Yc >> c) & 1u)) continue;
+                        if (mean) wsum[row * C + c] += mas_ahg_fix(p[c]);
+                        else if (mas_f2u(p[c]) > wbits[row * C + c]) wbits[row * C + c] = mas_f2u(p[c]);
+                    }
+                }
+            }
+            if (mean) {
+                for (size_t i = 0; i < pairs; ++i) {
+                    const size_t row = i / C;
+                    if (wcnt[row] != 0u && ((any[row] >> (i % C)) & 1u)) wgt[i] = mas_ahg_mean(wsum[i], wcnt[row]);
+                }
+            }
+            delete[] wsum;
+            delete[] wcnt;
+        }
+    }
+    const Geo g = make_geo(C, 0, h, w, H, W, Ss);
+    if (wmode != MAS_AHG_WEIGHT_NONE) host_ce(HostWHierCe{small, small_dtype, mask, mult, any, wgt, C, Ss}, zq, g, N, 1.0f, 0, grad, acc, loss, dzq_fix);
+    else host_ce(HostHierCe{small, small_dtype, mask, mult, any, C, Ss}, zq, g, N, 1.0f, 0, grad, acc, loss, dzq_fix);
     return 0;
 }

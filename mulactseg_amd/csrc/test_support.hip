@@ -2,6 +2,7 @@
 // load (tests/helpers.py:occupy_cus).  A CU-hogging neighbour kernel for the co-residency tests of the stream-K hand-off
 // (tests/test_stream_k_coresidency_gpu.py).
 #include "common.h"
+#include "hier_group.h"
 
 // Test-only neighbour kernel: workgroups that hold their CU resources (256 threads, `lds_bytes` of LDS) and wait on the wall
 // clock.  Every wave leaves once `ticks` (100 MHz) have passed since ITS OWN start: the grid always drains.
@@ -253,4 +254,15 @@ extern "C" int mas_test_occupy(int blocks, int lds_bytes, unsigned long long tic
     hipLaunchKernelGGL(k_test_occupy, dim3((unsigned)blocks), dim3(256), (size_t)lds_bytes, static_cast<hipStream_t>(stream), ticks,
                        static_cast<unsigned*>(nullptr));
     return mas_launch_status();
+}
+
+// Host side only: the mean weight's own fixed-point floor (hier_group.h: mas_ahg_fix) beside the general one, mas_fix(p,
+// MAS_AHG_WEIGHT_FRAC), for n floats -- tests/test_async_hier_cpu.py holds the two equal over the probabilities' range.
+extern "C" int mas_test_ahg_fix(const float* p, long long n, uint64_t* own, uint64_t* general) {
+    if (!p || !own || !general || n < 0) return MAS_ERR_NULL;
+    for (long long i = 0; i < n; ++i) {
+        own[i] = mas_ahg_fix(p[i]);
+        general[i] = mas_fix(p[i], MAS_AHG_WEIGHT_FRAC);
+    }
+    return 0;
 }

@@ -12,7 +12,7 @@ with ``register_dataset_factory``.
 import importlib
 
 from .region_active_dataset import RegionActiveDataset  # noqa: F401
-from .transform import get_train_transform, get_train_transform_voc, get_val_transform  # noqa: F401
+from .transform import get_async_train_transform, get_train_transform, get_train_transform_voc, get_val_transform  # noqa: F401
 from .utils import DataProvider, ResidentProvider, collate_fn  # noqa: F401
 
 
@@ -61,7 +61,12 @@ def get_active_dataset(args, train_transform=None):
         raise NotImplementedError("src_dataset %r (the reference's GTA5 / SYNTHIA choices have no region loader either)" % args.src_dataset)
     if getattr(args, 'active_mode', 'region') != 'region':
         raise NotImplementedError("active_mode %r" % args.active_mode)
-    lbl_transform = (get_train_transform_voc if voc else get_train_transform)(args, train_transform)
+    if args.loader.lower() == 'region_cityscapes_or_tensor_ignore_async':       # the one loader with three maps per sample
+        if voc or not getattr(args, 'or_labeling', False):
+            raise NotImplementedError("--loader region_cityscapes_or_tensor_ignore_async is a Cityscapes --or_labeling loader")
+        lbl_transform = get_async_train_transform(args, train_transform)
+    else:
+        lbl_transform = (get_train_transform_voc if voc else get_train_transform)(args, train_transform)
     pool_transform = get_val_transform('voc' if voc else 'cityscapes', ignore_idx=args.ignore_idx, nseg=args.nseg)
     loader = importlib.import_module("%s.%s" % (__name__, args.loader.lower()))
     from .picture_store import PictureStore

@@ -172,6 +172,49 @@ class DeviceTrainAugment:
         return out, outs
 
 
+class DeviceTrainAugmentThreeMaps(DeviceTrainAugment):
+    """``DeviceTrainAugment`` with THREE maps (``rescale_769_multi_notrg_ignore`` with ``--load_smaller_spx``, ``transform.py:115-125``
+    of the reference: precise label, superpixel ids, finer superpixel ids).  The main launch takes the picture and the first two maps;
+    the third map goes through the map-only entry (``mas_train_augment_maps``) with the draws and the NEAREST tables of that launch, so
+    the picture is resampled once.  The random draws are those of the two-map transform, in the same order.  With ``params`` given
+    (``DeviceResize.geometry``) it is the deterministic resize of the same three maps."""
+
+    def __init__(self, pad_values=(0, 2048, 8192), **kw):
+        pads = list(pad_values)
+        if len(pads) != 3:
+            raise ValueError("three maps, three pad values")
+        super().__init__(pad_values=pads[:2], **kw)
+        self.third_pad = pads[2]
+
+    @property
+    def all_pad_values(self):
+        return list(self.pad_values) + [self.third_pad]
+
+    def __call__(self, img, maps=(), params=None):
+        maps = list(maps)
+        if len(maps) != 3:
+            raise ValueError("the three-map augmentation takes exactly three maps, got %d" % len(maps))
+        third = maps[2]
+        H, W = int(img.shape[0]), int(img.shape[1])
+        if not (third.is_cuda and tuple(third.shape) == (H, W) and third.dtype in _MAP_CODES and third.is_contiguous()):
+            raise ValueError("maps must be contiguous [H,W] integer tensors on the picture's device")
+        p, geom, margs, outs, tab = self._prepare(img, maps[:2], params)
+        ch, cw = self.size
+        out = torch.empty((3, ch, cw), dtype=torch.float32, device=img.device)
+        u8 = self.keep_u8 and third.dtype == torch.uint8
+        o3 = torch.empty((ch, cw), dtype=torch.uint8 if u8 else torch.int64, device=img.device)
+        lib = _lib.load()
+        with torch.cuda.device(img.device):
+            st = torch.cuda.current_stream(img.device).cuda_stream
+            _lib.check(lib.mas_train_augment(*geom, self.mean.ctypes.data, self.std.ctypes.data, self.fill.ctypes.data, *margs,
+                                             out.data_ptr(), st), "mas_train_augment")
+            # geom: img, H, W, th, tw, hb, hk, hks, vb, vk, vks, xidx, yidx, gap_y, gap_x, i, j, flip, out_h, out_w
+            _lib.check(lib.mas_train_augment_maps(*geom[1:5], *geom[11:20], third.data_ptr(), _MAP_CODES[third.dtype], int(self.third_pad),
+                                                  o3.data_ptr(), int(u8), None, 0, 0, None, 0, st), "mas_train_augment_maps")
+        tab.record_stream(torch.cuda.current_stream(img.device))
+        return out, outs + [o3]
+
+
 def _jitter_range(value, center=1.0, clip_first_on_zero=True):
     """torchvision 0.12 ``ColorJitter._check_input`` for a number: ``[center - v, center + v]`` (the first clipped at 0);
     ``None`` when the range collapses to its centre (nothing is drawn then)."""

@@ -16,10 +16,6 @@ class RegionCityscapesOr(region_cityscapes_or_tensor.RegionCityscapesOr):
         assert self.mask_region
         self.remove_dominant = 'eval_save' not in args.method
 
-    def precise_label_file(self, lbl_fname):
-        stem = lbl_fname.split('/')[-1].split('.')[0]
-        return '{}/gtFine/train/{}/{}_gtFine_labelIds.png'.format(self.root, stem.split('_')[0], stem)
-
     def sample_files(self, index):
         img, lbl, spx = self.im_idx[index]
         return [('rgb', img), ('map', self.precise_label_file(lbl)), ('ids', spx)]

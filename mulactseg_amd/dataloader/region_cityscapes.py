@@ -79,6 +79,11 @@ class RegionCityscapes(torch.utils.data.Dataset):
             self._encode = torch.from_numpy(id_to_train_id_u8).to(raw.device)
         return self._encode[raw.long()].long()
 
+    def precise_label_file(self, lbl_fname):
+        """The picture's ``gtFine_labelIds`` file (raw label ids), from the stem of its label file."""
+        stem = lbl_fname.split('/')[-1].split('.')[0]
+        return '{}/gtFine/train/{}/{}_gtFine_labelIds.png'.format(self.root, stem.split('_')[0], stem)
+
     # -- selection mask ---------------------------------------------------------------------------
     def selection_lut(self, spx_fname, device):
         """bool [nseg + 1] of the ids this split holds for one picture (the pad id ``nseg`` is never set); rebuilt only when the list

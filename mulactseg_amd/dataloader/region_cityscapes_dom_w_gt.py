@@ -21,10 +21,6 @@ class RegionCityscapes(region_cityscapes.RegionCityscapes):
         assert self.dominant_labeling
         self.pred_ignore = pred_ignore_of(args)
 
-    def precise_label_file(self, lbl_fname):
-        stem = lbl_fname.split('/')[-1].split('.')[0]
-        return '{}/gtFine/train/{}/{}_gtFine_labelIds.png'.format(self.root, stem.split('_')[0], stem)
-
     def sample_files(self, index):
         img, lbl, spx = self.im_idx[index]
         return [('rgb', img), ('map', lbl), ('map', self.precise_label_file(lbl)), ('ids', spx)]

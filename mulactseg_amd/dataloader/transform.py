@@ -14,13 +14,15 @@ same stage to the other built crops.
 
 ``--load_smaller_spx`` (the finer superpixel map of the hierarchical group loss) is taken by ``rescale_769_multi_notrg`` alone, where
 it is the second of two maps [superpixel, small], padded with [nseg, small_nseg]; the names that would need a THIRD map
-(``rescale_769_multi``, ``..._ignore``) and every ``_strongv1`` name refuse it.
+(``rescale_769_multi``, ``..._ignore``) and every ``_strongv1`` name refuse it in ``get_train_transform``.  The one loader whose
+samples carry three maps, ``region_cityscapes_or_tensor_ignore_async``, gets ``rescale_769_multi_notrg_ignore`` with [label, superpixel,
+small] from ``get_async_train_transform`` (``get_active_dataset`` calls it for that loader).
 
 Not offered (outside the production configurations): the unpadded 512x1024 crops (``orig_*``, ``rescale``).  ``eval_spx_identity`` (VOC) keeps the picture and its two maps at their own size;
 ``eval_spx_identity_ms`` (VOC) returns a LIST of ten pictures (five scales, then the same
 flipped) and takes no map (``n_maps == 0``)."""
 from .device_transforms import (DeviceIdentity, DeviceMultiScaleFlip, DeviceResize, DeviceResizeFlip, DeviceResizeThreeMaps, DeviceTrainAugment,
-                                DeviceTrainAugmentStrong)
+                                DeviceTrainAugmentStrong, DeviceTrainAugmentThreeMaps)
 
 STRONG_V1 = dict(brightness=0.4, contrast=0.4, saturation=0.4, hue=0.1, p_jitter=0.2, p_gray=0.2)
 
@@ -33,6 +35,19 @@ def _with_maps(t, n):
 def _no_small(args, name):
     if getattr(args, 'load_smaller_spx', False):
         raise NotImplementedError("train_transform %r with --load_smaller_spx (a third map) is outside the hot path" % name)
+
+
+def get_async_train_transform(args, transform):
+    """The training transform of the loader ``region_cityscapes_or_tensor_ignore_async``: the reference's name
+    ``rescale_769_multi_notrg_ignore`` with ``--load_smaller_spx`` (``transform.py:115-125``), THREE maps [label padded with 0,
+    superpixel, small] through ``DeviceTrainAugmentThreeMaps``.  ``get_train_transform`` keeps refusing that combination for every
+    other loader, whose samples carry no third map."""
+    if transform != 'rescale_769_multi_notrg_ignore':
+        raise NotImplementedError("--loader region_cityscapes_or_tensor_ignore_async takes --train_transform rescale_769_multi_notrg_ignore "
+                                  "(three maps: label, superpixel, small), got %r" % (transform,))
+    if not getattr(args, 'load_smaller_spx', False):
+        raise NotImplementedError("--loader region_cityscapes_or_tensor_ignore_async needs --load_smaller_spx (and --small_nseg)")
+    return _with_maps(DeviceTrainAugmentThreeMaps(pad_values=[0, args.nseg, args.small_nseg], size=(768, 768), scale_range=(0.5, 2.0)), 3)
 
 
 def get_train_transform(args, transform):

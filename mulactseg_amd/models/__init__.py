@@ -28,6 +28,19 @@ def freeze_bn(model):
             m.eval()
 
 
+def keep_bn_frozen(net):
+    """``net.train(True)`` freezes the BatchNorm layers again from now on (``--freeze_bn``): ``log_validation()`` calls ``net.train()``
+    after each evaluation, which alone would put them back into training mode."""
+    _train = net.train
+
+    def train_keep_bn_frozen(mode=True):
+        out = _train(mode)
+        if mode:
+            freeze_bn(net)
+        return out
+    net.train = train_keep_bn_frozen
+
+
 def get_model(model, num_classes, output_stride, separable_conv, pretrained_backbone=True):
     """``pretrained_backbone=True`` reproduces the reference: the ImageNet deep-stem backbone is read from
     ``./checkpoint/resnet50_deepstem.pth`` (``backbone/resnet.py:306``; FileNotFoundError if absent)."""

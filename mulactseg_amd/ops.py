@@ -547,6 +547,140 @@ def hier_group_loss_reference(z, size, spx, small, small_nseg, mask, bits, only_
 
 
 # ------------------------------------------------------------------------------------------------
+# cross-view hierarchical group term: the pair table of a weak view, the sum over the strong view (csrc/hier_group.h, second section)
+# ------------------------------------------------------------------------------------------------
+_WEIGHT_MODES = {None: _lib.AHG_WEIGHT_NONE, 'max': _lib.AHG_WEIGHT_MAX, 'mean': _lib.AHG_WEIGHT_MEAN}
+
+
+def weight_reduce_mode(weight_reduce):
+    """``--weight_reduce`` as the library's mode: None (the unweighted class), 'max' or 'mean'."""
+    try:
+        return _WEIGHT_MODES[weight_reduce]
+    except (KeyError, TypeError):
+        raise ValueError("weight_reduce must be None, 'max' or 'mean', got %r" % (weight_reduce,))
+
+
+def async_hier_tables(zq_weak, size_weak, spx_weak, small_weak, small_nseg, mask_weak, bits, weight_reduce=None):
+    """The tables of the cross-view hierarchical group term from the WEAK view in ONE library call: the group scan at temperature 1 on
+    the teacher's logits ``zq_weak`` [N,C,h_o,w_o] upsampled in-kernel to ``size_weak`` (None: full-resolution logits), the pair table,
+    and with ``weight_reduce`` 'max' / 'mean' the teacher's per-pair weight.  Returns a dict: mult int32 [N,Ss,C], any int32 [N,Ss],
+    gmax i64 [N,S,C], wgt f32 [N,Ss,C] (None without ``weight_reduce``).  Run-to-run identical bytes."""
+    mode = weight_reduce_mode(weight_reduce)
+    mask_weak, N, C, H, W, S, Ss, h, w = _hier_shapes(zq_weak, size_weak, spx_weak, small_weak, small_nseg, mask_weak, bits)
+    dev = zq_weak.device
+    lib = _lib.load()
+    nbytes = lib.mas_async_hier_work_bytes(N, S, Ss, C, mode)
+    work = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)                  # (zeroed inside the call)
+    tab = torch.empty(N * Ss * C + N * Ss, dtype=torch.int32, device=dev)
+    mult, any_ = tab[:N * Ss * C].view(N, Ss, C), tab[N * Ss * C:].view(N, Ss)
+    wgt = torch.empty((N, Ss, C), dtype=torch.float32, device=dev) if mode else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.mas_async_hier_tables(zq_weak.data_ptr(), h, w, spx_weak.data_ptr(), _id_code(spx_weak), small_weak.data_ptr(),
+                                             _id_code(small_weak), mask_weak.data_ptr(), bits.data_ptr(), N, C, H, W, S, Ss, mode,
+                                             work.data_ptr(), nbytes, mult.data_ptr(), any_.data_ptr(), _opt(wgt), _stream(zq_weak)),
+                   "mas_async_hier_tables")
+    return dict(mult=mult, any=any_, gmax=work[8:8 + N * S * C].view(N, S, C), wgt=wgt)
+
+
+def _async_strong_shapes(z, size, small, small_nseg, mask, mult, any_, wgt, host=False):
+    N, C, h, w = z.shape
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    Ss = int(small_nseg)
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    for t, name, dt in ((z, "inputs", torch.float32), (small, "superpixel_smalls", None), (mask, "spmasks", torch.uint8),
+                        (mult, "mult", torch.int32), (any_, "any", torch.int32), (wgt, "wgt", torch.float32)):
+        if t is None:
+            continue
+        if host:
+            if t.is_cuda or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous host tensor" % name)
+            if dt is not None and t.dtype != dt:
+                raise TypeError("%s must be %s, got %s" % (name, dt, t.dtype))
+        else:
+            _need(t, name, dt)
+    if (Ss <= 0 or tuple(small.shape) != (N, H, W) or tuple(mask.shape) != (N, H, W) or tuple(mult.shape) != (N, Ss, C)
+            or tuple(any_.shape) != (N, Ss) or (wgt is not None and tuple(wgt.shape) != (N, Ss, C))):
+        raise ValueError("shape mismatch between inputs %s, superpixel_smalls %s, spmasks %s, the pair table %s / %s and its weights %s"
+                         % (tuple(z.shape), tuple(small.shape), tuple(mask.shape), tuple(mult.shape), tuple(any_.shape),
+                            None if wgt is None else tuple(wgt.shape)))
+    return mask, N, C, H, W, Ss, h, w
+
+
+def async_hier_loss_fwd(z, size, small, small_nseg, mask, mult, any_, wgt=None, reduce_acc=None):
+    """Forward of the cross-view term on GIVEN tables over the STRONG view: ``z`` [N,C,H,W] (``size`` None) or quarter-resolution
+    [N,C,h,w] upsampled in-kernel to ``size``.  ``wgt`` None is the unweighted class (the kernels of ``hier_group_loss_fwd``); with
+    ``wgt`` every pair's term is multiplied by its weight and a pair of weight 0 is not counted.  Returns (loss f32 [1], acc i64 [2])."""
+    mask, N, C, H, W, Ss, h, w = _async_strong_shapes(z, size, small, small_nseg, mask, mult, any_, wgt)
+    acc = torch.empty(2, dtype=torch.int64, device=z.device)
+    loss = torch.empty(1, dtype=torch.float32, device=z.device)
+    lib = _lib.load()
+    with torch.cuda.device(z.device):
+        st = _stream(z)
+        _lib.check(lib.mas_async_hier_fwd(z.data_ptr(), h, w, small.data_ptr(), _id_code(small), mask.data_ptr(), mult.data_ptr(),
+                                          any_.data_ptr(), _opt(wgt), N, C, H, W, Ss, acc.data_ptr(),
+                                          None if reduce_acc is not None else loss.data_ptr(), st), "mas_async_hier_fwd")
+        if reduce_acc is not None:
+            reduce_acc(acc)
+            _lib.check(lib.mas_async_hier_value(acc.data_ptr(), loss.data_ptr(), st), "mas_async_hier_value")
+    return loss, acc
+
+
+def async_hier_loss_bwd(z, size, small, small_nseg, mask, mult, any_, wgt, acc, grad, want_fix=False):
+    """Backward of ``async_hier_loss_fwd``: the gradient with respect to ``z`` for the upstream gradient ``grad`` f32 [1], summed in
+    int64 fixed point (run-to-run identical bytes) and rounded to f32; ``want_fix`` returns (dz, the sums)."""
+    mask, N, C, H, W, Ss, h, w = _async_strong_shapes(z, size, small, small_nseg, mask, mult, any_, wgt)
+    _need(grad, "grad", torch.float32)
+    fix = torch.empty(z.shape, dtype=torch.int64, device=z.device)               # (zeroed inside the call)
+    dz = torch.empty_like(z)
+    with torch.cuda.device(z.device):
+        _lib.check(_lib.load().mas_async_hier_bwd(z.data_ptr(), h, w, small.data_ptr(), _id_code(small), mask.data_ptr(), mult.data_ptr(),
+                                                  any_.data_ptr(), _opt(wgt), acc.data_ptr(), grad.data_ptr(), N, C, H, W, Ss,
+                                                  fix.data_ptr(), dz.data_ptr(), _stream(z)), "mas_async_hier_bwd")
+    return (dz, fix) if want_fix else dz
+
+
+def async_hier_loss_reference(z, size, small, small_nseg, mask, weak=None, tables=None, weight_reduce=None, grad=None):
+    """The cross-view term on HOST tensors: the library's plain loop through csrc/hier_group.h (``mas_async_hier_reference``), the
+    statement the kernels are held to bit for bit.  Needs no GPU.  ``weak`` = (zq_weak, size_weak, spx_weak, small_weak, mask_weak,
+    bits): the tables are built from that view (``weight_reduce`` None / 'max' / 'mean').  ``tables`` = (mult, any, wgt or None)
+    instead: they are used as given (``weight_reduce`` is ignored).  Returns a dict: loss, acc, mult, any, wgt, gmax (None with
+    ``tables``) and, with ``grad`` f32 [1], dzq_fix i64 (shaped as ``z``) and dz f32."""
+    if (weak is None) == (tables is None):
+        raise ValueError("give either the weak view or the tables")
+    Ss = int(small_nseg)
+    N, C = z.shape[:2]
+    gmax = None
+    if tables is not None:
+        mult, any_, wgt = tables
+        mode = _lib.AHG_TABLES_GIVEN | (_lib.AHG_WEIGHT_MAX if wgt is not None else 0)
+        head = (None, 0, 0, None, 0, None, 0, None, None, 0, 0, 0)
+    else:
+        zw, size_w, spx_w, small_w, mask_w, bits = weak
+        mask_w, Nw, Cw, Ho, Wo, S, _, ho, wo = _hier_shapes(zw, size_w, spx_w, small_w, Ss, mask_w, bits, host=True)
+        if (Nw, Cw) != (N, C):
+            raise ValueError("the weak view %s does not match the strong view %s" % (tuple(zw.shape), tuple(z.shape)))
+        mode = weight_reduce_mode(weight_reduce)
+        gmax = torch.zeros((N, S, C), dtype=torch.int64)
+        mult, any_ = torch.zeros((N, Ss, C), dtype=torch.int32), torch.zeros((N, Ss), dtype=torch.int32)
+        wgt = torch.zeros((N, Ss, C), dtype=torch.float32) if mode else None
+        head = (zw.data_ptr(), ho, wo, spx_w.data_ptr(), _id_code(spx_w), small_w.data_ptr(), _id_code(small_w), mask_w.data_ptr(),
+                bits.data_ptr(), Ho, Wo, S)
+    mask, N, C, H, W, Ss, h, w = _async_strong_shapes(z, size, small, Ss, mask, mult, any_, wgt, host=True)
+    if grad is not None and (grad.is_cuda or grad.dtype != torch.float32):
+        raise TypeError("grad must be a float32 host tensor")
+    acc, loss = torch.zeros(2, dtype=torch.int64), torch.zeros(1, dtype=torch.float32)
+    fix = torch.zeros(z.shape, dtype=torch.int64) if grad is not None else None
+    _lib.check(_lib.load().mas_async_hier_reference(*head, mode, z.data_ptr(), h, w, small.data_ptr(), _id_code(small), mask.data_ptr(), N, C,
+                                                    H, W, Ss, _opt(grad), _opt(gmax), mult.data_ptr(), any_.data_ptr(), _opt(wgt),
+                                                    acc.data_ptr(), loss.data_ptr(), _opt(fix)), "mas_async_hier_reference")
+    out = dict(loss=loss, acc=acc, mult=mult, any=any_, wgt=wgt, gmax=gmax)
+    if fix is not None:
+        out.update(dzq_fix=fix, dz=(fix.to(torch.float64) * 2.0 ** -_lib.GRAD_FRAC).to(torch.float32))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # online local-prototype pseudo labels and the cross entropy on them (csrc/online_plbl.hip)
 # ------------------------------------------------------------------------------------------------
 LCE_UNWEIGHTED, LCE_WEIGHTED, LCE_THRESHOLD, LCE_EMPTY_NAN = _lib.LCE_UNWEIGHTED, _lib.LCE_WEIGHTED, _lib.LCE_THRESHOLD, _lib.LCE_EMPTY_NAN

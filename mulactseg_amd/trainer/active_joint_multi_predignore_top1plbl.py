@@ -22,7 +22,7 @@ import contextlib
 
 import torch
 
-from ..models import freeze_bn
+from ..models import keep_bn_frozen
 from ..utils.loss import FusedTeacherTermLoss, GroupMultiLabelCE_, MultiChoiceCE_, TopOnePlbl
 from ..utils.scheduler import ramp_up
 from . import active_joint_multi_predignore
@@ -81,15 +81,8 @@ class TeacherTermTrainer(active_joint_multi_predignore.ActiveTrainer):
         return pos, group, self.term_module()(*args)
 
     def train_impl(self, total_itrs, val_period):
-        if getattr(self.args, 'freeze_bn', False) is True:         # (as trainer/active_voc.py: log_validation() calls net.train() again)
-            _train = self.net.train
-
-            def train_keep_bn_frozen(mode=True):
-                out = _train(mode)
-                if mode:
-                    freeze_bn(self.net)
-                return out
-            self.net.train = train_keep_bn_frozen
+        if getattr(self.args, 'freeze_bn', False) is True:         # (log_validation() calls net.train() again after each eval)
+            keep_bn_frozen(self.net)
         self.net.train()
         for iteration in range(total_itrs):
             images, labels, superpixels, spmasks = self._batch()

@@ -17,7 +17,7 @@ One deliberate difference, the same as ``active_joint_multi_predignore_top1plbl`
 teacher forward (:117), which un-freezes BatchNorm under ``--freeze_bn`` from the second iteration on.  Here every module goes back
 to the mode it had before the teacher forward, so a frozen BatchNorm stays frozen.
 """
-from ..models import freeze_bn
+from ..models import keep_bn_frozen
 from ..utils.loss import FusedWGroupLoss, MultiChoiceCE_, WeightedGroupMultiLabelCE
 from . import active_joint_multi_predignore
 from .active_joint_multi_predignore_top1plbl import eval_mode
@@ -47,15 +47,8 @@ class ActiveTrainer(active_joint_multi_predignore.ActiveTrainer):
         return pos, group
 
     def train_impl(self, total_itrs, val_period):
-        if getattr(self.args, 'freeze_bn', False) is True:         # (as trainer/active_voc.py: log_validation() calls net.train() again)
-            _train = self.net.train
-
-            def train_keep_bn_frozen(mode=True):
-                out = _train(mode)
-                if mode:
-                    freeze_bn(self.net)
-                return out
-            self.net.train = train_keep_bn_frozen
+        if getattr(self.args, 'freeze_bn', False) is True:         # (log_validation() calls net.train() again after each eval)
+            keep_bn_frozen(self.net)
         self.net.train()
         for iteration in range(total_itrs):
             images, labels, superpixels, spmasks = self._batch()

@@ -107,6 +107,9 @@ def get_parser():
     # hierarchical group term (active_joint_hier_multi; refused for every other --method)
     a('--nocropsp', action='store_true', default=False, help="drop the labels of the superpixels on the crop's border")
     a('--gumbel_scale', type=float, default=-1, help="-1 (off) only: the reference's Gumbel-max sampling cannot be reproduced")
+    # teacher-weighted cross-view hierarchical group term (active_joint_hier_multi_async_weight; refused for every other --method)
+    a('--weight_reduce', type=str, default='max', choices=['max', 'mean'],
+      help="how the teacher's class probability is reduced over a fine superpixel of the weak view")
     # active learning
     a("--seed", type=int, default=0)
     a("--start_over", action='store_true', default=False)
@@ -275,6 +278,10 @@ WGROUP_DEFAULTS = dict(group_only_single=False)
 # the hierarchical group term reads --group_only_single, --nocropsp, --gumbel_scale (-1 only) and needs --load_smaller_spx
 HIER_METHODS = ('active_joint_hier_multi',)
 HIER_DEFAULTS = dict(nocropsp=False, gumbel_scale=-1)
+# the cross-view hierarchical group terms need --load_smaller_spx; --gumbel_scale is -1 only; there is no --nocropsp class, and the
+# reference's two classes never read --group_only_single (refused, not ignored); the weighted one alone reads --weight_reduce
+ASYNC_HIER_METHODS = ('active_joint_hier_multi_async', 'active_joint_hier_multi_async_weight')
+ASYNC_WEIGHT_DEFAULTS = dict(weight_reduce='max')
 
 
 def _refuse_changed(args, defaults, honoured_by):
@@ -327,6 +334,10 @@ def arg_assert(args):
                                       % (args.gumbel_scale,))
         if not getattr(args, 'load_smaller_spx', False):
             raise ValueError("--method active_joint_hier_multi reads the finer superpixel map: give --load_smaller_spx (and --small_nseg)")
+    if args.method in ASYNC_HIER_METHODS and not getattr(args, 'load_smaller_spx', False):
+        raise ValueError("--method %s reads the finer superpixel map of both views: give --load_smaller_spx (and --small_nseg)" % args.method)
+    if args.method != ASYNC_HIER_METHODS[1]:
+        _refuse_changed(args, ASYNC_WEIGHT_DEFAULTS, ASYNC_HIER_METHODS[1:])
     from ..ops import stage2_threshold_method       # NotImplementedError here; the reference raises it at the first picture
     stage2_threshold_method(getattr(args, 'cosprop_threshold_method', 'median'))            # (trainer/eval_save_cosplbl_prop.py:253)
 

@@ -45,6 +45,8 @@ class here                     reference definition
 ``HierGroupMultiLabelCE``      ``utils/loss.py:143-235`` (the group term spread over the fine superpixel around every arg-pixel;
                                ``forward(inputs, targets, spmasks, superpixels, superpixel_smalls)``; ``csrc/hier_group.h``)
 ``AugHierGroupMultiLabelCE``   ``utils/loss.py:439-533`` (``--nocropsp``: rows of the superpixels on the crop's border cleared)
+``AsyncHierGroupMultiLabelCE`` ``utils/loss.py:341-437`` (the pair table from a weak view of the picture, the sum over the strong view)
+``WeightAsyncHierGroupMultiLabelCE``  ``utils/loss.py:237-339`` (the same, every pair weighted by the teacher's max / mean probability)
 =============================  =================================================================
 
 Inputs must be ROCm tensors; there is no CPU path (``_lib.MulActSegHipError`` otherwise).
@@ -838,3 +840,88 @@ class AugHierGroupMultiLabelCE(HierGroupMultiLabelCE):
     effective objective is what is built here, without touching the caller's tensor: the rows are cleared in a copy of the bits table
     on the device (``last_bits``), and ``merged_positive`` gives the second term on it."""
     _nocropsp = True
+
+
+class _AsyncHierFn(torch.autograd.Function):
+    """loss = f(z) of the cross-view hierarchical group term on given tables (``csrc/hier_group.h``, second section): the tile-queue sum
+    over the strong view forward, one backward.  The tables come from the teacher's view and carry no gradient.  Returns (loss, acc)."""
+
+    @staticmethod
+    def forward(ctx, z, size, smalls, small_nseg, spmasks, mult, any_, wgt, sync):
+        z, sml, msk = z.contiguous(), smalls.contiguous(), spmasks.contiguous()
+        loss, acc = ops.async_hier_loss_fwd(z, size, sml, small_nseg, msk, mult, any_, wgt, reduce_acc=_all_reduce_sum if sync else None)
+        saved = (z, sml, msk, mult, any_, acc) + (() if wgt is None else (wgt,))
+        ctx.save_for_backward(*saved)
+        ctx.consts = (size, small_nseg)
+        ctx.mark_non_differentiable(acc)
+        return loss[0], acc
+
+    @staticmethod
+    def backward(ctx, g, _g_acc):
+        z, sml, msk, mult, any_, acc = ctx.saved_tensors[:6]
+        wgt = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
+        size, small_nseg = ctx.consts
+        dz = ops.async_hier_loss_bwd(z, size, sml, small_nseg, msk, mult, any_, wgt, acc, g.reshape(1).to(torch.float32).contiguous())
+        return (dz,) + (None,) * 8
+
+
+class AsyncHierGroupMultiLabelCE(HierGroupMultiLabelCE):
+    """Cross-view hierarchical group loss -- reference ``utils/loss.py:341-437``.  Two views of one picture: on the WEAK view (the whole
+    picture, seen by an eval-mode teacher) every (superpixel, class of its target row, last column dropped) chooses its arg-pixel among
+    the pixels of ``spmasks_weak``, and the pair (fine superpixel of that pixel in ``spx_smalls_weak``, class) is kept; on the STRONG
+    view (the student's augmented crop) every selected pixel whose fine id in ``superpixel_smalls`` holds a pair pays ``M * -log(p_c +
+    eps)``, normalised by ``1 + sum M`` over those pixels.  The fine ids are the only link between the two geometries.
+
+    ``forward(inputs, inputs_weak, targets, spmasks, spmasks_weak, superpixels, superpixels_weak, superpixel_smalls, spx_smalls_weak)``
+    is the reference's signature on full-resolution logits of both views; ``forward_lowres`` takes quarter-resolution logits and the
+    two sizes.  ``superpixels`` (the strong view's coarse ids) is not read by this term, as in the reference.
+
+    ``temperature`` is accepted and has NO effect (the base constructor is handed 1.0 whatever it is given); ``only_single`` is stored
+    and NOT read, as in the reference's two classes -- the parser refuses ``--group_only_single`` for their trainers rather than ignore
+    it.  ``gumbel_scale`` other than -1: ``NotImplementedError``.  A pair whose summed value is exactly 0 over a non-empty fine
+    superpixel is counted here and not in the reference (``size[value.nonzero()]``)."""
+    _weight_reduce = None
+
+    def _tables(self, zw, size_weak, bits, spmasks_weak, superpixels_weak, spx_smalls_weak):
+        with torch.no_grad():
+            return ops.async_hier_tables(zw.detach().contiguous(), size_weak, superpixels_weak.contiguous(), spx_smalls_weak.contiguous(),
+                                         self.num_small_superpixel, spmasks_weak.contiguous(), bits, weight_reduce=self._weight_reduce)
+
+    def _run(self, z, size, zw, size_weak, targets, spmasks, spmasks_weak, superpixels_weak, superpixel_smalls, spx_smalls_weak):
+        if targets.shape[1] != self.num_superpixel:
+            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        if targets.dtype != torch.uint8:
+            targets = targets.to(torch.uint8)
+        bits = ops.target_bits(targets.contiguous(), targets.shape[-1] - 1)
+        size = None if size is None else (int(size[0]), int(size[1]))
+        size_weak = None if size_weak is None else (int(size_weak[0]), int(size_weak[1]))
+        self.last_tables = tab = self._tables(zw, size_weak, bits, spmasks_weak, superpixels_weak, spx_smalls_weak)
+        loss, self.last_acc = _AsyncHierFn.apply(z, size, superpixel_smalls, self.num_small_superpixel, spmasks, tab['mult'], tab['any'],
+                                                 tab['wgt'], self.sync_normalisers)
+        self.last_bits = bits
+        if self.reduction == 'mean':
+            return loss
+        num_valid = self.last_acc[1] + 1
+        return loss * num_valid.to(torch.float32), num_valid
+
+    def forward(self, inputs, inputs_weak, targets, spmasks, spmasks_weak, superpixels, superpixels_weak, superpixel_smalls, spx_smalls_weak):
+        return self._run(inputs, None, inputs_weak, None, targets, spmasks, spmasks_weak, superpixels_weak, superpixel_smalls, spx_smalls_weak)
+
+    def forward_lowres(self, zq, size, zq_weak, size_weak, targets, spmasks, spmasks_weak, superpixels, superpixels_weak, superpixel_smalls,
+                       spx_smalls_weak):
+        """``zq`` [N,C,h,w] and ``zq_weak`` [N,C,h_o,w_o]: the quarter-resolution logits of the two views, interpolated in registers to
+        ``size`` and ``size_weak`` -- no full-resolution tensor of either view exists."""
+        return self._run(zq, size, zq_weak, size_weak, targets, spmasks, spmasks_weak, superpixels_weak, superpixel_smalls, spx_smalls_weak)
+
+
+class WeightAsyncHierGroupMultiLabelCE(AsyncHierGroupMultiLabelCE):
+    """``AsyncHierGroupMultiLabelCE`` with the teacher's confidence -- reference ``utils/loss.py:237-339``: every pair's summed value is
+    multiplied by the detached ``weight_reduce`` ('max', the default, or 'mean') of the teacher's ``p_c`` over the selected weak-view
+    pixels of the pair's fine superpixel, and a pair of weight exactly 0 leaves the count.  The reference's mean is an f32 sum in source
+    order; here it is a fixed-point sum rounded once (``csrc/hier_group.h``)."""
+
+    def __init__(self, args, num_class, num_superpixel, only_single, gumbel_scale, reduction='mean', temperature=1.0, weight_reduce='max'):
+        super().__init__(args, num_class, num_superpixel, only_single, gumbel_scale, reduction, temperature)
+        if weight_reduce not in ('max', 'mean'):
+            raise ValueError("weight_reduce must be 'max' or 'mean', got %r" % (weight_reduce,))
+        self.weight_reduce = self._weight_reduce = weight_reduce
