@@ -3,6 +3,8 @@
 ``.classifier``, ``.forward``, ``.feat_forward``, ``.set_return_feat`` whose ``state_dict`` key names
 equal the reference's, so the authors' checkpoints load.  In scope: the production architecture
 ``deeplabv3pluswn_resnet50deepstem`` (and its ResNet-101 twin, same code)."""
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -39,6 +41,20 @@ def keep_bn_frozen(net):
             freeze_bn(net)
         return out
     net.train = train_keep_bn_frozen
+
+
+@contextlib.contextmanager
+def eval_mode(net):
+    """Eval mode under ``no_grad`` for a teacher / pseudo-label forward; on exit EVERY module has the mode it had
+    (``net.train(was_training)`` would put a frozen BatchNorm back into training mode)."""
+    modes = [(m, m.training) for m in net.modules()]
+    with torch.no_grad():
+        net.eval()
+        try:
+            yield net
+        finally:
+            for m, mode in modes:
+                m.training = mode
 
 
 def get_model(model, num_classes, output_stride, separable_conv, pretrained_backbone=True):

@@ -22,13 +22,13 @@ Skipping: the reference's ``check_loss_sanity`` (:21-27) skips the step on a zer
 uses ``active_joint_multi.ActiveTrainer.update`` like its siblings: a zero loss skips the optimizer step, a NaN loss RAISES -- the
 project's policy for every stage-1 trainer, kept as it is.
 """
-import torch
-
 from ..utils.loss import AugHierGroupMultiLabelCE, HierGroupMultiLabelCE, MultiChoiceCE
 from . import active_joint_multi
 
 
 class ActiveTrainer(active_joint_multi.ActiveTrainer):
+    batch_keys = ('images', 'labels', 'spx', 'spx_small', 'spmask')
+
     def get_criterion(self):
         a = self.args
         cls = AugHierGroupMultiLabelCE if getattr(a, 'nocropsp', False) else HierGroupMultiLabelCE
@@ -50,21 +50,3 @@ class ActiveTrainer(active_joint_multi.ActiveTrainer):
         # the bits the group term saw (rows cleared under --nocropsp): the reference's second term reads the tensor the first one modified
         pos = hier.merged_positive(preds, size, superpixels, spmasks, self.multi_pos_loss.temp)
         return pos, group
-
-    def train_impl(self, total_itrs, val_period):
-        self.net.train()
-        for iteration in range(total_itrs):
-            batch = next(self.train_dataset_loader)
-            images = batch['images'].to(self.device, dtype=torch.float32)
-            labels = batch['labels'].to(self.device, dtype=self.target_dtype)
-            superpixels, spmasks = batch['spx'].to(self.device), batch['spmask'].to(self.device)
-            superpixel_smalls = batch['spx_small'].to(self.device)
-            self.optimizer.zero_grad()
-            pos_loss, group_loss = self.step_losses(images, labels, superpixels, superpixel_smalls, spmasks)
-            loss = self.args.coeff * pos_loss + group_loss
-            self.update(loss)
-            self.update_average_meter({'train-loss': loss, 'pos-loss': pos_loss, 'group-loss': group_loss})
-            self.log_training(iteration, None, total_itrs)
-            self.log_validation(iteration, val_period)
-        self.flush_meters()
-        self.check_stream_k()

@@ -23,15 +23,13 @@ By default (``args.lowres_loss``) both forwards run at quarter resolution and th
 registers: no full-resolution tensor of either view exists.  With ``args.lowres_loss = False`` the same kernels run on full-resolution
 logits.
 """
-import torch
-
-from ..models import keep_bn_frozen
 from ..utils.loss import AsyncHierGroupMultiLabelCE, MultiChoiceCE
 from . import active_joint_hier_multi
-from .active_joint_multi_predignore_top1plbl import eval_mode
 
 
 class ActiveTrainer(active_joint_hier_multi.ActiveTrainer):
+    batch_keys = ('images', 'image_weak', 'labels', 'spx', 'spx_weak', 'spx_small', 'spx_small_weak', 'spmask', 'spmask_weak')
+
     def group_criterion(self):
         a = self.args
         return AsyncHierGroupMultiLabelCE(args=a, num_class=self.num_classes, num_superpixel=a.nseg,
@@ -41,10 +39,6 @@ class ActiveTrainer(active_joint_hier_multi.ActiveTrainer):
     def get_criterion(self):
         self.hier_group_multi_loss = self.group_criterion()
         self.multi_pos_loss = MultiChoiceCE(num_class=self.num_classes, temperature=self.args.multi_ce_temp)
-
-    def teacher_forward(self, images, lowres):
-        with eval_mode(self.net) as net:
-            return net(images, lowres=True).detach() if lowres else net(images).detach()
 
     def step_losses(self, images, images_weak, labels, superpixels, superpixels_weak, superpixel_smalls, spx_smalls_weak, spmasks, spmasks_weak):
         """(pos, group) of one batch."""
@@ -60,24 +54,3 @@ class ActiveTrainer(active_joint_hier_multi.ActiveTrainer):
             group = hier(preds, preds_weak, labels, spmasks, spmasks_weak, superpixels, superpixels_weak, superpixel_smalls, spx_smalls_weak)
         pos = hier.merged_positive(preds, size, superpixels, spmasks, self.multi_pos_loss.temp)
         return pos, group
-
-    def train_impl(self, total_itrs, val_period):
-        if getattr(self.args, 'freeze_bn', False) is True:         # (log_validation() calls net.train() again after each eval)
-            keep_bn_frozen(self.net)
-        self.net.train()
-        for iteration in range(total_itrs):
-            batch = next(self.train_dataset_loader)
-            images = batch['images'].to(self.device, dtype=torch.float32)
-            images_weak = batch['image_weak'].to(self.device, dtype=torch.float32)
-            labels = batch['labels'].to(self.device, dtype=self.target_dtype)
-            on = {k: batch[k].to(self.device) for k in ('spx', 'spx_weak', 'spx_small', 'spx_small_weak', 'spmask', 'spmask_weak')}
-            self.optimizer.zero_grad()
-            pos_loss, group_loss = self.step_losses(images, images_weak, labels, on['spx'], on['spx_weak'], on['spx_small'],
-                                                    on['spx_small_weak'], on['spmask'], on['spmask_weak'])
-            loss = self.args.coeff * pos_loss + group_loss
-            self.update(loss)
-            self.update_average_meter({'train-loss': loss, 'pos-loss': pos_loss, 'group-loss': group_loss})
-            self.log_training(iteration, None, total_itrs)
-            self.log_validation(iteration, val_period)
-        self.flush_meters()
-        self.check_stream_k()

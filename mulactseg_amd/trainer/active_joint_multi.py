@@ -3,6 +3,7 @@
 a NaN raises (``check_loss_sanity`` :23-29)."""
 import torch
 
+from ..models import eval_mode, keep_bn_frozen
 from ..utils.loss import GroupMultiLabelCE, MultiChoiceCE
 from . import active
 
@@ -130,24 +131,51 @@ class ActiveTrainer(active.ActiveTrainer):
             self.flush_meters()                 # the meters about to be popped include this step
         super().log_training(iteration, pbar, total_itrs)
 
+    batch_keys = ('images', 'labels', 'spx', 'spmask')        # what ``step`` receives of a batch, in this order
+
     def _batch(self):
         batch = next(self.train_dataset_loader)
-        images = batch['images'].to(self.device, dtype=torch.float32)
-        labels = batch['labels'].to(self.device, dtype=self.target_dtype)
-        return images, labels, batch['spx'].to(self.device), batch['spmask'].to(self.device)
+        dtypes = {'images': torch.float32, 'image_weak': torch.float32, 'labels': self.target_dtype}     # (the rest as loaded)
+        return tuple(batch[k].to(self.device, dtype=dtypes.get(k)) for k in self.batch_keys)
+
+    def teacher_forward(self, images, lowres):
+        """Logits of the eval-mode forward with the parameters of this step, under ``no_grad``; every module goes back to the mode
+        it had."""
+        with eval_mode(self.net) as net:
+            return net(images, lowres=True).detach() if lowres else net(images).detach()
+
+    def pseudo_label_forward(self, images, lowres):
+        """(features, logits) of the same eval-mode forward."""
+        with eval_mode(self.net) as net:
+            return net.feat_forward_quarter(images) if lowres else net.feat_forward(images)
+
+    def step_losses(self, images, labels, superpixels, spmasks):
+        """(pos, group) of one batch."""
+        preds = self.forward_train(images)
+        group = self.group_multi_loss(preds, labels, superpixels, spmasks)
+        pos = self.multi_pos_loss(preds, labels, superpixels, spmasks)
+        return pos, group
+
+    def step(self, iteration, total_itrs, *batch):
+        """(objective, meters after ``train-loss``) of one batch: what a joint stage-1 trainer overrides."""
+        pos_loss, group_loss = self.step_losses(*batch)
+        return self.args.coeff * pos_loss + group_loss, {'pos-loss': pos_loss, 'group-loss': group_loss}
 
     def train_impl(self, total_itrs, val_period):
+        """THE loop of every joint stage-1 trainer; a trainer says what its objective is in ``step`` (and which maps of the batch
+        that needs in ``batch_keys``).  ``args.freeze_bn`` (set programmatically, not a parser option) is honoured here for all of
+        them: the BatchNorm layers stay frozen across the eval-mode forwards and across ``log_validation()``, which calls
+        ``net.train()`` again after each evaluation."""
+        if getattr(self.args, 'freeze_bn', False) is True:
+            keep_bn_frozen(self.net)
         self.net.train()
         for iteration in range(total_itrs):
-            images, labels, superpixels, spmasks = self._batch()
+            batch = self._batch()
             self.optimizer.zero_grad()
-            preds = self.forward_train(images)
-            group_loss = self.group_multi_loss(preds, labels, superpixels, spmasks)
-            pos_loss = self.multi_pos_loss(preds, labels, superpixels, spmasks)
-            loss = self.args.coeff * pos_loss + group_loss
+            loss, meters = self.step(iteration, total_itrs, *batch)
             self.update(loss)
-            self.update_average_meter({'train-loss': loss, 'pos-loss': pos_loss, 'group-loss': group_loss})
+            self.update_average_meter({'train-loss': loss, **meters})
             self.log_training(iteration, None, total_itrs)
             self.log_validation(iteration, val_period)
-        self.flush_meters()
-        self.check_stream_k()
+        self.flush_meters()                 # the last step's meters
+        self.check_stream_k()               # a give-up in the last backward pass

@@ -10,4 +10,5 @@ class ActiveTrainer(active_joint_multi.ActiveTrainer):
     predicts_ignore = False
     get_criterion = _decomp.ActiveTrainer.get_criterion
     losses = _decomp.ActiveTrainer.losses
-    train_impl = _decomp.ActiveTrainer.train_impl
+    group_term = True
+    step = _decomp.ActiveTrainer.step

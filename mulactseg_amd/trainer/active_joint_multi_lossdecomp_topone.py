@@ -12,28 +12,9 @@ from . import active_joint_multi_lossdecomp
 
 class ActiveTrainer(active_joint_multi_lossdecomp.ActiveTrainer):
     multi_hot = 'topone'
+    group_term = False          # (the step is active_joint_multi_predignore_lossdecomp's, without its group term)
 
     def get_criterion(self):
         a = self.args
         self.multi_pos_loss = OnehotCEMultihotTopone(num_class=self.num_classes, temperature=a.multi_ce_temp)       # (drop-in surface)
         self.fused_loss = FusedPartialLabelLoss(a.nseg, a.multi_ce_temp, a.multi_ce_temp, decomp=True, multi_hot=self.multi_hot, group=False)
-
-    def train_impl(self, total_itrs, val_period):
-        a = self.args
-        self.net.train()
-        for iteration in range(total_itrs):
-            images, labels, superpixels, spmasks = self._batch()
-            self.optimizer.zero_grad()
-            if getattr(a, 'lowres_loss', True) and images.is_cuda:
-                preds_q = self.forward_train(images, lowres=True)
-                loss, _, ce_loss, mc_loss = self.fused_loss.weighted_lowres(preds_q, images.shape[-2:], labels, superpixels, spmasks,
-                                                                            a.coeff, a.coeff_mc, 0.0)
-            else:
-                _, ce_loss, mc_loss = self.fused_loss(self.forward_train(images), labels, superpixels, spmasks)
-                loss = (a.coeff * ce_loss) + (a.coeff_mc * mc_loss)
-            self.update(loss)
-            self.update_average_meter({'train-loss': loss, 'ce-loss': ce_loss, 'pos-loss': mc_loss})
-            self.log_training(iteration, None, total_itrs)
-            self.log_validation(iteration, val_period)
-        self.flush_meters()
-        self.check_stream_k()

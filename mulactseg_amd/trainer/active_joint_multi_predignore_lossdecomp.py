@@ -20,6 +20,8 @@ from . import active_joint_multi_predignore
 
 
 class ActiveTrainer(active_joint_multi_predignore.ActiveTrainer):
+    group_term = True               # False: no group term in the objective or among the meters (lossdecomp_rc, lossdecomp_topone)
+
     def get_criterion(self):
         a = self.args
         # the reference's two modules stay available under their names (drop-in surface) ...
@@ -27,7 +29,7 @@ class ActiveTrainer(active_joint_multi_predignore.ActiveTrainer):
         multi_hot = getattr(a, 'partial_loss', 'choice')
         decomp = {'choice': OnehotCEMultihotChoice, 'rc': OnehotCEMultihotRC, 'topone': OnehotCEMultihotTopone}[multi_hot]
         self.multi_pos_loss = decomp(num_class=self.num_classes, temperature=a.multi_ce_temp)
-        # ... and train_impl uses the fused scan when both temperatures agree (they do in every script)
+        # ... and step uses the fused scan when both temperatures agree (they do in every script)
         self.fused_loss = None
         if a.group_ce_temp == a.multi_ce_temp:
             self.fused_loss = FusedPartialLabelLoss(a.nseg, a.group_ce_temp, a.multi_ce_temp, only_multi=True, decomp=True, multi_hot=multi_hot)
@@ -39,24 +41,20 @@ class ActiveTrainer(active_joint_multi_predignore.ActiveTrainer):
         ce, mc = self.multi_pos_loss(preds, labels, superpixels, spmasks)
         return group, ce, mc
 
-    def train_impl(self, total_itrs, val_period):
+    def step(self, iteration, total_itrs, images, labels, superpixels, spmasks):
         a = self.args
-        self.net.train()
-        for iteration in range(total_itrs):
-            images, labels, superpixels, spmasks = self._batch()
-            self.optimizer.zero_grad()
-            if self.fused_loss is not None and getattr(a, 'lowres_loss', True) and images.is_cuda:
-                # quarter-resolution logits in, upsampling inside the loss scans (no [N,C,H,W] logit / gradient tensors)
-                preds_q = self.forward_train(images, lowres=True)
-                loss, group_loss, ce_loss, mc_loss = self.fused_loss.weighted_lowres(preds_q, images.shape[-2:], labels, superpixels, spmasks,
-                                                                                     a.coeff, a.coeff_mc, a.coeff_gm)
-            else:
-                preds = self.forward_train(images)
-                group_loss, ce_loss, mc_loss = self.losses(preds, labels, superpixels, spmasks)
-                loss = (a.coeff * ce_loss) + (a.coeff_mc * mc_loss) + (a.coeff_gm * group_loss)
-            self.update(loss)
-            self.update_average_meter({'train-loss': loss, 'ce-loss': ce_loss, 'pos-loss': mc_loss, 'group-loss': group_loss})
-            self.log_training(iteration, None, total_itrs)
-            self.log_validation(iteration, val_period)
-        self.flush_meters()
-        self.check_stream_k()
+        coeff_gm = a.coeff_gm if self.group_term else 0.0
+        if self.fused_loss is not None and getattr(a, 'lowres_loss', True) and images.is_cuda:
+            # quarter-resolution logits in, upsampling inside the loss scans (no [N,C,H,W] logit / gradient tensors)
+            preds_q = self.forward_train(images, lowres=True)
+            loss, group_loss, ce_loss, mc_loss = self.fused_loss.weighted_lowres(preds_q, images.shape[-2:], labels, superpixels, spmasks,
+                                                                                 a.coeff, a.coeff_mc, coeff_gm)
+        else:
+            group_loss, ce_loss, mc_loss = self.losses(self.forward_train(images), labels, superpixels, spmasks)
+            loss = (a.coeff * ce_loss) + (a.coeff_mc * mc_loss)
+            if self.group_term:
+                loss = loss + (coeff_gm * group_loss)
+        meters = {'ce-loss': ce_loss, 'pos-loss': mc_loss}
+        if self.group_term:
+            meters['group-loss'] = group_loss
+        return loss, meters

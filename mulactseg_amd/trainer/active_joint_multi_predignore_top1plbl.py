@@ -18,28 +18,9 @@ As in the reference the top-1 term is built with ``temperature=1.0`` whatever ``
 One deliberate difference: the reference calls ``net.train()`` after the teacher forward (:119), which un-freezes BatchNorm under
 ``--freeze_bn`` from the second iteration on.  Here every module goes back to the mode it had before the teacher forward.
 """
-import contextlib
-
-import torch
-
-from ..models import keep_bn_frozen
 from ..utils.loss import FusedTeacherTermLoss, GroupMultiLabelCE_, MultiChoiceCE_, TopOnePlbl
 from ..utils.scheduler import ramp_up
 from . import active_joint_multi_predignore
-
-
-@contextlib.contextmanager
-def eval_mode(net):
-    """Eval mode under ``no_grad`` for the teacher forward; on exit EVERY module has the mode it had (``net.train(was_training)``
-    would put a frozen BatchNorm back into training mode)."""
-    modes = [(m, m.training) for m in net.modules()]
-    with torch.no_grad():
-        net.eval()
-        try:
-            yield net
-        finally:
-            for m, mode in modes:
-                m.training = mode
 
 
 class TeacherTermTrainer(active_joint_multi_predignore.ActiveTrainer):
@@ -64,10 +45,6 @@ class TeacherTermTrainer(active_joint_multi_predignore.ActiveTrainer):
                                                within_filtering=getattr(a, 'within_filtering', False),
                                                filtering_threshold=getattr(a, 'plbl_th', 0.0))
 
-    def teacher_forward(self, images, lowres):
-        with eval_mode(self.net) as net:
-            return net(images, lowres=True).detach() if lowres else net(images).detach()
-
     def step_losses(self, images, labels, superpixels, spmasks):
         """(pos, group, term) of one batch."""
         lowres = getattr(self.args, 'lowres_loss', True) and images.is_cuda
@@ -80,21 +57,10 @@ class TeacherTermTrainer(active_joint_multi_predignore.ActiveTrainer):
         args = (preds, teacher, labels, superpixels, spmasks) if self.needs_teacher else (preds, labels, superpixels, spmasks)
         return pos, group, self.term_module()(*args)
 
-    def train_impl(self, total_itrs, val_period):
-        if getattr(self.args, 'freeze_bn', False) is True:         # (log_validation() calls net.train() again after each eval)
-            keep_bn_frozen(self.net)
-        self.net.train()
-        for iteration in range(total_itrs):
-            images, labels, superpixels, spmasks = self._batch()
-            self.optimizer.zero_grad()
-            pos_loss, group_loss, term_loss = self.step_losses(images, labels, superpixels, spmasks)
-            loss = self.args.coeff * pos_loss + group_loss + self.term_weight(iteration, total_itrs) * term_loss
-            self.update(loss)
-            self.update_average_meter({'train-loss': loss, 'pos-loss': pos_loss, 'group-loss': group_loss, self.term_meter: term_loss})
-            self.log_training(iteration, None, total_itrs)
-            self.log_validation(iteration, val_period)
-        self.flush_meters()
-        self.check_stream_k()
+    def step(self, iteration, total_itrs, *batch):
+        pos_loss, group_loss, term_loss = self.step_losses(*batch)
+        loss = self.args.coeff * pos_loss + group_loss + self.term_weight(iteration, total_itrs) * term_loss
+        return loss, {'pos-loss': pos_loss, 'group-loss': group_loss, self.term_meter: term_loss}
 
 
 class ActiveTrainer(TeacherTermTrainer):

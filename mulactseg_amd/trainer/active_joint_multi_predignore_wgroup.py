@@ -17,10 +17,8 @@ One deliberate difference, the same as ``active_joint_multi_predignore_top1plbl`
 teacher forward (:117), which un-freezes BatchNorm under ``--freeze_bn`` from the second iteration on.  Here every module goes back
 to the mode it had before the teacher forward, so a frozen BatchNorm stays frozen.
 """
-from ..models import keep_bn_frozen
 from ..utils.loss import FusedWGroupLoss, MultiChoiceCE_, WeightedGroupMultiLabelCE
 from . import active_joint_multi_predignore
-from .active_joint_multi_predignore_top1plbl import eval_mode
 
 
 class ActiveTrainer(active_joint_multi_predignore.ActiveTrainer):
@@ -30,10 +28,6 @@ class ActiveTrainer(active_joint_multi_predignore.ActiveTrainer):
                                                           temperature=a.group_ce_temp)
         self.multi_pos_loss = MultiChoiceCE_(num_class=self.num_classes, temperature=a.multi_ce_temp)
         self.fused_loss = FusedWGroupLoss(a.nseg, a.group_ce_temp, a.multi_ce_temp, group_only_single=getattr(a, 'group_only_single', False))
-
-    def teacher_forward(self, images, lowres):
-        with eval_mode(self.net) as net:
-            return net(images, lowres=True).detach() if lowres else net(images).detach()
 
     def step_losses(self, images, labels, superpixels, spmasks):
         """(pos, group) of one batch."""
@@ -45,19 +39,3 @@ class ActiveTrainer(active_joint_multi_predignore.ActiveTrainer):
         group = self.group_multi_loss(preds, teacher, labels, superpixels, spmasks)
         pos = self.multi_pos_loss(preds, labels, superpixels, spmasks)
         return pos, group
-
-    def train_impl(self, total_itrs, val_period):
-        if getattr(self.args, 'freeze_bn', False) is True:         # (log_validation() calls net.train() again after each eval)
-            keep_bn_frozen(self.net)
-        self.net.train()
-        for iteration in range(total_itrs):
-            images, labels, superpixels, spmasks = self._batch()
-            self.optimizer.zero_grad()
-            pos_loss, group_loss = self.step_losses(images, labels, superpixels, spmasks)
-            loss = self.args.coeff * pos_loss + group_loss
-            self.update(loss)
-            self.update_average_meter({'train-loss': loss, 'pos-loss': pos_loss, 'group-loss': group_loss})
-            self.log_training(iteration, None, total_itrs)
-            self.log_validation(iteration, val_period)
-        self.flush_meters()
-        self.check_stream_k()

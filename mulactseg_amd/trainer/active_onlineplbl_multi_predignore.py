@@ -12,11 +12,10 @@ By default (``args.lowres_loss``) the step runs at quarter resolution: ``forward
 any ``[N,C,H,W]`` logit tensor exists, and nothing between forward and backward waits for the host.
 
 One deliberate difference: the reference calls ``net.eval()`` inside the loop and never ``net.train()`` again, so from its second
-iteration on it trains with frozen BatchNorm statistics.  Here the pseudo-label forward runs in eval mode and the module's previous
-mode is restored after it: every step trains with batch statistics.  The loss classes themselves are exact.
+iteration on it trains with frozen BatchNorm statistics.  Here the pseudo-label forward runs in eval mode and every module's previous
+mode is restored after it (``active_joint_multi.ActiveTrainer.pseudo_label_forward``): every step trains with batch statistics, unless
+``args.freeze_bn`` froze them.  The loss classes themselves are exact.
 """
-import torch
-
 from ..utils.loss import FusedPartialLabelLoss, LocalProtoCE, MultiChoiceCE_
 from ..utils.scheduler import ramp_up
 from . import active_joint_multi_predignore
@@ -33,18 +32,6 @@ class ActiveTrainer(active_joint_multi_predignore.ActiveTrainer):
         self.multi_pos_loss = MultiChoiceCE_(num_class=self.num_classes, temperature=a.multi_ce_temp)       # (drop-in surface)
         # the same merged-positive CE from the quarter-resolution logits: the CE-only form of the fused scans
         self.pos_lowres = FusedPartialLabelLoss(a.nseg, a.multi_ce_temp, a.multi_ce_temp, decomp=False, group=False)
-
-    def pseudo_label_forward(self, images, lowres):
-        """(features, logits) of the eval-mode forward with the parameters of this step, under ``no_grad``; the module goes back to
-        the mode it was in (the reference leaves it in eval mode for the rest of the run)."""
-        net = self.net
-        was_training = net.training
-        with torch.no_grad():
-            net.eval()
-            try:
-                return net.feat_forward_quarter(images) if lowres else net.feat_forward(images)
-            finally:
-                net.train(was_training)
 
     def proto_weight(self, iteration, total_itrs):
         a = self.args
@@ -64,21 +51,9 @@ class ActiveTrainer(active_joint_multi_predignore.ActiveTrainer):
         pos = self.multi_pos_loss(preds, labels, superpixels, spmasks) if self.uses_pos_loss else None
         return pos, self.multi_local_proto_loss(preds_plbl, feats_plbl, preds, labels, superpixels, spmasks)
 
-    def train_impl(self, total_itrs, val_period):
-        self.net.train()
-        for iteration in range(total_itrs):
-            images, labels, superpixels, spmasks = self._batch()
-            self.optimizer.zero_grad()
-            pos_loss, proto_loss = self.step_losses(images, labels, superpixels, spmasks)
-            if self.uses_pos_loss:
-                loss = self.args.coeff * pos_loss + self.proto_weight(iteration, total_itrs) * proto_loss
-                meters = {'train-loss': loss, 'pos-loss': pos_loss, self.proto_meter: proto_loss}
-            else:
-                loss = proto_loss
-                meters = {'train-loss': loss}
-            self.update(loss)
-            self.update_average_meter(meters)
-            self.log_training(iteration, None, total_itrs)
-            self.log_validation(iteration, val_period)
-        self.flush_meters()
-        self.check_stream_k()
+    def step(self, iteration, total_itrs, *batch):
+        pos_loss, proto_loss = self.step_losses(*batch)
+        if not self.uses_pos_loss:
+            return proto_loss, {}
+        loss = self.args.coeff * pos_loss + self.proto_weight(iteration, total_itrs) * proto_loss
+        return loss, {'pos-loss': pos_loss, self.proto_meter: proto_loss}

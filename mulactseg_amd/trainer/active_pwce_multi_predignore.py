@@ -9,15 +9,13 @@ By default (``args.lowres_loss``) the step runs at quarter resolution, and the m
 both as in ``active_onlineplbl_multi_predignore``, whose documented difference from the reference (which never calls ``net.train()``
 again) this trainer shares."""
 from ..utils.loss import JointLocalProtoWeightingCE
-from . import active_joint_multi_predignore, active_onlineplbl_multi_predignore
+from . import active_joint_multi_predignore
 
 SIMW_SCHEDULE_ITERATIONS = 20000
 SIMW_SCHEDULE_TEMP = 1000.0
 
 
 class ActiveTrainer(active_joint_multi_predignore.ActiveTrainer):
-    pseudo_label_forward = active_onlineplbl_multi_predignore.ActiveTrainer.pseudo_label_forward
-
     def __init__(self, args, logger, selection_iter):
         super().__init__(args, logger, selection_iter)
         self.simw_temp_orig = args.simw_temp
@@ -42,15 +40,5 @@ class ActiveTrainer(active_joint_multi_predignore.ActiveTrainer):
         feats_plbl, preds_plbl = self.pseudo_label_forward(images, False)
         return crit(preds_plbl, feats_plbl, preds, labels, superpixels, spmasks, simw_temp=simw_temp)
 
-    def train_impl(self, total_itrs, val_period):
-        self.net.train()
-        for iteration in range(total_itrs):
-            images, labels, superpixels, spmasks = self._batch()
-            self.optimizer.zero_grad()
-            loss = self.step_loss(images, labels, superpixels, spmasks, self.simw_temp_at(iteration))
-            self.update(loss)
-            self.update_average_meter({'train-loss': loss})
-            self.log_training(iteration, None, total_itrs)
-            self.log_validation(iteration, val_period)
-        self.flush_meters()
-        self.check_stream_k()
+    def step(self, iteration, total_itrs, *batch):
+        return self.step_loss(*batch, self.simw_temp_at(iteration)), {}

@@ -57,6 +57,33 @@ import torch.nn as nn
 from .. import _lib, ops
 
 
+def _check_superpixels(targets, num_superpixel):
+    if targets.shape[1] != num_superpixel:
+        raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], num_superpixel))
+
+
+def _u8(targets):
+    """The multi-hot targets as the kernels read them: contiguous u8."""
+    return (targets if targets.dtype == torch.uint8 else targets.to(torch.uint8)).contiguous()
+
+
+def _hw(size):
+    """``size`` of the ``forward_lowres`` forms as a plain (H, W); None (full-resolution logits) stays None."""
+    return None if size is None else (int(size[0]), int(size[1]))
+
+
+def _shared_temperature(group_temperature, multi_temperature):
+    if group_temperature != multi_temperature:
+        raise ValueError("the fused scan shares one softmax: group_ce_temp must equal multi_ce_temp "
+                         "(both 0.1 in the reference scripts)")
+    return multi_temperature
+
+
+def _mean_only(reduction, why="only reduction='mean' is on the hot path"):
+    if reduction != 'mean':
+        raise NotImplementedError(why)
+
+
 def _fused_forward(ctx, z, size, tgt, cols_used, superpixels, spmasks, invT, flags, sync, weights):
     """Shared forward of the three autograd functions below: ONE library call (prep + scan + finalize with the loss values,
     ops.partial_loss_fwd_fused); ``tgt`` is the u8 multi-hot target tensor (``cols_used`` columns count) or, with ``cols_used``
@@ -94,7 +121,7 @@ class _PartialLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inputs, size, tgt, cols_used, superpixels, spmasks, invT, flags, sync):
-        size = None if size is None else (int(size[0]), int(size[1]))
+        size = _hw(size)
         losses, acc = _fused_forward(ctx, inputs, size, tgt, cols_used, superpixels, spmasks, invT, flags, sync, None)
         return losses[0], losses[1], losses[2], acc
 
@@ -144,10 +171,8 @@ def _run(inputs, targets, superpixels, spmasks, temp, flags, drop_last_column, s
     its peers wait in the gradient all-reduce.
 
     ``size`` = (H, W): ``inputs`` are the quarter-resolution logits (``_PartialLossFn``)."""
-    if targets.dtype != torch.uint8:
-        targets = targets.to(torch.uint8)
     cols = targets.shape[-1]
-    return _PartialLossFn.apply(inputs, size, targets.contiguous(), cols - 1 if drop_last_column else cols, superpixels, spmasks,
+    return _PartialLossFn.apply(inputs, size, _u8(targets), cols - 1 if drop_last_column else cols, superpixels, spmasks,
                                 ops.inv_temperature(temp), flags, sync)
 
 
@@ -207,8 +232,7 @@ class MultiChoiceCE(nn.Module):
 
     def __init__(self, num_class, temperature=1.0, reduction='mean'):
         super().__init__()
-        if reduction != 'mean':
-            raise NotImplementedError("only reduction='mean' is on the hot path")
+        _mean_only(reduction)
         self.num_class = num_class
         self.reduction = reduction
         self.eps = 1e-8
@@ -265,8 +289,7 @@ class GroupMultiLabelCE(nn.Module):
 
     def __init__(self, args, num_class, num_superpixel, temperature=1.0, reduction='mean'):
         super().__init__()
-        if reduction != 'mean':
-            raise NotImplementedError("only reduction='mean' is on the hot path")
+        _mean_only(reduction)
         self.args = args
         self.num_class = num_class
         self.num_superpixel = num_superpixel
@@ -275,8 +298,7 @@ class GroupMultiLabelCE(nn.Module):
         self.reduction = reduction
 
     def forward(self, inputs, targets, superpixels, spmasks):
-        if targets.shape[1] != self.num_superpixel:
-            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        _check_superpixels(targets, self.num_superpixel)
         _, _, group, _ = _run(inputs, targets, superpixels, spmasks, self.temp, self._flags, self._drop_last)
         return group
 
@@ -297,8 +319,7 @@ class JointMultiLoss(nn.Module):
 
     def __init__(self, group_multi_loss, multi_pos_loss, reduction='mean'):
         super().__init__()
-        if reduction != 'mean':
-            raise NotImplementedError("the reference's 'none' branch is broken (wrong arity, utils/loss.py:57-61)")
+        _mean_only(reduction, "the reference's 'none' branch is broken (wrong arity, utils/loss.py:57-61)")
         self.group_multi_loss = group_multi_loss
         self.multi_pos_loss = multi_pos_loss
         self.reduction = reduction
@@ -328,11 +349,8 @@ class FusedPartialLabelLoss(nn.Module):
         # single-GPU objective over the global batch; multiply the loss by world_size before backward()
         # when gradients are then AVERAGED over ranks (DistributedDataParallel does).
         self.sync_normalisers = sync_normalisers
-        if group_temperature != multi_temperature:
-            raise ValueError("the fused scan shares one softmax: group_ce_temp must equal multi_ce_temp "
-                             "(both 0.1 in the reference scripts)")
         self.num_superpixel = num_superpixel
-        self.temp = multi_temperature
+        self.temp = _shared_temperature(group_temperature, multi_temperature)
         self.flags = _lib.LOSS_CE | ((_lib.LOSS_GROUP | (_lib.LOSS_GROUP_ONLY_MULTI if only_multi else 0)) if group else 0) \
             | (_lib.LOSS_DECOMP if decomp else 0) | MULTI_HOT_FLAGS[multi_hot]
 
@@ -352,12 +370,10 @@ class FusedPartialLabelLoss(nn.Module):
         """``(coeff * ce + coeff_mc * mc) + coeff_gm * group`` (``..._lossdecomp.py:104``) as one differentiable scalar, plus the
         detached parts ``(group, ce, mc)`` for logging -- same value, bit for bit, as composing ``forward_lowres`` with torch
         arithmetic, in half the kernel launches."""
-        if targets.dtype != torch.uint8:
-            targets = targets.to(torch.uint8)
         key = (float(coeff), float(coeff_mc), float(coeff_gm), quarter_logits.device)
         if getattr(self, '_w_key', None) != key:
             self._w_key, self._w = key, torch.tensor(key[:3], dtype=torch.float32, device=quarter_logits.device)
-        total, parts, self.last_acc = _WeightedLowResLossFn.apply(quarter_logits, tuple(size), targets.contiguous(), targets.shape[-1], superpixels, spmasks,
+        total, parts, self.last_acc = _WeightedLowResLossFn.apply(quarter_logits, tuple(size), _u8(targets), targets.shape[-1], superpixels, spmasks,
                                                                   ops.inv_temperature(self.temp), self.flags, self.sync_normalisers, self._w)
         return total, parts[2], parts[0], parts[1]
 
@@ -381,8 +397,7 @@ class LocalProtoCE(nn.Module):
 
     def __init__(self, args, num_superpixel, temperature=1.0, reduction='mean'):
         super().__init__()
-        if reduction != 'mean':
-            raise NotImplementedError("only reduction='mean' exists (the reference asserts it)")
+        _mean_only(reduction, "only reduction='mean' exists (the reference asserts it)")
         self.args = args
         self.num_superpixel = num_superpixel
         self.temp = temperature
@@ -394,8 +409,7 @@ class LocalProtoCE(nn.Module):
         """(weight f32 [N,H,W], nn_plbl u8 [N,H,W]) as the reference's ``generate_plbl`` returns them (255 = no label, weight 0).
         ``size`` None: the tensors are at the resolution of ``superpixels``; else they are quarter-resolution maps upsampled
         in-kernel to ``size``."""
-        if targets.shape[1] != self.num_superpixel:
-            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        _check_superpixels(targets, self.num_superpixel)
         if size is None:
             size = superpixels.shape[-2:]
         wo_proto = self._honours_weight_wo_proto and bool(getattr(self.args, 'weight_wo_proto', False))
@@ -424,7 +438,7 @@ class LocalProtoCE(nn.Module):
     def forward_lowres(self, zq_p, featq, zq, size, targets, superpixels, spmasks):
         """``zq_p`` [N,C,h,w] / ``featq`` [N,Ch,h,w]: logits and normalised point features of the eval-mode forward
         (``net.feat_forward_quarter``); ``zq`` [N,C,h,w]: the training-mode logits (``net(images, lowres=True)``); ``size`` = (H, W)."""
-        size = (int(size[0]), int(size[1]))
+        size = _hw(size)
         weight, labels = self.generate_plbl(zq_p, featq, targets, superpixels, spmasks, size=size)
         return self._loss(zq, size, labels, weight)
 
@@ -475,8 +489,7 @@ class JointLocalProtoWeightingCE(nn.Module):
 
     def __init__(self, args, num_superpixel, temperature=1.0, reduction='mean'):
         super().__init__()
-        if reduction != 'mean':
-            raise NotImplementedError("only reduction='mean' exists (the reference asserts it)")
+        _mean_only(reduction, "only reduction='mean' exists (the reference asserts it)")
         self.args = args
         self.num_superpixel = num_superpixel
         self.ce_temp = args.ce_temp
@@ -487,8 +500,7 @@ class JointLocalProtoWeightingCE(nn.Module):
 
     def soft_weights(self, inputs_plbl, feats_plbl, targets, superpixels, spmasks, size=None, simw_temp=None):
         """(softw f32 [N,C,H,W], defined on the candidate planes of the valid pixels; live int32 [N]; bits int32 [N,S])"""
-        if targets.shape[1] != self.num_superpixel:
-            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        _check_superpixels(targets, self.num_superpixel)
         if size is None:
             size = superpixels.shape[-2:]
         tau = self.args.simw_temp if simw_temp is None else simw_temp
@@ -507,7 +519,7 @@ class JointLocalProtoWeightingCE(nn.Module):
         return self._loss(inputs, inputs.shape[-2:], superpixels, spmasks, softw, live, bits)
 
     def forward_lowres(self, zq_p, featq, zq, size, targets, superpixels, spmasks, simw_temp=None):
-        size = (int(size[0]), int(size[1]))
+        size = _hw(size)
         softw, live, bits = self.soft_weights(zq_p, featq, targets, superpixels, spmasks, size=size, simw_temp=simw_temp)
         return self._loss(zq, size, superpixels, spmasks, softw, live, bits)
 
@@ -541,10 +553,7 @@ class _TeacherLossFn(torch.autograd.Function):
 
 
 def _teacher_run(z, zt, size, targets, superpixels, spmasks, temp, temp_x, plbl_th, flags, sync):
-    if targets.dtype != torch.uint8:
-        targets = targets.to(torch.uint8)
-    size = None if size is None else (int(size[0]), int(size[1]))
-    return _TeacherLossFn.apply(z, zt, size, targets.contiguous(), superpixels, spmasks, ops.inv_temperature(temp),
+    return _TeacherLossFn.apply(z, zt, _hw(size), _u8(targets), superpixels, spmasks, ops.inv_temperature(temp),
                                 ops.inv_temperature(temp_x), float(plbl_th), flags, sync)
 
 
@@ -557,8 +566,7 @@ class MultiChoiceEnt_(nn.Module):
 
     def __init__(self, num_class, temperature=1.0, reduction='mean'):
         super().__init__()
-        if reduction != 'mean':
-            raise NotImplementedError("only reduction='mean' is on the hot path")
+        _mean_only(reduction)
         self.num_class = num_class
         self.reduction = reduction
         self.eps = 1e-8
@@ -616,12 +624,9 @@ class FusedTeacherTermLoss(nn.Module):
         super().__init__()
         if term not in ('top1', 'ent'):
             raise ValueError("term must be 'top1' or 'ent', got %r" % (term,))
-        if group_temperature != multi_temperature:
-            raise ValueError("the fused scan shares one softmax: group_ce_temp must equal multi_ce_temp "
-                             "(both 0.1 in the reference scripts)")
         self.num_superpixel = num_superpixel
         self.term = term
-        self.temp = multi_temperature
+        self.temp = _shared_temperature(group_temperature, multi_temperature)
         self.term_temp = term_temperature
         self.plbl_th = filtering_threshold
         self.sync_normalisers = sync_normalisers
@@ -629,8 +634,7 @@ class FusedTeacherTermLoss(nn.Module):
                                                        _lib.LOSS_TOP1 | (_lib.LOSS_WITHIN if within_filtering else 0))
 
     def _run(self, z, zt, size, targets, superpixels, spmasks):
-        if targets.shape[1] != self.num_superpixel:
-            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        _check_superpixels(targets, self.num_superpixel)
         if (zt is None) != (self.term == 'ent'):
             raise ValueError("the top1 term needs the teacher's logits, the entropy takes none")
         pos, _, group, x, self.last_acc = _teacher_run(z, zt, size, targets, superpixels, spmasks, self.temp, self.term_temp, self.plbl_th,
@@ -672,10 +676,7 @@ class _WGroupLossFn(torch.autograd.Function):
 def _wgroup_run(z, zt, size, targets, superpixels, spmasks, temp, flags, sync):
     if zt is None:
         raise ValueError("the weighted group term needs the teacher's logits")
-    if targets.dtype != torch.uint8:
-        targets = targets.to(torch.uint8)
-    size = None if size is None else (int(size[0]), int(size[1]))
-    return _WGroupLossFn.apply(z, zt, size, targets.contiguous(), superpixels, spmasks, ops.inv_temperature(temp), flags, sync)
+    return _WGroupLossFn.apply(z, zt, _hw(size), _u8(targets), superpixels, spmasks, ops.inv_temperature(temp), flags, sync)
 
 
 class WeightedGroupMultiLabelCE(GroupMultiLabelCE_):
@@ -694,8 +695,7 @@ class WeightedGroupMultiLabelCE(GroupMultiLabelCE_):
         return _lib.LOSS_GROUP | _lib.LOSS_WGROUP | (_lib.LOSS_GROUP_ONLY_MULTI if self.ignore_only_single else 0)
 
     def _run(self, z, zt, size, targets, superpixels, spmasks):
-        if targets.shape[1] != self.num_superpixel:
-            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        _check_superpixels(targets, self.num_superpixel)
         _, _, group, self.last_acc = _wgroup_run(z, zt, size, targets, superpixels, spmasks, self.temp, self._f(), self.sync_normalisers)
         return group
 
@@ -715,17 +715,13 @@ class FusedWGroupLoss(nn.Module):
 
     def __init__(self, num_superpixel, group_temperature=1.0, multi_temperature=1.0, group_only_single=False, sync_normalisers=True):
         super().__init__()
-        if group_temperature != multi_temperature:
-            raise ValueError("the fused scan shares one softmax: group_ce_temp must equal multi_ce_temp "
-                             "(both 0.1 in the reference scripts)")
         self.num_superpixel = num_superpixel
-        self.temp = multi_temperature
+        self.temp = _shared_temperature(group_temperature, multi_temperature)
         self.sync_normalisers = sync_normalisers
         self.flags = _lib.LOSS_CE | _lib.LOSS_GROUP | _lib.LOSS_WGROUP | (_lib.LOSS_GROUP_ONLY_MULTI if group_only_single else 0)
 
     def _run(self, z, zt, size, targets, superpixels, spmasks):
-        if targets.shape[1] != self.num_superpixel:
-            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
+        _check_superpixels(targets, self.num_superpixel)
         pos, _, group, self.last_acc = _wgroup_run(z, zt, size, targets, superpixels, spmasks, self.temp, self.flags, self.sync_normalisers)
         return pos, group
 
@@ -799,12 +795,9 @@ class HierGroupMultiLabelCE(nn.Module):
         self.last_bits = None
 
     def _run(self, z, size, targets, spmasks, superpixels, superpixel_smalls):
-        if targets.shape[1] != self.num_superpixel:
-            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
-        if targets.dtype != torch.uint8:
-            targets = targets.to(torch.uint8)
-        bits = ops.target_bits(targets.contiguous(), targets.shape[-1] - 1)
-        size = None if size is None else (int(size[0]), int(size[1]))
+        _check_superpixels(targets, self.num_superpixel)
+        bits = ops.target_bits(_u8(targets), targets.shape[-1] - 1)
+        size = _hw(size)
         loss, self.last_acc, cleared = _HierGroupFn.apply(z, size, bits, superpixels, superpixel_smalls, self.num_small_superpixel, spmasks,
                                                           self.only_single, self._nocropsp, self.sync_normalisers)
         self.last_bits = cleared if self._nocropsp else bits
@@ -825,7 +818,7 @@ class HierGroupMultiLabelCE(nn.Module):
         term saw in its last call."""
         if self.last_bits is None:
             raise RuntimeError("merged_positive reads the bits of the last forward; call the loss first")
-        size = None if size is None else (int(size[0]), int(size[1]))
+        size = _hw(size)
         ce, _, _, _ = _PartialLossFn.apply(inputs, size, self.last_bits, None, superpixels, spmasks, ops.inv_temperature(temperature),
                                            _lib.LOSS_CE, self.sync_normalisers)
         return ce
@@ -888,13 +881,10 @@ class AsyncHierGroupMultiLabelCE(HierGroupMultiLabelCE):
                                          self.num_small_superpixel, spmasks_weak.contiguous(), bits, weight_reduce=self._weight_reduce)
 
     def _run(self, z, size, zw, size_weak, targets, spmasks, spmasks_weak, superpixels_weak, superpixel_smalls, spx_smalls_weak):
-        if targets.shape[1] != self.num_superpixel:
-            raise ValueError("targets carry %d superpixels, loss was built for %d" % (targets.shape[1], self.num_superpixel))
-        if targets.dtype != torch.uint8:
-            targets = targets.to(torch.uint8)
-        bits = ops.target_bits(targets.contiguous(), targets.shape[-1] - 1)
-        size = None if size is None else (int(size[0]), int(size[1]))
-        size_weak = None if size_weak is None else (int(size_weak[0]), int(size_weak[1]))
+        _check_superpixels(targets, self.num_superpixel)
+        bits = ops.target_bits(_u8(targets), targets.shape[-1] - 1)
+        size = _hw(size)
+        size_weak = _hw(size_weak)
         self.last_tables = tab = self._tables(zw, size_weak, bits, spmasks_weak, superpixels_weak, spx_smalls_weak)
         loss, self.last_acc = _AsyncHierFn.apply(z, size, superpixel_smalls, self.num_small_superpixel, spmasks, tab['mult'], tab['any'],
                                                  tab['wgt'], self.sync_normalisers)

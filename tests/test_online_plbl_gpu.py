@@ -311,3 +311,53 @@ def test_trainer_runs_two_steps_with_fresh_pseudo_labels():
     # lambda of step 0 is ramp_up(0) = 0: the first train-loss is coeff * pos
     first = seen['meters'][0]
     assert abs(float(first['train-loss']) - 16.0 * float(first['pos-loss'])) <= 1e-5 * abs(float(first['train-loss']))
+
+
+def test_freeze_bn_holds_across_the_pseudo_label_forward():
+    """two steps of active_onlineplbl_multi_predignore with ``args.freeze_bn``: every BatchNorm is in eval mode before and after each
+    pseudo-label forward while the root trains, the parameters move, the meters are finite"""
+    _gpu()
+    import importlib
+    from mulactseg_amd import dataloader
+    from mulactseg_amd.utils import common
+    method = 'active_onlineplbl_multi_predignore'
+    a = common.get_parser().parse_args([
+        '-m', 'deeplabv3pluswn_resnet50deepstem', '--separable_conv', '--method', method, '--ce_temp', '0.1', '--multi_ce_temp', '0.1',
+        '--group_ce_temp', '0.1', '--coeff', '16.0', '--or_labeling', '--fair_counting', '--nseg', str(TS), '--train_batch_size', '2',
+        '--val_batch_size', '1', '--num_workers', '0', '--val_num_workers', '0', '--train_lr', '2e-4', '--finetune_itrs', '2',
+        '--val_period', '1000', '--log_period', '1', '--dorampup', '--lamscale', '2.0', '-p', tempfile.mkdtemp()])
+    a.pretrained_backbone = False
+    a.freeze_bn = True
+    dataloader.register_dataset_factory(lambda args, name, data_root, datalist, imageset: _Val())
+    torch.manual_seed(0)
+    tr = importlib.import_module("mulactseg_amd.trainer." + method).ActiveTrainer(a, logging.getLogger("test"), 1)
+    bns = [m for m in tr.net.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+    seen = dict(modes=[], meters=[])
+    plf, meter = tr.pseudo_label_forward, tr.update_average_meter
+
+    def modes():
+        return tr.net.training, [m.training for m in bns]
+
+    def pseudo_label_forward(images, lowres):
+        before = modes()
+        out = plf(images, lowres)
+        seen['modes'].append((before, modes()))
+        return out
+
+    def update_average_meter(values):
+        seen['meters'].append({k: v.detach().clone() for k, v in values.items()})
+        return meter(values)
+
+    tr.pseudo_label_forward, tr.update_average_meter = pseudo_label_forward, update_average_meter
+    tr._wandb_log = lambda payload, step: None
+    start = [p.detach().clone() for p in tr.net.parameters()]
+    tr.train(types.SimpleNamespace(selection_iter=1, get_trainset=lambda: _Train()))
+    assert bns and len(seen['modes']) == 2
+    for before, after in seen['modes']:
+        assert before == after == (True, [False] * len(bns))
+    assert modes() == (True, [False] * len(bns))
+    assert len(seen['meters']) == 2
+    for m in seen['meters']:
+        assert list(m) == ['train-loss', 'pos-loss', 'local-proto-loss'] and all(bool(torch.isfinite(v)) for v in m.values())
+    moved = sum(float((p.detach() - q).abs().sum()) for p, q in zip(tr.net.parameters(), start))
+    assert moved > 0 and np.isfinite(moved)
