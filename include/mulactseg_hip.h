@@ -65,7 +65,7 @@ extern "C" {
  * MAS_LOSS_WITHIN flag bits (the mas_partial_loss_* entry points answer MAS_ERR_RANGE to them), then mas_wgroup_loss_fwd / _bwd and
  * mas_wgroup_loss_reference with the MAS_LOSS_WGROUP flag bit (a library built before them answers MAS_ERR_RANGE to the bit), then
  * mas_hier_group_fwd / _value / _bwd and mas_hier_group_reference, then mas_async_hier_work_bytes / _tables / _fwd / _value / _bwd and
- * mas_async_hier_reference, and mas_train_augment_maps: new entry
+ * mas_async_hier_reference, and mas_train_augment_maps, then mas_within_eval_work_bytes / _counts / _reference: new entry
  * points change no existing signature or argument; a library built before them lacks their symbols, and load() refuses it with a
  * rebuild message rather than binding a partial table. */
 #define MAS_ABI_VERSION 9
@@ -1149,6 +1149,39 @@ int mas_adamw_max_groups(void);
 unsigned mas_adamw_job(void* job_host, float* p, const float* g, float* m, float* v, long long n, int group, unsigned first_block);
 int mas_adamw_multi(const void* jobs_dev, int njobs, unsigned nblocks, const float* lr_host, int ngroups, double beta1, double beta2, double eps,
                     double weight_decay, float* step_dev, const float* skip_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Quality of the local-prototype pseudo labels inside the queried superpixels of the labelled set
+ * (trainer/eval_cosplbl_within_multihot.py:84-179, eval_cosplbl_filt_within_multihot.py:68-173, eval_maxcosplbl_within_multihot.py:71-176,
+ * eval_ensemble_plbl_within_multihot.py).  Per-pixel arithmetic: csrc/within_eval.h.
+ *
+ * mas_within_eval_counts: one call per batch, no host round trip.  zq [N,C,h,w] are the quarter-resolution logits of the eval-mode
+ * forward, featq [N,Ch,h,w] its L2-normalised point features; both are interpolated per pixel to (H, W) in registers, neither
+ * full-resolution tensor exists.  A pixel is valid when its mask byte is set, its id lies in [0, S) and bits[n, id] != 0 (one-hot rows
+ * count).  The prototype of (n, s, c), c in bits[n, s], is the valid pixel of s with the largest softmax(up(zq))[c] at temperature 1,
+ * ties to the lowest pixel index: the table of mas_partial_loss_fwd_lowres with MAS_LOSS_GROUP, which this call runs.  A valid pixel
+ * takes the candidate class whose prototype feature has the largest inner product (a sequential fma chain over the channels) with its
+ * own, candidates in ascending class order, replaced on strict '>'.  mode MAS_WE_PROTO: that label.  MAS_WE_FILT: the label survives
+ * only where it equals the first arg-max of up(zq) over all C channels, then every prototype pixel takes its own class, the highest
+ * when it is the prototype of several.  Every other pixel is 255 (a selected superpixel with an empty row makes the reference raise).
+ * counts [3K+3] += what mas_iou_counts adds for that label map against gt int64 [N,H,W] with ignore_label (C <= K <= MAS_MAX_CLASSES);
+ * diag [4] += {valid pixels, table entries with a prototype, valid pixels whose winning inner product is below
+ * max_c (c in bits ? up(zq)[c] : 0), valid pixels labelled under MAS_WE_PROTO and 255 under MAS_WE_FILT}.  labels u8 [N,H,W] or NULL
+ * (never written).  Ranges as mas_online_plbl_labels; `work`: mas_within_eval_work_bytes(N, S, C) bytes, 8-byte aligned, not
+ * initialised by the caller.  Every check happens before the first launch.
+ *
+ * mas_within_eval_reference: the CPU-side statement, HOST pointers only, a plain loop through csrc/within_eval.h; counts and diag are
+ * added to as by the device call; gmax u64 [N,S,C] (the table) may be NULL.  The kernel is tested against it bit for bit. */
+#define MAS_WE_PROTO 0
+#define MAS_WE_FILT 1
+size_t mas_within_eval_work_bytes(int N, int S, int C);
+int mas_within_eval_counts(const float* zq, const float* featq, int Ch, int h, int w, const void* spx, int spx_dtype, const uint8_t* mask,
+                           const uint32_t* bits, int N, int C, int H, int W, int S, const int64_t* gt, int mode, int K,
+                           int64_t ignore_label, void* work, size_t work_bytes, uint64_t* counts /* [3K+3] += */,
+                           uint64_t* diag /* [4] += */, uint8_t* labels /* [N,H,W] or NULL */, void* stream);
+int mas_within_eval_reference(const float* zq, const float* featq, int Ch, int h, int w, const void* spx, int spx_dtype,
+                              const uint8_t* mask, const uint32_t* bits, int N, int C, int H, int W, int S, const int64_t* gt, int mode,
+                              int K, int64_t ignore_label, uint64_t* counts, uint64_t* diag, uint8_t* labels, uint64_t* gmax);
 
 #ifdef __cplusplus
 }

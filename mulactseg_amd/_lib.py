@@ -34,6 +34,7 @@ OPL_WEIGHT_WO_PROTO = 1                 # mas_online_plbl_labels: a prototype pi
 OPL_WEIGHT_SIM = 2                      # ... the weight is the inner product with the chosen prototype (LocalsimWProtoCE)
 LCE_UNWEIGHTED, LCE_WEIGHTED, LCE_THRESHOLD, LCE_EMPTY_NAN = 0, 1, 2, 4     # mas_label_ce_*: the weight mode, and NaN for an empty mean
 LCE_SIGNED = 8                          # mas_label_ce_*: weights may be negative, the sum is two's complement
+WE_PROTO, WE_FILT = 0, 1                # mas_within_eval_*: the nearest-prototype label, or that label filtered by the model's arg-max
 PM_BRIGHTNESS, PM_CONTRAST, PM_SATURATION, PM_HUE = 0, 1, 2, 3
 ABI_VERSION = 9        # MAS_ABI_VERSION of include/mulactseg_hip.h this table was written against (load() refuses any other library)
 
@@ -209,6 +210,10 @@ SIGNATURES = {
     "mas_async_hier_bwd": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mas_async_hier_reference": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mas_within_eval_work_bytes": (_c.c_size_t, [_i, _i, _i]),
+    "mas_within_eval_counts": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i64, _vp, _c.c_size_t, _vp, _vp,
+                                    _vp, _vp]),
+    "mas_within_eval_reference": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

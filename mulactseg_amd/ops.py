@@ -710,16 +710,17 @@ def _weight_flags(weight_wo_proto, weight_sim):
     return (_lib.OPL_WEIGHT_WO_PROTO if weight_wo_proto else 0) | (_lib.OPL_WEIGHT_SIM if weight_sim else 0)
 
 
-def _plbl_args(zq_p, featq, size, spx, mask, targets, bits):
-    """What both online per-pixel entry points take: the checked arguments up to S in call order, the work buffer and its size, the
-    (N, C, H, W) of the outputs, ``bits``, and the tensors behind the pointers that the caller holds until it has made the call."""
+def _plbl_args(zq_p, featq, size, spx, mask, targets, bits, work_bytes="mas_online_plbl_work_bytes"):
+    """What the per-pixel prototype entry points take: the checked arguments up to S in call order, the work buffer (sized by the entry
+    point's own ``work_bytes`` function) and its size, the (N, C, H, W) of the outputs, ``bits``, and the tensors behind the pointers
+    that the caller holds until it has made the call."""
     _need(zq_p, "inputs_plbl", torch.float32)
     _need(featq, "feats_plbl", torch.float32)
     _need(spx, "superpixels")
     mask = _mask_u8(mask)
     bits = _need(_plbl_bits(targets, bits), "bits", torch.int32)
     N, C, h, w, H, W, Ch, S = _plbl_shapes(zq_p, featq, size, spx, mask, bits)
-    nbytes = int(_lib.load().mas_online_plbl_work_bytes(N, S, C))
+    nbytes = int(getattr(_lib.load(), work_bytes)(N, S, C))
     work = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=zq_p.device)  # (zeroed inside the call)
     head = (zq_p.data_ptr(), featq.data_ptr(), Ch, h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(), bits.data_ptr(), N, C, H, W, S)
     return head, (work.data_ptr(), work.numel() * 8), (N, C, H, W), bits, (mask, work)
@@ -868,6 +869,85 @@ def online_plbl_reference(zq_p, featq, size, spx, mask, targets=None, bits=None,
         if fix is not None:
             out['dzq_fix'] = fix
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# local-prototype label quality inside the queried superpixels (csrc/within_eval.hip)
+# ------------------------------------------------------------------------------------------------
+WE_MODES = {'proto': _lib.WE_PROTO, 'filt': _lib.WE_FILT}
+
+
+def _we_mode(mode):
+    try:
+        return WE_MODES[mode]
+    except KeyError:
+        raise ValueError("mode must be 'proto' or 'filt', got %r" % (mode,))
+
+
+def _we_classes(num_classes, C):
+    K = C if num_classes is None else int(num_classes)
+    if K < C or K > _lib.MAX_CLASSES:
+        raise ValueError("num_classes must lie in [C = %d, %d], got %d" % (C, _lib.MAX_CLASSES, K))
+    return K
+
+
+def within_multihot_eval(zq, featq, size, spx, mask, gt, targets=None, bits=None, mode='proto', num_classes=None, ignore_label=255,
+                         counts=None, diag=None, want_labels=False):
+    """The label generation of the reference's ``eval_cosplbl_within_multihot`` family (``trainer/eval_cosplbl_within_multihot.py:
+    84-179``; ``mode='filt'``: ``eval_cosplbl_filt_within_multihot.py:162-169``) and ``MeanIoU._after_step`` on its result, for the whole
+    batch in ONE library call: ``zq`` [N,C,h,w] quarter-resolution logits of the eval-mode forward, ``featq`` [N,Ch,h,w] its
+    L2-normalised point features, both interpolated to ``size`` = (H, W) per pixel inside the kernel; ``spx`` / ``mask`` / ``gt``
+    (int64) [N,H,W]; ``targets`` u8 [N,S,cols] or ready ``bits`` int32 [N,S].  A selected pixel of a superpixel with a non-empty row
+    takes the candidate class with the nearest local prototype; every other pixel is 255.  Adds to ``counts`` int64 [3K+3]
+    (K = ``num_classes`` >= C, default C) what ``iou_counts`` adds for that map, and to ``diag`` int64 [4] the valid pixels, the
+    prototypes, the valid pixels whose winning similarity is below ``max_c (logit_c * Y_c)``, and the labels the filter removed.
+    Returns (counts, diag, labels u8 [N,H,W] or None); the label map exists only with ``want_labels``."""
+    head, work, (N, C, H, W), bits, _keep = _plbl_args(zq, featq, size, spx, mask, targets, bits, "mas_within_eval_work_bytes")
+    _need(gt, "labels", torch.int64)
+    if tuple(gt.shape) != (N, H, W):
+        raise ValueError("ground truth %s does not match the size %s" % (tuple(gt.shape), (N, H, W)))
+    K, dev = _we_classes(num_classes, C), zq.device
+    if counts is None:
+        counts = torch.zeros(3 * K + 3, dtype=torch.int64, device=dev)
+    if diag is None:
+        diag = torch.zeros(4, dtype=torch.int64, device=dev)
+    _need(counts, "counts", torch.int64)
+    _need(diag, "diag", torch.int64)
+    if counts.numel() != 3 * K + 3 or diag.numel() != 4:
+        raise ValueError("counts must hold 3K+3 = %d and diag 4 elements" % (3 * K + 3))
+    labels = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if want_labels else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mas_within_eval_counts(*head, gt.data_ptr(), _we_mode(mode), K, int(ignore_label), *work, counts.data_ptr(),
+                                                      diag.data_ptr(), _opt(labels), _stream(zq)), "mas_within_eval_counts")
+    return counts, diag, labels
+
+
+def within_multihot_reference(zq, featq, size, spx, mask, gt, targets=None, bits=None, mode='proto', num_classes=None, ignore_label=255,
+                              counts=None, diag=None):
+    """``within_multihot_eval`` on HOST tensors: the library's plain loop through csrc/within_eval.h (``mas_within_eval_reference``),
+    the CPU-side statement of the arithmetic the kernel is checked against.  Needs no GPU.  Returns a dict: counts, diag, labels (u8,
+    always), gmax (the arg-pixel table)."""
+    for t in (zq, featq, spx, mask, gt, bits, targets, counts, diag):
+        if t is not None and (t.is_cuda or not t.is_contiguous()):
+            raise ValueError("within_multihot_reference takes contiguous host tensors")
+    if zq.dtype != torch.float32 or featq.dtype != torch.float32 or gt.dtype != torch.int64:
+        raise TypeError("logits and features must be float32, the ground truth int64")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    bits = _plbl_bits_host(targets, bits)
+    N, C, h, w, H, W, Ch, S = _plbl_shapes(zq, featq, size, spx, mask, bits)
+    if tuple(gt.shape) != (N, H, W):
+        raise ValueError("ground truth %s does not match the size %s" % (tuple(gt.shape), (N, H, W)))
+    K = _we_classes(num_classes, C)
+    counts = torch.zeros(3 * K + 3, dtype=torch.int64) if counts is None else counts
+    diag = torch.zeros(4, dtype=torch.int64) if diag is None else diag
+    labels = torch.empty((N, H, W), dtype=torch.uint8)
+    gmax = torch.zeros((N, S, C), dtype=torch.int64)
+    _lib.check(_lib.load().mas_within_eval_reference(zq.data_ptr(), featq.data_ptr(), Ch, h, w, spx.data_ptr(), _id_code(spx), mask.data_ptr(),
+                                                     bits.data_ptr(), N, C, H, W, S, gt.data_ptr(), _we_mode(mode), K, int(ignore_label),
+                                                     counts.data_ptr(), diag.data_ptr(), labels.data_ptr(), gmax.data_ptr()),
+               "mas_within_eval_reference")
+    return dict(counts=counts, diag=diag, labels=labels, gmax=gmax)
 
 
 def online_soft_weights(zq_p, featq, size, spx, mask, targets=None, bits=None, invT=1.0, inv_tau=1.0):

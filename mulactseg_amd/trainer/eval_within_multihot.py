@@ -12,6 +12,7 @@ from .base import BaseTrainer
 class ActiveTrainer(BaseTrainer):
     predicts_ignore = True
     extra_channels = 1          # the "undefined" channel of the Cityscapes models; 0 in the VOC twin (..._voc.py:21)
+    meter_class = MeanIoU       # what ``inference`` counts with; a generator whose kernel counts by itself names its own
 
     def __init__(self, args, logger, selection_iter):
         self.selection_iter = selection_iter
@@ -53,7 +54,7 @@ class ActiveTrainer(BaseTrainer):
         return self.top_pseudo_label_generation(labels, outputs, targets, spmasks, superpixels)
 
     def inference(self, loader, prefix=''):
-        meter = MeanIoU(self.num_classes + 1, self.args.ignore_idx)
+        meter = self.meter_class(self.num_classes + 1, self.args.ignore_idx)
         meter._before_epoch()
         self.net.eval()
         with torch.no_grad():

@@ -10,6 +10,8 @@ on the device (``csrc/metrics.hip``) instead of 19 x 3 host-synchronising reduct
 registers: the full-resolution logits never exist.
 ``MultiScaleLogitsIoU`` (new): the same counters of the mean logits of scaled and flipped copies of a picture, from their
 quarter-resolution logits in one launch.
+``WithinMultihotIoU`` (new): the counters of the local-prototype labels inside the queried superpixels, from the quarter-resolution
+logits and features in one call; neither the labels nor a full-resolution tensor need exist.
 The only host synchronisation is in ``_after_epoch`` / ``total_*`` (one copy of 3C+3 integers).
 """
 import numpy as np
@@ -161,3 +163,26 @@ class MultiScaleLogitsIoU(LogitsIoU):
     def step_ms(self, logits_q, sizes, flips, labels):
         ops.ms_iou_counts([z.contiguous() for z in logits_q], sizes, flips, labels.shape[-2:], labels.contiguous(), self.num_classes,
                           self.ignore_label, self._ensure(logits_q[0].device))
+
+
+class WithinMultihotIoU(MeanIoU):
+    """``MeanIoU`` of the local-prototype labels inside the queried superpixels (``trainer/eval_cosplbl_within_multihot.py:84-179`` and
+    its ``filt`` sibling): ``step_within(zq, featq, spx, mask, targets, labels, mode)`` counts what ``_after_step`` counts on the label
+    map those generate from ``feat_forward``'s tensors, from the quarter-resolution logits and features (``ops.within_multihot_eval``).
+    ``diag`` int64 [4] on the device, added to by every step: valid pixels, prototypes, valid pixels whose winning similarity is below
+    ``max_c (logit_c * Y_c)``, labels removed by the filter."""
+
+    diag = None
+
+    def _before_epoch(self):
+        super()._before_epoch()
+        self.diag = None
+
+    def step_within(self, zq, featq, spx, mask, targets, labels, mode='proto', want_labels=False):
+        if self.diag is None:
+            self.diag = torch.zeros(4, dtype=torch.int64, device=zq.device)
+        targets = targets if targets.dtype == torch.uint8 else targets.to(torch.uint8)
+        return ops.within_multihot_eval(zq.contiguous(), featq.contiguous(), labels.shape[-2:], spx.contiguous(), mask.contiguous(),
+                                        labels.contiguous(), targets=targets.contiguous(), mode=mode, num_classes=self.num_classes,
+                                        ignore_label=self.ignore_label, counts=self._ensure(zq.device), diag=self.diag,
+                                        want_labels=want_labels)[2]
